@@ -1,21 +1,34 @@
 #!/usr/bin/env python3
 """Benchmark of the SPH step path: particle-steps/s of the `-m time` loop
-(main.cpp:68-76: N x simulateAndTime from the reference initial condition) plus
-the computeDensity roofline figures and the CPU-oracle baseline.
+(main.cpp:68-76: N x simulateAndTime from the reference initial condition).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N>1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
 
 A "step" is one simulateAndTime(): grid build + density + force/integrate +
 position read-back.  Warm-up steps run first, then the initial condition is
 re-uploaded so the K timed steps are steps 1..K of the reference's run (work per
 step grows as the fluid settles).  Prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (its
+`kernel_ms_per_step` and `roofline` come from the timed run's own HIP events).
+--full adds everything that takes runs of its own: the untimed pair-count replay
+(valu_frac figures), the linked-list and fast-math legs, the 100-step loop
+(`full_run_100`), the other BASELINE configurations (`other_configs`) and the
+CPU-oracle baseline.
+
+--dump-outputs DIR writes what the timed path returned in its last step -- the
+positions getPosition() hands the caller, (n, 3) float32 -- as DIR/positions.npy
+(a fixed, seeded sample of rows when the array exceeds 64 MB).  The inputs are the
+reference's deterministic initial condition, so two builds compare output for output.
 """
 import argparse
 import json
 import os
 import sys
 import time
+
+import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
@@ -27,6 +40,12 @@ DENSITY_BYTES_PER_PARTICLE = 20  # read 12-B position, write rho +
 DENSITY_LANEOPS_PER_TEST = 12    # SURVEY.md 8d convention (per candidate pair test)
 FORCE_LANEOPS_PER_PAIR = 55      # SURVEY.md 8d convention (per evaluated pair body)
 FULL_RUN_STEPS = 100             # main.cpp:69: the -m time loop is 100 x simulateAndTime
+# --full: the legs that repeat the timed window (pair-count replay, linked-list and fast-math legs)
+# cover at most its first 100 steps.  Past the 100 steps the fluid piles up on the floor and a step
+# costs tens of ms (the linked-list sweep seconds), so longer windows would not finish in bounded time.
+SECONDARY_MAX_STEPS = FULL_RUN_STEPS
+DUMP_MAX_BYTES = 64 * 10**6      # --dump-outputs: at most 64 MB in all
+DUMP_SAMPLE_SEED = 20240601      # fixed seed of the row sample of a larger output
 
 
 def parse():
@@ -65,15 +84,26 @@ def parse():
     ap.add_argument("--cpu-steps", type=int, default=12,
                     help="oracle steps timed for cpu_baseline (0 = skip)")
     ap.add_argument("--cpu-particles", type=int, default=0, help="0 = same n as the GPU run")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run what takes runs of its own: the pair-count replay, the linked-list and "
+                         "fast-math legs, the 100-step loop, the other configurations and the CPU baseline "
+                         "(off: set up, warm up, time --steps steps, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the positions of the last timed step as DIR/positions.npy (float32)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 def cpu_baseline(n, random_init, steps):
     """The CPU oracle (kind 'port': the reference has no CPU path and its CUDA
     source cannot be built here) on the host's cores, bounded sample.  A GPU box
     gives a job a CPU share smaller than the core count it reports, so two team
-    sizes are timed -- 16 threads and every reported core -- and the faster one is
-    the baseline (`cores` = the threads of that run)."""
+    sizes are timed -- 16 threads and the job's allotment (OMP_NUM_THREADS, else every
+    reported core) -- and the faster one is the baseline (`cores` = the threads of that run)."""
     from oracle import oracle as O
     build = O.use_native_build()  # BASELINE.md section 3: -O3 -march=native -fopenmp, built on this host
 
@@ -87,8 +117,11 @@ def cpu_baseline(n, random_init, steps):
         sim.close()
         return dt
 
+    # the second team size is the job's CPU allotment where OMP_NUM_THREADS states it, else
+    # every reported core
     ncpu = os.cpu_count() or 1
-    legs = {t: run(t) for t in sorted({min(16, ncpu), ncpu})}
+    allot = int(os.environ.get("OMP_NUM_THREADS", "0") or 0)
+    legs = {t: run(t) for t in sorted({min(16, ncpu), min(allot, ncpu) if allot > 0 else ncpu})}
     threads, dt = min(legs.items(), key=lambda kv: kv[1])
     out = {"value": n * steps / dt, "unit": "particle-steps/s", "cores": threads,
            "kind": "port", "steps": steps, "build": build,
@@ -110,10 +143,12 @@ def cpu_baseline(n, random_init, steps):
     return out
 
 
-def timed_run(sph, _lib, torch, s, args, K, W, device, settle=0, sweep=None, math=None, mode=None):
+def timed_run(sph, _lib, torch, s, args, K, W, device, settle=0, sweep=None, math=None, mode=None,
+              keep_positions=False):
     """K x simulateAndTime (or simulate) from the reference initial condition, after `settle` +
     W untimed steps and a re-upload of the initial condition.  Returns elapsed seconds, the
-    accumulated HIP-event kernel times, the -m time table and the wall time after every step."""
+    accumulated HIP-event kernel times, the -m time table and the wall time after every step
+    (keep_positions: and a copy of the last step's positions, taken after the clock stopped)."""
     sweep = sweep or args.sweep
     math = math or args.math
     mode = mode or args.mode
@@ -157,6 +192,11 @@ def timed_run(sph, _lib, torch, s, args, K, W, device, settle=0, sweep=None, mat
         print("step walls (ms): " + " ".join("%.2f" % ((w - p0) * 1e3) for w, p0 in zip(walls, [0.0] + walls[:-1])),
               file=sys.stderr)
     out = dict(elapsed=elapsed, kt=sim.kernel_times(), times=times, walls=walls)
+    if keep_positions:
+        # what getPosition() hands the caller after the last step; with --readback none the
+        # host buffer is not refreshed, so the positions are read from the device instead
+        pos = sim.download_state()["pos"] if args.readback == "none" else sim.getPosition()
+        out["positions"] = np.array(pos, dtype=np.float32, copy=True)
     if os.environ.get("SPH_STAMPS"):
         out["stamps"] = sim.debug_counters()
     sim.close()
@@ -276,6 +316,7 @@ def run_mgpu_bench(args, dist, rank, world, local_rank):
     if dist is not None:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    positions = np.array(mg.getPosition(), dtype=np.float32, copy=True) if args.dump_outputs else None
     st = mg.stats()
     local = st.local_slabs
     from cudafluidsimulator_amd import SphKernelTimes
@@ -287,6 +328,8 @@ def run_mgpu_bench(args, dist, rank, world, local_rank):
                          overflow_rounds=int(st.overflow_rounds),
                          kernel_ms_per_step_per_slab=[st.kernel_s[k] / max(st.steps, 1) * 1e3 for k in range(local)],
                          owned=[int(st.owned[k]) for k in range(local)]))
+    if positions is not None:
+        out["positions"] = positions
     mg.close()
     return out
 
@@ -310,6 +353,21 @@ def load_traffic(n, args, steps):
     except Exception:
         return None
     return None
+
+
+def dump_outputs(directory, arrays):
+    """DIR/<name>.npy of every array, float32 as computed; an output larger than the
+    64 MB budget is replaced by a fixed, seeded sample of its rows (same rows every run)."""
+    os.makedirs(directory, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_MAX_BYTES and len(a) > 0:
+            row_bytes = a.nbytes // len(a)
+            keep = max(1, min(len(a), int(DUMP_MAX_BYTES * a.nbytes / total) // row_bytes))
+            rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(len(a), size=keep, replace=False))
+            sys.stderr.write(f"bench.py: {name}: {keep} of {len(a)} rows written (seeded sample)\n")
+            a = a[rows]
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a))
 
 
 def main():
@@ -367,11 +425,13 @@ def main():
         s = sph.default_settings(n, random_init)
         # the timed run carries no counting code at all (SPH_FLAG_COUNT_PAIRS adds atomics
         # to the density sweep); pair tests and hits come from an untimed replay below
-        result = timed_run(sph, _lib, torch, s, args, K, W, local_rank, settle=RUNTIME_SETTLE_STEPS)
+        result = timed_run(sph, _lib, torch, s, args, K, W, local_rank, settle=RUNTIME_SETTLE_STEPS,
+                           keep_positions=bool(args.dump_outputs))
         result["n_total"] = n
-        if not args.no_count_replay:
+        KS = min(K, SECONDARY_MAX_STEPS)   # steps of the secondary legs below
+        if args.full and not args.no_count_replay and K <= SECONDARY_MAX_STEPS:
             result.update(count_replay(sph, _lib, s, args, K, local_rank))
-        if args.sweep == "list" and args.math == "strict" and not args.no_linked_leg:
+        if args.full and args.sweep == "list" and args.math == "strict" and not args.no_linked_leg:
             # secondary figure: the reference's own neighbour structure (per-cell
             # linked lists, no sort) on this GPU, same K steps (not `value`)
             lsim = sph.Simulator(s, sweep="linked", device=local_rank)
@@ -384,13 +444,14 @@ def main():
             lt = sph.Times()
             torch.cuda.synchronize()
             l0 = time.perf_counter()
-            for _ in range(K):
+            for _ in range(KS):
                 lsim.simulateAndTime(lt) if args.mode == "time" else lsim.simulate()
             lsim.sync()
             result["linked_elapsed"] = time.perf_counter() - l0
+            result["linked_steps"] = KS
             result["linked_kt"] = lsim.kernel_times()
             lsim.close()
-        if args.math == "strict" and args.sweep not in ("direct", "linked") and not args.no_fast_leg:
+        if args.full and args.math == "strict" and args.sweep not in ("direct", "linked") and not args.no_fast_leg:
             # secondary figure: the same K steps in SPH_MATH_FAST (not `value`)
             fsim = sph.Simulator(s, sweep=args.sweep, device=local_rank, math="fast")
             fsim.setup()
@@ -401,16 +462,17 @@ def main():
             fsim.setup()
             torch.cuda.synchronize()
             f0 = time.perf_counter()
-            for _ in range(K):
+            for _ in range(KS):
                 fsim.simulateAndTime(ft) if args.mode == "time" else fsim.simulate()
             fsim.sync()
             result["fast_elapsed"] = time.perf_counter() - f0
+            result["fast_steps"] = KS
             fsim.close()
-        if not args.no_extra_legs and args.mode == "time" and args.readback == "copy":
+        if args.full and not args.no_extra_legs and args.mode == "time" and args.readback == "copy":
             # The metric BASELINE.json names is the 100-step loop of main.cpp:68-76.  Whatever K the
             # command line asked for, the full loop runs too (0.2 s) and is reported as `full_run_100`.
             if K == FULL_RUN_STEPS:
-                result["full100"] = dict(result)
+                result["full100"] = {k: v for k, v in result.items() if k != "positions"}
             else:
                 r100 = timed_run(sph, _lib, torch, s, args, FULL_RUN_STEPS, min(W, 5), local_rank)
                 if not args.no_count_replay:
@@ -455,7 +517,8 @@ def main():
             "full_run_note": None if full else (
                 f"steps 1..{K} only: work per step grows 4.7x over the 100 steps (pressure and floor "
                 "contact start at step ~45), so this is not the 100-step figure: that one is `full_run_100` "
-                "below, measured in this same process"),
+                + ("below, measured in this same process" if "full100" in result else
+                   "of a --full run")),
             "value": result["n_total"] * K / elapsed,
             "unit": "particle-steps/s",
             "n_gpus": world, "steps": K, "warmup": W,
@@ -495,26 +558,31 @@ def main():
             out["m_time_table_s"] = {"grid_construction": t.buildGrid, "sph_update": t.sphUpdate,
                                      "data_transfer_exposed": t.memcpy}
         if "fast_elapsed" in result:
-            out["fast_math"] = {"value": result["n_total"] * K / result["fast_elapsed"],
-                                "unit": "particle-steps/s",
+            fk = result["fast_steps"]
+            out["fast_math"] = {"value": result["n_total"] * fk / result["fast_elapsed"],
+                                "unit": "particle-steps/s", "steps": fk,
                                 "note": "SPH_MATH_FAST (FMA + approximate rcp/rsq): not bit-exact; max relative "
                                         "position error 8.1e-7 after 100 steps of -n 8192 -i grid vs the oracle "
                                         "(north-star tolerance 1e-5; tests/test_gpu_parity.py). Not `value`."}
         if "linked_elapsed" in result:
             lk = result["linked_kt"]
             lst = max(int(lk.steps), 1)
+            lk_steps = result["linked_steps"]
             out["reference_structure"] = {
-                "value": result["n_total"] * K / result["linked_elapsed"], "unit": "particle-steps/s",
-                "ms_per_step": result["linked_elapsed"] / K * 1e3,
+                "value": result["n_total"] * lk_steps / result["linked_elapsed"], "unit": "particle-steps/s",
+                "ms_per_step": result["linked_elapsed"] / lk_steps * 1e3, "steps": lk_steps,
                 "kernel_ms_per_step": {"grid": (lk.hash + lk.sort + lk.gather) / lst * 1e3,
                                        "density": lk.density / lst * 1e3,
                                        "force_integrate": lk.force / lst * 1e3},
                 "note": "SPH_SWEEP_LINKED: the reference's main-branch neighbour structure (one atomically "
                         "built linked list per cell, no sort; simulator.cu:44-55,133-147) written for this "
                         "GPU with the library's float4 streams -- the closest thing to 'the reference's "
-                        "algorithm on MI355X' that can be run (the CUDA source cannot). Same K steps, same "
-                        "input; summation order is a race, results match the oracle to 1e-5 relative "
+                        "algorithm on MI355X' that can be run (the CUDA source cannot). The first `steps` of "
+                        "the same run (at most 100), same input; summation order is a race, results match the oracle to 1e-5 relative "
                         "(tests/test_gpu_linked.py). Not `value`."}
+        if args.full and world == 1 and K > SECONDARY_MAX_STEPS and not args.no_count_replay:
+            roof["valu_frac_note"] = (f"no pair-count replay of a {K}-step window (the replay covers at most "
+                                      f"{SECONDARY_MAX_STEPS} steps): see full_run_100")
         tr = load_traffic(result["n_total"], args, steps=K) if world == 1 else None
         if tr:
             roof["traffic"] = tr["bytes_per_launch"]
@@ -531,7 +599,7 @@ def main():
                                               else "LOOPBACK: N slabs on one GPU, device-to-device copies"))
             if world == 1:
                 out["config"]["parallelism"] = f"LOOPBACK: {args.loopback_slabs} z-slabs on ONE GPU (decomposition cost study)"
-        if args.cpu_steps > 0 and world == 1:  # rank 0 at N=1 only
+        if args.full and args.cpu_steps > 0 and world == 1:  # rank 0 at N=1 only
             out["cpu_baseline"] = cpu_baseline(args.cpu_particles or n, random_init, args.cpu_steps)
             # the GPU over the SAME window (steps 1..cpu_steps of the same run), from the per-step wall
             # times of a timed loop above (-m time waits for the compute stream after every step)
@@ -542,6 +610,8 @@ def main():
                     "value": n * args.cpu_steps / w, "unit": "particle-steps/s",
                     "ratio": n * args.cpu_steps / w / out["cpu_baseline"]["value"],
                     "window": f"steps 1..{args.cpu_steps} of the same run, wall time of the -m time loop"}
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"positions": result["positions"]})
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(out) + "\n").encode())
 

@@ -1,6 +1,6 @@
 #!/bin/bash
 # One round's evidence for the bench line, all from the SAME bench command line
-# (bench.py --steps K --warmup W): the plain bench line, the rocprofv3 kernel-trace
+# (bench.py --steps K --warmup W): the --full bench line, the rocprofv3 kernel-trace
 # stats, and the HBM traffic counters (FETCH_SIZE / WRITE_SIZE in separate --pmc
 # passes, as MI355X_MICROARCH.md prescribes).  Summaries land in gpurun_out/TAG/;
 # copy what should be judged into profiles/.
@@ -9,7 +9,7 @@ set -o pipefail
 TAG=$1; K=$2; W=$3; shift 3
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG; mkdir -p $OUT; export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
-timeout -k 10 400 python bench.py --steps $K --warmup $W "$@" > $OUT/bench.json 2> $OUT/bench.err; echo "bench exit $?"
+timeout -k 10 400 python bench.py --steps $K --warmup $W --full "$@" > $OUT/bench.json 2> $OUT/bench.err; echo "bench exit $?"
 cd /tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o bench -- python3 $GRAFT_REPO_ROOT/bench.py --steps $K --warmup $W --cpu-steps 0 --no-linked-leg --no-fast-leg --no-count-replay --no-extra-legs "$@" > $OUT/prof_bench.json 2> $OUT/prof.err; echo "rocprof exit $?"
 # averages over the TIMED steps only (the last K dispatches of each kernel: settle and warm-up
