@@ -30,9 +30,6 @@
 #define RS_SMALL_N (3 << 19)
 #endif
 #define RS_WAVES (RS_THREADS / SPH_WAVE)
-#ifndef RS_HIST_BALLOT
-#define RS_HIST_BALLOT 0 // 1: count with the scatter's ballot match (A/B)
-#endif
 
 // Lanes of this wave whose digit equals mine (among valid lanes).
 template <int BITS>
@@ -157,10 +154,6 @@ __global__ __launch_bounds__(RS_THREADS *RS_ITEMS / RS_HIST_ITEMS) void k_radix_
         const long long idx = base + r * SPH_WAVE;
         const bool valid = idx < n;
         const uint32_t d = (key[r] >> shift) & (DIG - 1);
-#if RS_HIST_BALLOT
-        unsigned long long mm = match_digit<BITS>(d, valid);
-        if (valid && lanes_below(mm) == 0) atomicAdd(&hist[d], (uint32_t)__popcll(mm));
-#else
         const uint32_t dprev = __shfl_up(d, 1);
         const unsigned long long live = __ballot(valid); // a prefix of the wave: lanes [0, count)
         const unsigned long long heads = __ballot(valid && (lane == 0 || d != dprev));
@@ -170,7 +163,6 @@ __global__ __launch_bounds__(RS_THREADS *RS_ITEMS / RS_HIST_ITEMS) void k_radix_
             const int end = above ? __builtin_ctzll(above) : (int)__popcll(live);
             atomicAdd(&hist[d], (uint32_t)(end - lane));
         }
-#endif
     }
     __syncthreads();
     for (int d = t; d < DIG; d += HT) blockHist[(size_t)d * numBlocks + blockIdx.x] = hist[d];

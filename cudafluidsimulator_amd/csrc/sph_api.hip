@@ -33,7 +33,7 @@ thread_local std::string g_create_error;
 
 constexpr int kEventRing = 64;
 constexpr int kCounterWords = 16 + 256 * 16; // 16 spare words, then 256 shards x 16: [0] pair tests,
-                                             // [1..13] in-kernel stamps (diagnostic builds), [15] hits
+                                             // [1..13] reserved (always zero), [14] bodies, [15] hits
 constexpr size_t kCursorBytes = (size_t)SL_POOL_SHARDS * SL_CURSOR_STRIDE * sizeof(unsigned long long);
 
 struct PairEvent { // one timed section of the slab path
@@ -746,7 +746,6 @@ SweepArgs make_sweep_args(sph_handle *h) {
     A.host_order_pos = nullptr;
     A.force_out = h->force4;
     A.pairCounter = nullptr;
-    A.stampCounter = (h->opt.flags & SPH_FLAG_COUNT_PAIRS) ? h->pairCounter : nullptr;
     A.i_begin = 0;
     A.i_end = h->n;
     A.i_origin = 0;

@@ -157,7 +157,7 @@ struct SweepArgs {
     float *host_order_pos;    // n x 3 floats by original id (may be null)
     float4 *force_out;        // optional (SPH_FLAG_STORE_FORCE)
     unsigned long long *pairCounter; // optional (SPH_FLAG_COUNT_PAIRS)
-    unsigned long long *stampCounter; // diagnostic builds only (same buffer)
+    unsigned long long *stampCounter; // unused: no kernel reads it (kept so that the fields after it keep their offsets)
     int i_begin, i_end;       // owned range (whole array for one domain)
     int i_origin;             // list sweep: particle 0 of wave 0 of the hit stream (the density
                               // sweep's i_begin); a force launch may cover a sub-range of it

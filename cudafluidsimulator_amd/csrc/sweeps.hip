@@ -12,8 +12,9 @@
 // ranges of the sorted stream ("runs": cells x-1..x+1 of row (y+dy, z+dz)),
 // visited in ascending order -- which is the canonical summation order.
 //
-// Production variant (SPH_SWEEP_LDS): every 64-lane wave is autonomous (no
-// workgroup barrier).  It owns 64 consecutive sorted particles, groups its
+// LDS variant (SPH_SWEEP_LDS; the production sweep, SPH_SWEEP_LIST in
+// sweeps_list.hip, stages its density walk the same way): every 64-lane wave is
+// autonomous (no workgroup barrier).  It owns 64 consecutive sorted particles, groups its
 // lanes by grid row, and for each of the nine runs stages the UNION of its
 // lanes' ranges into its private LDS slice in chunks of SW_CAP float4
 // (coalesced 16-B loads -> ds_write_b128), then each lane walks ITS OWN
@@ -104,38 +105,13 @@ __global__ __launch_bounds__(SW_THREADS) void k_force_direct(DevParams P, SweepA
     store_particle(A, i, pi, vx, vy, vz, vi.w, F);
 }
 
-// =====================  LDS variant (production)  ============================
+// =====================  LDS variant  ========================================
 // Walks the nine runs of the lanes of one wave.  The inner loop is branch-free
 // and unrolled by SW_UNROLL: each trip issues SW_UNROLL ds_read_b128 up front and
 // calls V.candidate(j, pj) for every lane; a lane that has run out of candidates
 // reads the SENTINEL slot (a point 1e18 away: it fails every radius test), so no
 // per-lane exec masking is needed.  V.poll() is called wave-uniformly once per
 // trip.
-// In-kernel phase stamps (diagnostic builds only: -DSW_STAMPS=1).  Sums of
-// s_memtime deltas per phase go to counters 1.. of A.pairCounter; the shipped
-// build executes none of this.
-#ifndef SW_STAMPS
-#define SW_STAMPS 0
-#endif
-#if SW_STAMPS
-__device__ __forceinline__ unsigned long long sw_stamp() {
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return t;
-}
-#define SW_STAMP(var) unsigned long long var = sw_stamp()
-#else
-#define SW_STAMP(var)
-#endif
-struct WalkStamps {
-    unsigned long long stage = 0, test = 0;
-};
-
-#ifndef SW_PIPELINE
-#define SW_PIPELINE 1
-#endif
 // Negative results kept out of the code (measured on MI355X, n = 4,194,304):
 //  * streaming the next run with global_load_lds (LDS-DMA) while the current one
 //    is tested: density 1.29 ms vs 0.98 ms -- hipcc drains lgkmcnt(0) on every LDS
@@ -153,8 +129,7 @@ template <class Visitor>
 __device__ __forceinline__ void wave_walk(const SweepArgs &A, float4 *__restrict__ stage,
                                           int lane, bool valid, int rowId,
                                           const int (&js)[9], const int (&je)[9],
-                                          Visitor &V, WalkStamps &W) {
-    (void)W;
+                                          Visitor &V) {
     if (lane < SW_UNROLL) stage[SW_SENTINEL + lane] = make_float4(1e18f, 1e18f, 1e18f, 0.f);
     unsigned long long todo = __ballot(valid);
     while (todo) {
@@ -182,15 +157,10 @@ __device__ __forceinline__ void wave_walk(const SweepArgs &A, float4 *__restrict
             const int u0 = __builtin_amdgcn_readlane(jsr, lo);
             const int u1 = __builtin_amdgcn_readlane(jer, hi);
             for (int cs = u0; cs < u1; cs += SW_CAP) {
-                SW_STAMP(tA);
                 const int len = min(SW_CAP, u1 - cs);
                 for (int k = lane; k < len; k += SPH_WAVE) stage[k] = A.pos4[cs + k];
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
-#if SW_STAMPS
-                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-#endif
-                SW_STAMP(tB);
                 const int a = nonempty ? max(jsr, cs) - cs : 0;      // first local slot
                 const int b = nonempty ? min(jer, cs + len) - cs : 0; // one past last
                 // per-lane cursor: LDS slot, candidates left, global index
@@ -198,10 +168,12 @@ __device__ __forceinline__ void wave_walk(const SweepArgs &A, float4 *__restrict
                 const float4 *const sent = stage + SW_SENTINEL;
                 int rem = max(b - a, 0);
                 int jcur = cs + a;
-#if SW_PIPELINE
                 // Software-pipelined by one trip: the ds_read_b128 of trip t+1 are
                 // in flight while trip t is evaluated, so the wave does not park on
-                // LDS latency once per trip (two register sets, A and B).
+                // LDS latency once per trip (two register sets, A and B).  Exhausted
+                // lanes read sentinel slot u (the +u folds into the ds_read offset
+                // field), and .w is kept live so each read is one ds_read_b128 (4 LDS
+                // cycles per wave) instead of the ds_read_b96 (8 cycles) hipcc would pick.
                 float4 pa[SW_UNROLL], pb[SW_UNROLL];
 #define SW_ISSUE(dst, remv, curv)                                              \
     _Pragma("unroll") for (int u = 0; u < SW_UNROLL; ++u) {                    \
@@ -228,32 +200,8 @@ __device__ __forceinline__ void wave_walk(const SweepArgs &A, float4 *__restrict
                 }
 #undef SW_ISSUE
 #undef SW_CONSUME
-#else
-                for (; __ballot(rem > 0); rem -= SW_UNROLL, cur += SW_UNROLL, jcur += SW_UNROLL) {
-                    float4 pj[SW_UNROLL];
-#pragma unroll
-                    for (int u = 0; u < SW_UNROLL; ++u) {
-                        // exhausted lanes read sentinel slot u (the +u folds into the
-                        // ds_read offset field either way)
-                        const float4 *p = (rem > u) ? cur : sent;
-                        pj[u] = p[u];
-                    }
-#pragma unroll
-                    for (int u = 0; u < SW_UNROLL; ++u) V.candidate(jcur + u, pj[u]);
-                    // keep .w live so each read is one ds_read_b128 (4 LDS cycles per
-                    // wave) instead of the ds_read_b96 (8 cycles) hipcc would pick
-#pragma unroll
-                    for (int u = 0; u < SW_UNROLL; ++u) asm volatile("" ::"v"(pj[u].w));
-                    V.poll();
-                }
-#endif
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
-#if SW_STAMPS
-                SW_STAMP(tC);
-                W.stage += tB - tA;
-                W.test += tC - tB;
-#endif
             }
         }
     }
@@ -290,7 +238,6 @@ __global__ __launch_bounds__(SW_THREADS) void k_density_lds(DevParams P, SweepAr
     __shared__ float4 stageAll[SW_WAVES][SW_CAP + SW_UNROLL];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     float4 *stage = stageAll[w];
-    SW_STAMP(t0);
     const int i = A.i_begin + xcd_tile(blockIdx.x, gridDim.x, A.tileChunk, A.tileRotate) * blockDim.x + threadIdx.x;
     const bool valid = i < A.i_end;
     float4 pi = valid ? A.pos4[i] : make_float4(0, 0, 0, 0);
@@ -305,35 +252,15 @@ __global__ __launch_bounds__(SW_THREADS) void k_density_lds(DevParams P, SweepAr
         if (lane == 0) atomicAdd(A.pairCounter, (unsigned long long)s);
     }
     DensityVisitor<FAST> V{P, pi.x, pi.y, pi.z, 0.f};
-    WalkStamps W;
-#if SW_STAMPS
-    asm volatile("" ::"v"(js[0] + je[8]));
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-#endif
-    SW_STAMP(t1);
-    wave_walk(A, stage, lane, valid, c.y + c.z * P.D, js, je, V, W);
+    wave_walk(A, stage, lane, valid, c.y + c.z * P.D, js, je, V);
     if (valid) {
         float rho = fmaxf(V.rho, SPH_EPS_F);
         A.vel4[i].w = rho;
     }
-#if SW_STAMPS
-    SW_STAMP(t2);
-    if (lane == 0 && A.pairCounter) { // 256 shards: same-address atomics would distort
-        unsigned long long *S = A.pairCounter + 16 + (blockIdx.x & 255) * 16;
-        atomicAdd(S + 1, t1 - t0);  // prologue
-        atomicAdd(S + 2, W.stage);  // staging (global -> LDS) incl. waits
-        atomicAdd(S + 3, W.test);   // test loops
-        atomicAdd(S + 4, t2 - t0);  // whole wave
-        atomicAdd(S + 5, 1ull);     // waves
-    }
-#endif
 }
 
 #ifndef SW_DRAIN
 #define SW_DRAIN 4 // FIFO entries evaluated per drain (loads of all issued first)
-#endif
-#ifndef SW_PUSH_BRANCHFREE
-#define SW_PUSH_BRANCHFREE 1 // measured: force sweep 2.47 ms vs 2.55 ms (n = 4,194,304)
 #endif
 
 template <bool FAST, bool SLIM>
@@ -346,8 +273,6 @@ struct ForceVisitor {
     float pix, piy, piz, vix, viy, viz, prs_i;
     uint32_t head, tail;
     ForceAcc F;
-    unsigned long long drains = 0;
-    uint32_t items = 0; // diagnostic: FIFO entries really evaluated by this lane
 
     __device__ __forceinline__ void candidate(int j, float4 pj) {
         float dx = pix - pj.x;
@@ -355,27 +280,17 @@ struct ForceVisitor {
         float dz = piz - pj.z;
         float dist2 = FAST ? __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx))
                            : dx * dx + dy * dy + dz * dz;
-#if SW_PUSH_BRANCHFREE
         // the slot at `tail` is always free here (poll() keeps SW_UNROLL slots
-        // spare), so store unconditionally and only advance on a hit
+        // spare), so store unconditionally and only advance on a hit (measured
+        // against a push behind a branch: force sweep 2.47 ms vs 2.55 ms, n = 4,194,304)
         queue[(tail & (SW_QCAP - 1)) * SPH_WAVE + lane] = (uint32_t)j;
         tail += !(dist2 > P.cut2) ? 1u : 0u;
-#else
-        if (!(dist2 > P.cut2)) {
-            queue[(tail & (SW_QCAP - 1)) * SPH_WAVE + lane] = (uint32_t)j;
-            ++tail;
-        }
-#endif
     }
     // Pop up to SW_DRAIN hits per lane, issue all their loads, then evaluate them
     // in FIFO order.  An empty slot is replaced by the particle itself, whose
     // pair terms are gated off by dist < EPS_F -- an exact no-op.
     __device__ __forceinline__ void drain() {
         const uint32_t have = tail - head;
-#if SW_STAMPS
-        ++drains;
-        items += min(have, (uint32_t)SW_DRAIN);
-#endif
         uint32_t j[SW_DRAIN];
         float4 pj[SW_DRAIN], vj[SW_DRAIN];
 #pragma unroll
@@ -409,7 +324,6 @@ __global__ __launch_bounds__(SW_THREADS) void k_force_lds(DevParams P, SweepArgs
     __shared__ float4 stageAll[SW_WAVES][SW_CAP + SW_UNROLL];
     __shared__ uint32_t queueAll[SW_WAVES][SW_QCAP * SPH_WAVE];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    SW_STAMP(t0);
     const int i = A.i_begin + xcd_tile(blockIdx.x, gridDim.x, A.tileChunk, A.tileRotate) * blockDim.x + threadIdx.x;
     const bool valid = i < A.i_end;
     const int iSafe = valid ? i : A.i_begin; // i_end > i_begin whenever we are launched
@@ -421,37 +335,13 @@ __global__ __launch_bounds__(SW_THREADS) void k_force_lds(DevParams P, SweepArgs
     ForceVisitor<FAST, SLIM> V{P, A, queueAll[w], lane, (uint32_t)iSafe, pi.x, pi.y, pi.z, vi.x, vi.y, vi.z,
                    fmaxf(0.f, SPH_GAS_CONSTANT * (vi.w - SPH_REST_DENSITY)),
                    0u, 0u, {0.f, 0.f, 0.f}};
-    WalkStamps W;
-#if SW_STAMPS
-    asm volatile("" ::"v"(js[0] + je[8]));
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-#endif
-    SW_STAMP(t1);
-    wave_walk(A, stageAll[w], lane, valid, c.y + c.z * P.D, js, je, V, W);
-    SW_STAMP(t2);
+    wave_walk(A, stageAll[w], lane, valid, c.y + c.z * P.D, js, je, V);
     V.flush();
-    SW_STAMP(t3);
     if (valid) {
         float vx = vi.x, vy = vi.y, vz = vi.z;
         integrate_particle(P, pi, vx, vy, vz, V.F, vi.w);
         store_particle(A, i, pi, vx, vy, vz, vi.w, V.F);
     }
-#if SW_STAMPS
-    SW_STAMP(t4);
-    if (lane == 0 && A.stampCounter) {
-        unsigned long long *S = A.stampCounter + 16 + (blockIdx.x & 255) * 16;
-        atomicAdd(S + 6, t1 - t0);   // prologue
-        atomicAdd(S + 7, W.stage);   // staging
-        atomicAdd(S + 8, W.test);    // test loops incl. drains they trigger
-        atomicAdd(S + 9, t3 - t2);   // final flush
-        atomicAdd(S + 10, t4 - t0);  // whole wave
-        atomicAdd(S + 11, V.drains); // drain() calls
-    }
-    if (A.stampCounter) {
-        uint32_t it = wave_sum_u32(V.items);
-        if (lane == 0) atomicAdd(A.stampCounter + 16 + (blockIdx.x & 255) * 16 + 12, (unsigned long long)it);
-    }
-#endif
 }
 
 void sph_launch_density(const DevParams &P, const SweepArgs &A, int mathMode, int sweep,

@@ -22,53 +22,19 @@
 #define SL_NONE 0xFFFFFFFFu
 // SL_POOL_SHARDS / SL_CURSOR_STRIDE live in sph_device.h (the host sizes the cursor array)
 
-// In-kernel phase stamps (diagnostic builds only: -DSW_STAMPS=1), as in sweeps.hip.
-#ifndef SW_STAMPS
-#define SW_STAMPS 0
-#endif
-#if SW_STAMPS
-__device__ __forceinline__ unsigned long long sl_stamp() {
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return t;
-}
-#define SL_STAMP(var) unsigned long long var = sl_stamp()
-#else
-#define SL_STAMP(var)
-#endif
 #ifndef SL_WINDOW
-#define SL_WINDOW 160 // records around the wave's own particles cached in LDS by the force sweep
-                      // (0 = off).  Measured: 1.60 -> 1.49 ms with 128; 160 or 192 another 1 %
-                      // (5 KiB per wave still leaves six waves per SIMD); 256 records or three
-                      // rows (12 KiB per wave) lose more to occupancy than they save.
+#define SL_WINDOW 160 // records around a wave's own particles cached in LDS by the force sweep
+                      // (measured with one wave per workgroup: 1.60 -> 1.49 ms with 128; 160 or
+                      // 192 another 1 % (5 KiB per wave still leaves six waves per SIMD); 256
+                      // records or three rows (12 KiB per wave) lose more to occupancy than they
+                      // save).  The dealt sweep's window is its rows +- (SL_WINDOW - 64) / 2.
 #endif
-// Workgroup sizes of the two sweeps.  Their waves are autonomous (no workgroup barrier),
+// Workgroup size of the density sweep.  Its waves are autonomous (no workgroup barrier),
 // but a workgroup's LDS and wave slots are only handed back when its LAST wave ends, and
 // wave times differ with the hit counts: one wave per workgroup measured -1.3 % (density)
-// and -2.7 % (force) against four.
+// and -2.7 % (the force sweep before rows were dealt to lanes) against four.
 #ifndef SL_K1_THREADS
 #define SL_K1_THREADS 64
-#endif
-#ifndef SL_K2_THREADS
-#define SL_K2_THREADS 64 // k_force_list (the one-wave-per-workgroup sweep; production is k_force_dealt below)
-#endif
-#ifndef SL_EXP_LDSONLY
-#define SL_EXP_LDSONLY 0
-#endif
-#ifndef SL_TRIVIAL_TEST
-#define SL_TRIVIAL_TEST 0
-#endif
-#ifndef SL_FETCH_UNIFORM
-#define SL_FETCH_UNIFORM 0
-#endif
-#ifndef SL_LDSDMA
-#define SL_LDSDMA 0
-#endif
-#ifndef SL_PV8
-#define SL_PV8 1 // gather one interleaved 32-B (pos4, vel4) record per hit: measured
-                 // force sweep 1.80 -> ~1.55 ms (two loads, ONE cache line per lane)
 #endif
 
 // ---------------------------------------------------------------------------
@@ -94,9 +60,6 @@ __device__ __forceinline__ unsigned long long sl_stamp() {
 // Per wave header: maskOff[2w] = base in quads (or SL_NONE: pool exhausted ->
 // k_force_fallback), maskOff[2w+1] = Q.
 // ---------------------------------------------------------------------------
-#ifndef SL_ADDC
-#define SL_ADDC 1
-#endif
 #ifndef SL_K1_WAVES
 #define SL_K1_WAVES 6 // resident waves per SIMD asked for (caps the VGPR budget at 80); measured: 5..8 the same
 #endif
@@ -143,20 +106,11 @@ __device__ __forceinline__ int wave_max_i32(int v) {
 // density term needs anyway, and one v_alignbit_b32 shifts it in (miss = 1; the word is
 // complemented when it is handed over) instead of a compare and an add-with-carry.
 template <bool FAST, bool SAMECUT>
-__global__
-#if SL_K1_WAVES
-__launch_bounds__(SL_K1_THREADS, SL_K1_WAVES * SL_K1_THREADS / 64)
-#else
-__launch_bounds__(SL_K1_THREADS)
-#endif
+__global__ __launch_bounds__(SL_K1_THREADS, SL_K1_WAVES * SL_K1_THREADS / 64)
 void k_density_mask_lds(DevParams P, SweepArgs A) {
     __shared__ float4 stageAll[SL_K1_THREADS / SPH_WAVE][SW_CAP + SW_UNROLL];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     float4 *stage = stageAll[w];
-    SL_STAMP(t0);
-#if SW_STAMPS
-    unsigned long long accStage = 0, accTest = 0;
-#endif
     const int wv = xcd_tile(blockIdx.x, gridDim.x, A.tileChunk * (256 / SL_K1_THREADS), A.tileRotate) * (SL_K1_THREADS / SPH_WAVE) + w;
     // waves are numbered from i_origin (<= i_begin, a multiple of 64 in slab mode so that a wave's
     // 64 rows are one word of the zero-pair filter's bit array); rows below i_begin are not this launch's
@@ -195,7 +149,7 @@ void k_density_mask_lds(DevParams P, SweepArgs A) {
         if (!ok) A.noneList[atomicAdd(A.maskCursor + 1, 1ull)] = (uint32_t)wv; // (for k_force_fallback)
     }
     uint4 *const myq = reinterpret_cast<uint4 *>(A.maskPool) + (ok ? base : 0ull) + lane;
-    if (A.pairCounter) { // sharded like the stamps: one address would serialise the waves
+    if (A.pairCounter) { // sharded: one address would serialise the waves
         uint32_t s = wave_sum_u32(pairs);
         if (lane == 0) atomicAdd(A.pairCounter + 16 + (wv & 255) * 16, (unsigned long long)s);
     }
@@ -203,11 +157,6 @@ void k_density_mask_lds(DevParams P, SweepArgs A) {
     if (lane < SW_UNROLL) stage[SW_CAP + lane] = make_float4(1e18f, 1e18f, 1e18f, 0.f);
     const float4 *const sent = stage + SW_CAP;
     float rho = 0.f;
-#if SW_STAMPS
-    asm volatile("" ::"v"(js[0] + je[8]));
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-#endif
-    SL_STAMP(t1);
     // VALU ops with an SGPR or literal source issue at half rate on gfx950
     // (scripts/microbench/valu_rate.hip): the loop constants live in VGPRs
     float h2v = P.h2, dcv = P.dcoef, cut2r = P.cut2, massv = SPH_MASS;
@@ -226,11 +175,8 @@ void k_density_mask_lds(DevParams P, SweepArgs A) {
                 pm0 = mask;
                 pending = true;
             } else {
-#if defined(SL_DBG_SAMEADDR) // (perf-only experiments: what the hit stream's stores cost the density sweep)
-                myq[0] = make_uint4(pj0, pm0, jbase, mask);
-#elif !defined(SL_DBG_NOEMIT) // (measured, round 3: a non-temporal store here: density 1.44 vs 1.35 ms at steps 81..100)
+                // (measured, round 3: a non-temporal store here: density 1.44 vs 1.35 ms at steps 81..100)
                 myq[(size_t)qidx * SPH_WAVE] = make_uint4(pj0, pm0, jbase, mask);
-#endif
                 ++qidx;
                 pending = false;
             }
@@ -297,16 +243,11 @@ void k_density_mask_lds(DevParams P, SweepArgs A) {
 #pragma unroll 1
         for (int r = 0; r < 9; ++r) {
             const Run R = describe(r, act);
-            SL_STAMP(tA);
             if (R.any && R.staged) { // the union of the wave's ranges of this run -> LDS slice
                 for (int k = lane; k < R.ulen; k += SPH_WAVE) stage[k] = A.pos4[R.u0 + k];
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
-#if SW_STAMPS
-                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-#endif
             }
-            SL_STAMP(tB);
             if (R.any) {
                 const int jsr = R.jsr, len = R.len;
                 const float4 *cur = stage + (jsr - R.u0);
@@ -340,7 +281,6 @@ void k_density_mask_lds(DevParams P, SweepArgs A) {
                             m = __builtin_amdgcn_alignbit(m, __float_as_uint(draw), 31);
                             continue;
                         }
-#if SL_ADDC
                         // hit bit shifted in through the carry: m = 2m + !(dist2 > cut2), two
                         // VALU ops per candidate instead of mov + cmp + cndmask + or.  The word
                         // fills from the top, so it is bit-reversed once when it is handed over.
@@ -348,21 +288,12 @@ void k_density_mask_lds(DevParams P, SweepArgs A) {
                             : "+v"(m)
                             : "v"(dist2), "v"(cut2r)
                             : "vcc");
-#else
-                        const uint32_t bit = 1u << ((k + u) & 31); // wave-uniform
-                        m |= !(dist2 > cut2r) ? bit : 0u;
-#endif
                     }
 #pragma unroll
                     for (int u = 0; u < SW_UNROLL; ++u) asm volatile("" ::"v"(pj[u].w));
                     if (((k + SW_UNROLL) & 31) == 0) { // a whole word is complete (wave-uniform)
                         if (SAMECUT) emit((uint32_t)(jsr + (k & ~31)), ~__builtin_bitreverse32(m));
-                        else
-#if SL_ADDC
-                            emit((uint32_t)(jsr + (k & ~31)), __builtin_bitreverse32(m));
-#else
-                            emit((uint32_t)(jsr + (k & ~31)), m);
-#endif
+                        else emit((uint32_t)(jsr + (k & ~31)), __builtin_bitreverse32(m));
                         m = 0;
                     }
                 };
@@ -391,11 +322,7 @@ void k_density_mask_lds(DevParams P, SweepArgs A) {
 #pragma unroll
                         for (int u = 0; u < SW_UNROLL; ++u) {
                             const float4 *p = (k + u < len) ? cur + k : sent;
-#if defined(SL_DBG_ONE_READ) // (perf-only: one LDS read per trip instead of four -- is the loop bound by LDS traffic?)
-                            pj[u] = u == 0 ? p[0] : make_float4(pj[0].x + (float)u, pj[0].y, pj[0].z, 0.f);
-#else
                             pj[u] = p[u];
-#endif
                         }
                         trip(pj);
                     }
@@ -413,26 +340,13 @@ void k_density_mask_lds(DevParams P, SweepArgs A) {
                 }
                 if ((k & 31) != 0) { // last, partial word
                     if (SAMECUT) emit((uint32_t)(jsr + (k & ~31)), (~__builtin_bitreverse32(m)) >> (32 - (k & 31)));
-                    else
-#if SL_ADDC
-                        emit((uint32_t)(jsr + (k & ~31)), __builtin_bitreverse32(m) >> (32 - (k & 31)));
-#else
-                        emit((uint32_t)(jsr + (k & ~31)), m);
-#endif
+                    else emit((uint32_t)(jsr + (k & ~31)), __builtin_bitreverse32(m) >> (32 - (k & 31)));
                 }
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
             }
-#if SW_STAMPS
-            {
-                SL_STAMP(tC);
-                accStage += tB - tA;
-                accTest += tC - tB;
-            }
-#endif
         }
     }
-    SL_STAMP(t2);
     if (ok && valid) { // end of this lane's sequence: a zero mask, unless all 2Q pairs are used
         if (pending) myq[(size_t)qidx * SPH_WAVE] = make_uint4(pj0, pm0, 0u, 0u);
         else if (qidx < Q) myq[(size_t)qidx * SPH_WAVE] = make_uint4(0u, 0u, 0u, 0u);
@@ -446,270 +360,6 @@ void k_density_mask_lds(DevParams P, SweepArgs A) {
     }
     if (A.quiet) sl_store_quiet(A, i, valid, rho, lane);
     if (A.hitCount && valid) A.hitCount[i] = hcount;
-#if SW_STAMPS
-    {
-        SL_STAMP(t3);
-        if (lane == 0 && A.stampCounter) {
-            unsigned long long *S = A.stampCounter + 16 + (blockIdx.x & 255) * 16;
-            atomicAdd(S + 1, t1 - t0);   // prologue (pos, cell, 27 table reads, pool slice)
-            atomicAdd(S + 2, accStage);  // staging (global -> LDS) incl. waits
-            atomicAdd(S + 3, accTest);   // test loops incl. mask hand-over
-            atomicAdd(S + 4, t3 - t0);   // whole wave
-            atomicAdd(S + 5, 1ull);      // waves
-            atomicAdd(S + 13, t3 - t2);  // final stores
-        }
-    }
-#endif
-}
-
-// ---------------------------------------------------------------------------
-// force + integrate over the recorded hits, one wave per workgroup, rows in place
-// (-DSL_DEAL=0: the A/B partner of k_force_dealt, and the home of the round-2/3 experiments)
-// ---------------------------------------------------------------------------
-// Measured dead end: non-temporal (`nt`) loads of the hit stream and stores of it in the
-// density sweep, meant to keep the stream from pushing neighbour records out of L2:
-// force sweep 1.30 -> 1.66 ms, density 1.12 -> 1.17 ms (an nt load does not keep the
-// lane's line for its next 8-byte pair either).
-#ifndef SL_K2_WAVES
-#define SL_K2_WAVES 0 // >0: ask for that many resident waves per SIMD (caps the VGPR budget)
-#endif
-template <bool FAST, bool SLIM>
-__global__
-#if SL_K2_WAVES
-__launch_bounds__(SL_K2_THREADS, SL_K2_WAVES)
-#else
-__launch_bounds__(SL_K2_THREADS)
-#endif
-void k_force_list(DevParams P, SweepArgs A) {
-    // wave w of the hit stream owns particles [i_origin + 64 w, +64); this launch covers
-    // the waves that intersect [i_begin, i_end) (a sub-range when the slab driver runs the
-    // interior while the halo densities are still in flight)
-    const bool second = (int)blockIdx.x >= A.nblk1; // wave-uniform: blocks past nblk1 serve range 2
-    const int rb = second ? A.i_begin2 : A.i_begin, re = second ? A.i_end2 : A.i_end;
-    const int tileIdx = ((rb - A.i_origin) >> 6) / (SL_K2_THREADS / SPH_WAVE) +
-                        xcd_tile(second ? (int)blockIdx.x - A.nblk1 : (int)blockIdx.x,
-                                 second ? (int)gridDim.x - A.nblk1 : A.nblk1,
-                                 A.tileChunk * (256 / SL_K2_THREADS), A.tileRotate);
-    const int i = A.i_origin + tileIdx * blockDim.x + threadIdx.x;
-    const bool valid = i >= rb && i < re;
-    const int iSafe = valid ? i : rb;
-    float4 pi = A.pv8[2 * (size_t)iSafe];
-    const float4 vi = A.pv8[2 * (size_t)iSafe + 1];
-    const float prs_i = fmaxf(0.f, SPH_GAS_CONSTANT * (vi.w - SPH_REST_DENSITY));
-    // this wave's hit stream (layout: k_density_mask_lds): Q quads per lane, quad q of
-    // this lane at stream4[q * 64] = two (first candidate, 32-bit hit mask) pairs
-    const int wv = tileIdx * (SL_K2_THREADS / SPH_WAVE) + (threadIdx.x >> 6);
-    const uint32_t baseq = __builtin_amdgcn_readfirstlane(A.maskOff[2 * (size_t)wv]);
-    const int Q = __builtin_amdgcn_readfirstlane((int)A.maskOff[2 * (size_t)wv + 1]);
-    ForceAcc F = {0.f, 0.f, 0.f};
-
-#if SL_WINDOW
-    // LDS copy of the records around the wave's own particles.  The kernel is bound
-    // by the texture addresser's gather rate (PMC: TA busy 89 %), and ~40 % of all
-    // hits are neighbours in the particle's own grid row, i.e. within a few dozen
-    // slots of the wave's 64 particles in the sorted stream: those are served by
-    // ds_read_b128 instead of a 64-address global gather.
-    __shared__ float4 winAll[SL_K2_THREADS / SPH_WAVE][2 * SL_WINDOW];
-    float4 *win = winAll[threadIdx.x >> 6];
-#if SL_LDSDMA
-    __shared__ float4 ringAll[SL_K2_THREADS / SPH_WAVE][2][2][SPH_WAVE];
-    float4(*ring)[2][SPH_WAVE] = ringAll[threadIdx.x >> 6];
-#endif
-    const int tile0 = A.i_origin + tileIdx * blockDim.x + (threadIdx.x & ~63);
-    const int w0 = max(tile0 - (SL_WINDOW - SPH_WAVE) / 2, 0);
-    const int wlen = max(min(SL_WINDOW, A.n_all - w0), 0);
-#endif
-
-    // A wave that found the mask pool exhausted has no stream: its particles are
-    // handled by k_force_fallback (kept out of this kernel: its 27 table reads and
-    // run arrays would cost two resident waves per SIMD here).
-    if (baseq == SL_NONE) return;
-    // Every row of the domain quiet (fluid in free fall): no pair adds anything -- the hit stream is
-    // not even read, the sweep is the integration alone.
-    const bool allQuiet = A.quietAll && __builtin_amdgcn_readfirstlane(*A.quietAll) != 0u &&
-                          (!A.quietHalo || __builtin_amdgcn_readfirstlane(*A.quietHalo) != 0u);
-    if (!allQuiet) {
-        // Bit cursor.  (jb, m): first candidate and remaining bits of the current
-        // pair; (jq, mq): the pairs of the last quad loaded.  A lane's sequence ends
-        // with a zero mask (or after Q quads).  pop() returns the next hit's sorted
-        // index, or the particle itself once the stream is exhausted (dist = 0 gates
-        // every term: exact no-op).
-        // (uniform base + one 32-bit per-lane quad index: a per-lane 64-bit pointer, a quad counter and a
-        // per-lane end cost three more VGPRs, and the 73rd costs the seventh resident wave)
-        const uint4 *const sbase = reinterpret_cast<const uint4 *>(A.maskPool) + baseq;
-        const uint32_t send = (uint32_t)Q * SPH_WAVE;                           // uniform: end of the wave's quads
-        uint32_t sidx = valid ? (threadIdx.x & 63u) : send;                      // this lane's next quad
-        uint32_t m = 0, mq[2] = {0u, 0u};
-        int jb = 0, jq[2] = {0, 0};
-        bool live = true;
-        // zero-pair filter: a quiet row drops its quiet candidates (see sl_is_quiet)
-        const bool qi = A.quiet && valid && ((A.quiet[i >> 5] >> (i & 31)) & 1u);
-        // post-condition: mq[0] != 0, or the lane's sequence is exhausted
-        auto fetch = [&]() {
-            while (sidx < send) {
-                uint4 t = sbase[sidx];
-                sidx = (t.w == 0u) ? send : sidx + SPH_WAVE; // a zero mask ends the sequence
-                if (qi) {
-                    t.y &= ~sl_quiet_window(A.quiet, t.x);
-                    t.w &= ~sl_quiet_window(A.quiet, t.z);
-                }
-                if (t.y == 0u) { // first pair empty (filtered, or the terminator): the second moves up
-                    t.x = t.z;
-                    t.y = t.w;
-                    t.w = 0u;
-                }
-                jq[0] = (int)t.x;
-                mq[0] = t.y;
-                jq[1] = (int)t.z;
-                mq[1] = t.w;
-                if (t.y != 0u) break;
-            }
-        };
-        fetch();
-        // A wave whose lanes have nothing left after the filter (fluid in free fall) skips the sweep:
-        // no window, no gathers, straight to the integration.
-        if (__ballot(mq[0] != 0u)) {
-#if SL_WINDOW
-        {
-            const int lane = threadIdx.x & 63;
-            for (int k = lane; k < 2 * wlen; k += SPH_WAVE) win[k] = A.pv8[2 * (size_t)w0 + k];
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-        }
-#endif
-        auto pop = [&]() -> int {
-            if (m == 0) { // next pair; queued masks are never 0, so mq[0] == 0 means "queue empty"
-                m = mq[0];
-                jb = jq[0];
-                mq[0] = mq[1];
-                jq[0] = jq[1];
-                mq[1] = 0;
-                if (mq[0] == 0) fetch();
-            }
-            live = (m | mq[0]) != 0;
-            const bool has = m != 0;
-            const int b = has ? __builtin_ctz(m) : 0;
-            m &= m - 1u; // (0 stays 0)
-            return has ? jb + b : iSafe;
-        };
-        auto body = [&](const float4 &pj, const float4 &vj) {
-            if (FAST) force_pair_fast(P, pi.x, pi.y, pi.z, vi.x, vi.y, vi.z, prs_i, pj, vj, F);
-            else force_pair<SLIM>(P, pi.x, pi.y, pi.z, vi.x, vi.y, vi.z, prs_i, pj, vj, F);
-        };
-        // Two gathers are always in flight while a pair body is evaluated: the
-        // loop is unrolled by two so the pipeline registers never move.  (Three in
-        // flight: 99 VGPRs, four resident waves, 1.24 -> 1.44 ms.)
-#if SL_EXP_LDSONLY
-        // PERF-ONLY experiment (results wrong by construction): every hit is read from the
-        // wave's LDS slice at (j mod window) -- what the sweep would cost if all records
-        // came from LDS at this LDS footprint.
-#define SL_FETCH(j, p, v)
-#define SL_USE(j, p, v)                                                        \
-    p = win[2 * ((j) & (SL_WINDOW - 1))];                                      \
-    v = win[2 * ((j) & (SL_WINDOW - 1)) + 1];                                  \
-    body(p, v);
-#elif SL_TRIVIAL_TEST
-        // experiment: a pair with no pressure on either side and no relative velocity adds
-        // exactly +-0 to the force (fPressure = -0, dv = +0): fetch the velocity half first and
-        // fetch the position half / run the body only for the other pairs (here: synchronously)
-#define SL_FETCH(j, p, v)                                                      \
-    if ((unsigned)((j)-w0) >= (unsigned)wlen) v = A.pv8[2 * (size_t)(j) + 1];
-#define SL_USE(j, p, v)                                                        \
-    {                                                                          \
-        const bool inw = (unsigned)((j)-w0) < (unsigned)wlen;                  \
-        if (inw) v = win[2 * ((j)-w0) + 1];                                    \
-        const float prs_j = fmaxf(0.f, SPH_GAS_CONSTANT * (v.w - SPH_REST_DENSITY)); \
-        const bool triv = (prs_i + prs_j == 0.f) && v.x == vi.x && v.y == vi.y && v.z == vi.z; \
-        if (!triv) {                                                           \
-            p = inw ? win[2 * ((j)-w0)] : A.pv8[2 * (size_t)(j)];              \
-            body(p, v);                                                        \
-        }                                                                      \
-    }
-#elif SL_WINDOW && SL_LDSDMA
-        // experiment: the gathers go through the LDS-DMA path -- per-lane
-        // `global_load_lds_dwordx4` into a two-slot ring in LDS (2 x 2 KB per wave), consumed by
-        // ds_read_b128 like the window's records: no VGPRs hold records in flight.
-#define SL_SLOT_p0 0
-#define SL_SLOT_p1 1
-#define SL_LDS_PTR(x) ((__attribute__((address_space(3))) void *)(x))
-#define SL_FETCH(j, p, v)                                                      \
-    if ((unsigned)((j)-w0) >= (unsigned)wlen) {                                \
-        __builtin_amdgcn_global_load_lds((const void *)(A.pv8 + 2 * (size_t)(j)), SL_LDS_PTR(&ring[SL_SLOT_##p][0][0]), 16, 0, 0); \
-        __builtin_amdgcn_global_load_lds((const void *)(A.pv8 + 2 * (size_t)(j) + 1), SL_LDS_PTR(&ring[SL_SLOT_##p][1][0]), 16, 0, 0); \
-    }
-#define SL_USE(j, p, v)                                                        \
-    {                                                                          \
-        const bool inw_ = (unsigned)((j)-w0) < (unsigned)wlen;                 \
-        const float4 *a_ = inw_ ? &win[2 * ((j)-w0)] : &ring[SL_SLOT_##p][0][threadIdx.x & 63]; \
-        const float4 *b_ = inw_ ? a_ + 1 : a_ + SPH_WAVE;                      \
-        p = *a_;                                                               \
-        v = *b_;                                                               \
-        body(p, v);                                                            \
-    }
-#elif SL_WINDOW && SL_FETCH_UNIFORM
-        // experiment: every lane issues both loads of every fetch, so the gathers are straight-line
-        // code and the compiler can wait with exact vmcnt counts (two gathers really in flight);
-        // a lane whose hit is inside the LDS window loads the window's FIRST record instead (one
-        // wave-uniform address: one line for all such lanes, not a lane-request each).
-#define SL_FETCH(j, p, v)                                                      \
-    {                                                                          \
-        const size_t a_ = ((unsigned)((j)-w0) < (unsigned)wlen) ? (size_t)w0 : (size_t)(j); \
-        p = A.pv8[2 * a_];                                                     \
-        v = A.pv8[2 * a_ + 1];                                                 \
-    }
-#define SL_USE(j, p, v)                                                        \
-    if ((unsigned)((j)-w0) < (unsigned)wlen) {                                 \
-        p = win[2 * ((j)-w0)];                                                 \
-        v = win[2 * ((j)-w0) + 1];                                             \
-    }                                                                          \
-    body(p, v);
-#elif SL_WINDOW
-        // fetch: issue the global gather only for lanes whose hit is outside the
-        // window (fewer active lanes = fewer addresses for the TA); the LDS copy is
-        // read when the hit is consumed.
-#define SL_FETCH(j, p, v)                                                      \
-    if ((unsigned)((j)-w0) >= (unsigned)wlen) {                                \
-        p = A.pv8[2 * (size_t)(j)];                                            \
-        v = A.pv8[2 * (size_t)(j) + 1];                                        \
-    }
-#define SL_USE(j, p, v)                                                        \
-    if ((unsigned)((j)-w0) < (unsigned)wlen) {                                 \
-        p = win[2 * ((j)-w0)];                                                 \
-        v = win[2 * ((j)-w0) + 1];                                             \
-    }                                                                          \
-    body(p, v);
-#else
-#define SL_FETCH(j, p, v)                                                      \
-    p = A.pv8[2 * (size_t)(j)];                                                \
-    v = A.pv8[2 * (size_t)(j) + 1];
-#define SL_USE(j, p, v) body(p, v);
-#endif
-        float4 p0 = make_float4(0, 0, 0, 0), v0 = p0, p1 = p0, v1 = p0;
-        int j0 = pop();
-        SL_FETCH(j0, p0, v0)
-        int j1 = pop();
-        SL_FETCH(j1, p1, v1)
-        for (;;) {
-            SL_USE(j0, p0, v0)
-            j0 = pop();
-            if (!__ballot(live)) { SL_USE(j1, p1, v1) SL_FETCH(j0, p0, v0) SL_USE(j0, p0, v0) break; }
-            SL_FETCH(j0, p0, v0)
-            SL_USE(j1, p1, v1)
-            j1 = pop();
-            if (!__ballot(live)) { SL_USE(j0, p0, v0) SL_FETCH(j1, p1, v1) SL_USE(j1, p1, v1) break; }
-            SL_FETCH(j1, p1, v1)
-        }
-        }
-#undef SL_FETCH
-#undef SL_USE
-    }
-    if (valid) {
-        // (measured, round 3: re-reading the id and the density here instead of keeping them alive saves
-        // two VGPRs -- 68 -- and nothing else; forcing 64 VGPRs for an eighth wave spills 8: 1.14 vs 0.83 ms)
-        float vx = vi.x, vy = vi.y, vz = vi.z;
-        integrate_particle(P, pi, vx, vy, vz, F, vi.w);
-        store_particle(A, i, pi, vx, vy, vz, vi.w, F);
-    }
 }
 
 // ---------------------------------------------------------------------------
@@ -732,10 +382,8 @@ void k_force_list(DevParams P, SweepArgs A) {
 //  * One LDS window per workgroup: the records of its own rows +- 48 (own grid row: ~40 % of all hits),
 //    staged only if one of those rows is not quiet.
 // Measured, n = 4,194,304 -i random, 100 steps: force sweep 0.812 (one wave per workgroup, rows in place)
-// -> 0.777 ms per step with 256-row groups (profiles/r03_experiments.md has every A/B).
-#ifndef SL_DEAL
-#define SL_DEAL 1
-#endif
+// -> 0.777 ms per step with 256-row groups (profiles/r03_experiments.md has every A/B).  That predecessor
+// was retired after commit 473aa9c; the notes below marked "one wave per workgroup" were measured on it.
 #ifndef SL_SORT_SHIFT
 #define SL_SORT_SHIFT 3 // 128 buckets of (1 << SL_SORT_SHIFT) hits (1 .. 6 measured the same)
 #endif
@@ -797,6 +445,9 @@ __global__ __launch_bounds__(SL_DEAL_THREADS) void k_force_dealt(DevParams P, Sw
     }
 
     // ---- the window ----
+    // The sweep is bound by the texture addresser's gather rate (PMC, one wave per workgroup: TA busy 89 %),
+    // and ~40 % of all hits are neighbours in the row's own grid row, i.e. within a few dozen slots of the
+    // group's rows in the sorted stream: those are served by ds_read_b128 instead of a 64-address global gather.
     // Every row of the domain quiet (fluid in free fall): no pair adds anything -- the hit stream is not even
     // read, the sweep is the integration alone.
     const bool allQuiet = A.quietAll && __builtin_amdgcn_readfirstlane(*A.quietAll) != 0u &&
@@ -831,7 +482,8 @@ __global__ __launch_bounds__(SL_DEAL_THREADS) void k_force_dealt(DevParams P, Sw
         const int rel = iSafe - A.i_origin;
         const uint32_t baseq = inRange ? A.maskOff[2 * (size_t)(rel >> 6)] : SL_NONE;
         const int Q = inRange ? (int)A.maskOff[2 * (size_t)(rel >> 6) + 1] : 0;
-        // (a row whose density wave found the pool exhausted has no stream: k_force_fallback integrates it)
+        // (a row whose density wave found the pool exhausted has no stream: k_force_fallback integrates it --
+        // kept out of this kernel: its 27 table reads and run arrays would cost two resident waves per SIMD here)
         const bool valid = inRange && baseq != SL_NONE;
         ForceAcc F = {0.f, 0.f, 0.f};
         if (!allQuiet) {
@@ -839,6 +491,9 @@ __global__ __launch_bounds__(SL_DEAL_THREADS) void k_force_dealt(DevParams P, Sw
             // the last quad loaded.  A lane's sequence ends with a zero mask (or after Q quads).  pop() returns the
             // next hit's sorted index, or the particle itself once the stream is exhausted (dist = 0 gates every
             // term: exact no-op).
+            // (uniform base + one 32-bit per-lane quad index, measured with one wave per workgroup: a per-lane
+            // 64-bit pointer, a quad counter and a per-lane end cost three more VGPRs, and the 73rd cost the
+            // seventh resident wave)
             const uint4 *const sbase = reinterpret_cast<const uint4 *>(A.maskPool);
             const uint32_t send = valid ? baseq + (uint32_t)Q * SPH_WAVE : 0u; // end of the row's quads
             uint32_t sidx = valid ? baseq + (uint32_t)(rel & 63) : 0u;         // this lane's next quad
@@ -848,6 +503,10 @@ __global__ __launch_bounds__(SL_DEAL_THREADS) void k_force_dealt(DevParams P, Sw
             // zero-pair filter: a quiet row drops its quiet candidates
             const bool qi = A.quiet && valid && ((A.quiet[i >> 5] >> (i & 31)) & 1u);
             // post-condition: mq[0] != 0, or the lane's sequence is exhausted
+            // (measured dead end, one wave per workgroup: non-temporal (`nt`) loads of the hit stream and stores
+            // of it in the density sweep, meant to keep the stream from pushing neighbour records out of L2:
+            // force sweep 1.30 -> 1.66 ms, density 1.12 -> 1.17 ms -- an nt load does not keep the lane's line
+            // for its next 8-byte pair either)
             auto fetch = [&]() {
                 while (sidx < send) {
                     uint4 q = sbase[sidx];
@@ -892,19 +551,15 @@ __global__ __launch_bounds__(SL_DEAL_THREADS) void k_force_dealt(DevParams P, Sw
                     else force_pair<SLIM>(P, pi.x, pi.y, pi.z, vi.x, vi.y, vi.z, prs_i, pj, vj, F);
                 };
                 // Two gathers are always in flight while a pair body is evaluated; the loop is unrolled by two so
-                // the pipeline registers never move.  A record comes EITHER from the gather (issued only by the
-                // lanes whose hit is outside the window: fewer addresses for the texture path) or from the window
-                // (read when the hit is consumed): the registers are declared undefined before the gather, or the
-                // compiler keeps "the old value where no load was issued" alive through both conditionals -- 14
-                // v_mov per pair body and a second set of record registers (70 -> 57 VGPRs).
+                // the pipeline registers never move (three in flight, one wave per workgroup: 99 VGPRs, four
+                // resident waves, 1.24 -> 1.44 ms).  A record is one interleaved 32-B (pos4, vel4) entry of pv8:
+                // two loads, ONE cache line per lane (measured against separate streams: force sweep 1.80 ->
+                // ~1.55 ms).  It comes EITHER from the gather (issued only by the lanes whose hit is outside the
+                // window: fewer addresses for the texture path) or from the window (read when the hit is
+                // consumed): the registers are declared undefined before the gather, or the compiler keeps "the
+                // old value where no load was issued" alive through both conditionals -- 14 v_mov per pair body
+                // and a second set of record registers (70 -> 57 VGPRs).
 #define SD_UNDEF4(q) asm volatile("" : "=v"(q.x), "=v"(q.y), "=v"(q.z), "=v"(q.w));
-#ifdef SD_EXP_LDSONLY // PERF-ONLY experiment (results wrong by construction): every hit is read from the window
-#define SD_FETCH(j, p, v) SD_UNDEF4(p) SD_UNDEF4(v)
-#define SD_USE(j, p, v)                                                        \
-    p = win[2 * ((unsigned)(j) % (unsigned)SL_DEAL_WINDOW)];                   \
-    v = win[2 * ((unsigned)(j) % (unsigned)SL_DEAL_WINDOW) + 1];               \
-    body(p, v);
-#else
 #define SD_FETCH(j, p, v)                                                      \
     SD_UNDEF4(p)                                                               \
     SD_UNDEF4(v)                                                               \
@@ -918,7 +573,6 @@ __global__ __launch_bounds__(SL_DEAL_THREADS) void k_force_dealt(DevParams P, Sw
         v = win[2 * ((j)-w0) + 1];                                             \
     }                                                                          \
     body(p, v);
-#endif
                 float4 p0 = make_float4(0, 0, 0, 0), v0 = p0, p1 = p0, v1 = p0;
                 int j0 = pop();
                 SD_FETCH(j0, p0, v0)
@@ -941,6 +595,9 @@ __global__ __launch_bounds__(SL_DEAL_THREADS) void k_force_dealt(DevParams P, Sw
             }
         }
         if (valid) {
+            // (measured, round 3, one wave per workgroup: re-reading the id and the density here instead of
+            // keeping them alive saves two VGPRs -- 68 -- and nothing else; forcing 64 VGPRs for an eighth wave
+            // spills 8: 1.14 vs 0.83 ms)
             float vx = vi.x, vy = vi.y, vz = vi.z;
             integrate_particle(P, pi, vx, vy, vz, F, vi.w);
             store_particle(A, i, pi, vx, vy, vz, vi.w, F);
@@ -986,7 +643,7 @@ __global__ __launch_bounds__(256) void k_count_hits(SweepArgs A) {
             for (int q = 0; q < Q; ++q) {
                 const uint4 t = q4[(size_t)q * SPH_WAVE];
                 n += (uint32_t)__builtin_popcount(t.y) + (uint32_t)__builtin_popcount(t.w);
-                if (qi) // what the zero-pair filter drops (k_force_list)
+                if (qi) // what the zero-pair filter drops (the force sweep)
                     dropped += (uint32_t)__builtin_popcount(t.y & sl_quiet_window(A.quiet, t.x)) +
                                (uint32_t)__builtin_popcount(t.w & sl_quiet_window(A.quiet, t.z));
                 if (t.w == 0u) break;
@@ -1079,13 +736,7 @@ void sph_launch_force_list(const DevParams &P, const SweepArgs &A, int mathMode,
     if (B.i_end <= B.i_begin) return;
     if (B.patchHalo) sph_launch_patch_halo(B, s);
     // groups of the stream's waves (numbered from i_origin) that hold rows of a range
-#if SL_DEAL
     const int wpb = SL_DEAL_ROWS / SPH_WAVE, threads = SL_DEAL_THREADS;
-#define SL_FORCE_KERNEL k_force_dealt
-#else
-    const int wpb = SL_K2_THREADS / SPH_WAVE, threads = SL_K2_THREADS;
-#define SL_FORCE_KERNEL k_force_list
-#endif
     auto blocks_of = [&](int a, int b) {
         if (b <= a) return 0;
         const int w0 = (a - B.i_origin) >> 6, w1 = (b - B.i_origin + 63) >> 6;
@@ -1095,14 +746,13 @@ void sph_launch_force_list(const DevParams &P, const SweepArgs &A, int mathMode,
     const int fblocks = B.nblk1 + blocks_of(B.i_begin2, B.i_end2);
     const int blocks = SL_FALLBACK_BLOCKS;
     if (mathMode == 1) {
-        SL_FORCE_KERNEL<true, true><<<fblocks, threads, 0, s>>>(P, B);
+        k_force_dealt<true, true><<<fblocks, threads, 0, s>>>(P, B);
         k_force_fallback<true, true><<<blocks, SPH_WAVE, 0, s>>>(P, B);
     } else if (P.slimDiv) { // the reference's h and kernel coefficients (sweep_common.h)
-        SL_FORCE_KERNEL<false, true><<<fblocks, threads, 0, s>>>(P, B);
+        k_force_dealt<false, true><<<fblocks, threads, 0, s>>>(P, B);
         k_force_fallback<false, true><<<blocks, SPH_WAVE, 0, s>>>(P, B);
     } else {
-        SL_FORCE_KERNEL<false, false><<<fblocks, threads, 0, s>>>(P, B);
+        k_force_dealt<false, false><<<fblocks, threads, 0, s>>>(P, B);
         k_force_fallback<false, false><<<blocks, SPH_WAVE, 0, s>>>(P, B);
     }
-#undef SL_FORCE_KERNEL
 }

@@ -178,8 +178,8 @@ int sph_num_particles(const sph_handle *h);
 int sph_num_table_cells(const sph_handle *h);
 int sph_get_kernel_times(sph_handle *h, SphKernelTimes *out, int reset);
 const char *sph_last_error(const sph_handle *h); /* h may be NULL: create errors */
-/* Diagnostics: [0] = pair tests; [1..] = in-kernel phase stamps, filled only by a
- * -DSW_STAMPS=1 build of the library (see sweeps.hip), zero otherwise. */
+/* Diagnostics: [0] = pair tests; [1..13] reserved, always zero; [14] = pair bodies the
+ * force sweep evaluated, [15] = hits recorded (SPH_FLAG_COUNT_PAIRS + SPH_SWEEP_LIST). */
 int sph_debug_counters(sph_handle *h, uint64_t *out16);
 
 /* ---- the step split into its phases (tests, profiling, slab driver) ---- */
