@@ -23,7 +23,11 @@ EXPORTED_SYMBOLS = [
     "sph_slab_force", "sph_initial_positions", "sph_save_state", "sph_load_state",
     "sph_debug_counters", "sph_get_stream", "sph_slab_partition_async", "sph_slab_sort_async",
     "sph_slab_patch_halo", "sph_slab_force_ranges", "sph_num_table_cells", "sph_slab_apply_click", "sph_slab_records",
+    "sph_render_frame", "sph_frame_host", "sph_download_frame_buffers", "sph_get_render_time", "sph_api_version",
 ]
+SPH_API_VERSION = 3
+SPH_SHADE_FLAT, SPH_SHADE_COUNT = 0, 1
+SHADES = {"flat": SPH_SHADE_FLAT, "count": SPH_SHADE_COUNT}
 
 
 class SphError(RuntimeError):
@@ -47,6 +51,11 @@ class SphOptions(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("device", C.c_int32),
                 ("math_mode", C.c_int32), ("sweep", C.c_int32), ("flags", C.c_int32),
                 ("capacity", C.c_int32), ("key_order", C.c_int32)]
+
+
+class SphRenderOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("point_size", C.c_int32), ("shade", C.c_int32)]
 
 
 class SphKernelTimes(C.Structure):
@@ -114,5 +123,11 @@ def load_library():
     L.sph_slab_partition.argtypes = [hp, C.c_int, C.c_int, C.c_int, u32p, C.c_int, i32p, C.c_void_p]
     L.sph_slab_density.argtypes = [hp, C.c_int, C.c_int, C.c_int, C.c_int]
     L.sph_slab_force.argtypes = [hp, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.sph_render_frame.argtypes = [hp, C.POINTER(SphRenderOptions)]
+    L.sph_frame_host.argtypes = [hp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.sph_frame_host.restype = C.POINTER(C.c_uint8)
+    L.sph_download_frame_buffers.argtypes = [hp, u32p, u32p, u32p]
+    L.sph_get_render_time.argtypes = [hp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]
+    L.sph_api_version.argtypes = []
     _lib = L
     return L

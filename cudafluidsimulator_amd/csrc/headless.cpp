@@ -4,6 +4,7 @@
 // Never linked together with display.cpp (duplicate symbols by design).
 #include <cstdio>
 #include <cstdlib>
+#include <string>
 
 #include "sha256.h"
 #include "simulator.h"
@@ -13,9 +14,32 @@ int2 clickCoords;
 
 extern "C" void glutInit(int *, char **) {}
 
+// SPH_FREE_FRAMES_DIR=<dir>: what the window would have shown after frame f, as <dir>/frame_%04d.ppm (binary P6)
+static bool write_frame(Simulator *simulator, const char *dir, int f) {
+    int w = 0, h = 0;
+    const unsigned char *rgb = simulator->renderFrame(&w, &h);
+    if (!rgb) return false;
+    char name[32];
+    snprintf(name, sizeof name, "/frame_%04d.ppm", f);
+    const std::string path = std::string(dir) + name;
+    FILE *out = fopen(path.c_str(), "wb");
+    if (!out) {
+        fprintf(stderr, "sph: cannot write %s\n", path.c_str());
+        return false;
+    }
+    fprintf(out, "P6\n%d %d\n255\n", w, h);
+    const size_t bytes = (size_t)w * (size_t)h * 3;
+    const bool ok = fwrite(rgb, 1, bytes, out) == bytes;
+    return (fclose(out) == 0) && ok;
+}
+
 void startVisualization(Simulator *simulator) {
     int frames = 100;
     if (const char *e = getenv("SPH_FREE_FRAMES")) frames = atoi(e);
+    const char *framesDir = getenv("SPH_FREE_FRAMES_DIR");
+    if (framesDir && !*framesDir) framesDir = NULL;
+    int every = 1;
+    if (const char *e = getenv("SPH_FREE_FRAME_EVERY")) every = atoi(e) > 0 ? atoi(e) : 1;
     fprintf(stderr, "sph: built without GLUT -- running %d frames headless\n", frames);
     for (int f = 0; f < frames; ++f) {
         if (f == frames / 2 && getenv("SPH_FREE_CLICK")) {
@@ -23,6 +47,7 @@ void startVisualization(Simulator *simulator) {
             clickCoords = make_int2(400, 300);
         }
         simulator->simulate();
+        if (framesDir && f % every == 0 && !write_frame(simulator, framesDir, f)) framesDir = NULL;
     }
     const float3 *p = simulator->getPosition();
     if (p && simulator->settings->numParticles > 0)

@@ -1,0 +1,226 @@
+// The visualiser's frame (display.cpp:35-90), drawn on the device: clear, splat, compose and the
+// one-off box-edge layer.  The image is defined exactly in DESIGN.md section 10; every operation
+// below is fp32 and rounded on its own (-ffp-contract=off), in the order that section gives.
+//
+// The splat is a scatter with heavy contention: at 800 x 600 every particle covers 9 pixels of a
+// 400 x 300 region, ~300 hits per pixel at n = 4 M and thousands on the rows the floor pile projects
+// to.  The stream it reads is cell-sorted, so the 1024 consecutive particles of a workgroup cover a
+// small screen rectangle: the workgroup accumulates them in an LDS tile over that rectangle (LDS
+// atomics) and sends ONE global atomic per touched pixel and buffer.  A workgroup whose rectangle
+// does not fit the tile (unsorted state right after an upload, very large images) issues the plain
+// per-hit global atomics instead.  Minimum and sum commute, so every path gives the same buffers.
+#include "sph_device.h"
+
+namespace {
+
+constexpr int kSplatThreads = 256;
+constexpr int kSplatPerThread = 4;
+constexpr int kSplatBlock = kSplatThreads * kSplatPerThread; // particles per workgroup
+constexpr int kTilePixels = 8192;                            // 2 x 32 KB of LDS
+
+struct Pixel {
+    int px, py;
+    uint32_t wbits;
+};
+
+// window coordinates of a point (glFrustum(-2, 2, -2, 2, 1, 100) x glTranslatef(-5, -5, -15), viewport
+// W x H): row 0 is the TOP of the window, as in the mouse coordinates of sph_apply_click
+__device__ __forceinline__ Pixel project(float x, float y, float z, const RenderParams &R) {
+    const float w = 15.f - z;
+    const float xw = (((0.5f * (x - 5.f)) / w) + 1.f) * (0.5f * R.Wf);
+    const float yw = (((0.5f * (y - 5.f)) / w) + 1.f) * (0.5f * R.Hf);
+    Pixel p;
+    // (clamped before the conversion: a float beyond the int range must not reach it; anything
+    // that far out is outside every viewport either way)
+    p.px = (int)fminf(fmaxf(floorf(xw), -65536.f), 65536.f);
+    p.py = (R.height - 1) - (int)fminf(fmaxf(floorf(yw), -65536.f), 65536.f);
+    p.wbits = __float_as_uint(w);
+    return p;
+}
+
+__global__ __launch_bounds__(256) void k_render_clear(uint32_t *__restrict__ depth, uint32_t *__restrict__ count, int npix) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < npix) {
+        depth[i] = 0xFFFFFFFFu;
+        count[i] = 0u;
+    }
+}
+
+// the check path (SPH_RENDER_PLAIN=1): one thread per particle, one atomic per hit and buffer
+__global__ __launch_bounds__(256) void k_splat_plain(const float4 *__restrict__ pos4, int n, RenderParams R,
+                                                     uint32_t *__restrict__ depth, uint32_t *__restrict__ count) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float4 p = pos4[i];
+    const Pixel q = project(p.x, p.y, p.z, R);
+    const int r = R.radius;
+    for (int y = max(q.py - r, 0); y <= min(q.py + r, R.height - 1); ++y)
+        for (int x = max(q.px - r, 0); x <= min(q.px + r, R.width - 1); ++x) {
+            atomicAdd(&count[y * R.width + x], 1u);
+            atomicMin(&depth[y * R.width + x], q.wbits);
+        }
+}
+
+__device__ __forceinline__ int wave_min(int v) {
+    for (int m = 32; m > 0; m >>= 1) v = min(v, __shfl_xor(v, m, 64));
+    return v;
+}
+__device__ __forceinline__ int wave_max(int v) {
+    for (int m = 32; m > 0; m >>= 1) v = max(v, __shfl_xor(v, m, 64));
+    return v;
+}
+
+__global__ __launch_bounds__(kSplatThreads) void k_splat_tile(const float4 *__restrict__ pos4, int n, RenderParams R,
+                                                              uint32_t *__restrict__ depth, uint32_t *__restrict__ count) {
+    __shared__ uint32_t tCount[kTilePixels];
+    __shared__ uint32_t tDepth[kTilePixels];
+    __shared__ int box[4]; // min x, min y, max x, max y over the workgroup's particle centres
+    const int t = threadIdx.x;
+    const int base = blockIdx.x * kSplatBlock;
+    const int r = R.radius;
+    if (t < 2) box[t] = 0x7fffffff;
+    else if (t < 4) box[t] = -0x7fffffff;
+
+    Pixel q[kSplatPerThread];
+    int lox = 0x7fffffff, loy = 0x7fffffff, hix = -0x7fffffff, hiy = -0x7fffffff;
+#pragma unroll
+    for (int k = 0; k < kSplatPerThread; ++k) {
+        const int i = base + k * kSplatThreads + t;
+        q[k].px = q[k].py = -0x40000000; // (no particle: covers nothing)
+        q[k].wbits = 0xFFFFFFFFu;
+        if (i < n) {
+            const float4 p = pos4[i];
+            q[k] = project(p.x, p.y, p.z, R);
+            // a centre whose square misses the viewport draws nothing and must not stretch the rectangle
+            if (q[k].px + r >= 0 && q[k].px - r < R.width && q[k].py + r >= 0 && q[k].py - r < R.height) {
+                lox = min(lox, q[k].px);
+                hix = max(hix, q[k].px);
+                loy = min(loy, q[k].py);
+                hiy = max(hiy, q[k].py);
+            } else {
+                q[k].px = q[k].py = -0x40000000;
+            }
+        }
+    }
+    lox = wave_min(lox);
+    loy = wave_min(loy);
+    hix = wave_max(hix);
+    hiy = wave_max(hiy);
+    __syncthreads();
+    if ((t & 63) == 0) {
+        atomicMin(&box[0], lox);
+        atomicMin(&box[1], loy);
+        atomicMax(&box[2], hix);
+        atomicMax(&box[3], hiy);
+    }
+    __syncthreads();
+    if (box[2] < box[0]) return; // nothing of this workgroup is on screen (uniform)
+    const int x0 = max(box[0] - r, 0), y0 = max(box[1] - r, 0);
+    const int x1 = min(box[2] + r, R.width - 1), y1 = min(box[3] + r, R.height - 1);
+    const int bw = x1 - x0 + 1, bh = y1 - y0 + 1;
+    const long long area = (long long)bw * bh;
+
+    if (area > kTilePixels) { // (uniform) the rectangle does not fit: per-hit global atomics
+#pragma unroll
+        for (int k = 0; k < kSplatPerThread; ++k) {
+            if (q[k].px == -0x40000000) continue;
+            for (int y = max(q[k].py - r, 0); y <= min(q[k].py + r, R.height - 1); ++y)
+                for (int x = max(q[k].px - r, 0); x <= min(q[k].px + r, R.width - 1); ++x) {
+                    atomicAdd(&count[y * R.width + x], 1u);
+                    atomicMin(&depth[y * R.width + x], q[k].wbits);
+                }
+        }
+        return;
+    }
+
+    const int tile = (int)area;
+    for (int e = t; e < tile; e += kSplatThreads) {
+        tCount[e] = 0u;
+        tDepth[e] = 0xFFFFFFFFu;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < kSplatPerThread; ++k) {
+        if (q[k].px == -0x40000000) continue;
+        // (every pixel of the clipped square lies inside [x0, x1] x [y0, y1] by construction)
+        for (int y = max(q[k].py - r, 0); y <= min(q[k].py + r, R.height - 1); ++y)
+            for (int x = max(q[k].px - r, 0); x <= min(q[k].px + r, R.width - 1); ++x) {
+                const int e = (y - y0) * bw + (x - x0);
+                atomicAdd(&tCount[e], 1u);
+                atomicMin(&tDepth[e], q[k].wbits);
+            }
+    }
+    __syncthreads();
+    for (int e = t; e < tile; e += kSplatThreads) {
+        const uint32_t c = tCount[e];
+        if (c == 0u) continue;
+        const int ey = e / bw;
+        const int g = (y0 + ey) * R.width + x0 + (e - ey * bw);
+        atomicAdd(&count[g], c);
+        // Depth only ever decreases during the splat, so whatever value a plain load returns (however
+        // stale) is >= the final one: if it is already <= ours, ours cannot change the result.
+        const uint32_t d = tDepth[e];
+        if (depth[g] > d) atomicMin(&depth[g], d);
+    }
+}
+
+// 12 edges x 4096 samples, each a 1-pixel point (built once per handle and image size)
+__global__ __launch_bounds__(256) void k_render_edges(RenderParams R, uint32_t *__restrict__ edge) {
+    const float V[8][3] = {{0.f, 0.f, 0.f},   {10.f, 0.f, 0.f},   {10.f, 10.f, 0.f},  {0.f, 10.f, 0.f},
+                           {0.f, 0.f, 10.f},  {10.f, 0.f, 10.f},  {10.f, 10.f, 10.f}, {0.f, 10.f, 10.f}};
+    const int E[12][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 0}, {4, 5}, {5, 6}, {6, 7}, {7, 4}, {0, 4}, {1, 5}, {2, 6}, {3, 7}};
+    const int gid = blockIdx.x * 256 + threadIdx.x;
+    if (gid >= 12 * 4096) return;
+    const int e = gid >> 12, i = gid & 4095;
+    const float s = (float)i / 4095.f;
+    const float *a = V[E[e][0]], *b = V[E[e][1]];
+    const float x = a[0] + s * (b[0] - a[0]);
+    const float y = a[1] + s * (b[1] - a[1]);
+    const float z = a[2] + s * (b[2] - a[2]);
+    const Pixel q = project(x, y, z, R);
+    if (q.px < 0 || q.px >= R.width || q.py < 0 || q.py >= R.height) return;
+    atomicMin(&edge[q.py * R.width + q.px], q.wbits);
+}
+
+__device__ __forceinline__ uint32_t pixel_rgb(uint32_t d, uint32_t c, uint32_t e, int shade) {
+    if (e != 0xFFFFFFFFu && e <= d) return 0xFFFFFFu; // GL_LESS, lines drawn first
+    if (c == 0u) return 0u;
+    if (shade == 0) return 0xFF0000u; // (r, g, b) = bytes 0, 1, 2
+    const uint32_t L = min(7u, 31u - (uint32_t)__clz((int)c));
+    return (32u * L) | ((32u * L) << 8) | 0xFF0000u;
+}
+
+// four pixels = 12 bytes = three dwords per thread; rgb is padded to a multiple of four pixels
+__global__ __launch_bounds__(256) void k_render_compose(const uint32_t *__restrict__ depth, const uint32_t *__restrict__ count,
+                                                        const uint32_t *__restrict__ edge, int npix, int shade,
+                                                        uint32_t *__restrict__ rgb) {
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    const int p0 = g * 4;
+    if (p0 >= npix) return;
+    uint32_t c[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) c[k] = (p0 + k < npix) ? pixel_rgb(depth[p0 + k], count[p0 + k], edge[p0 + k], shade) : 0u;
+    rgb[g * 3 + 0] = c[0] | (c[1] << 24);
+    rgb[g * 3 + 1] = (c[1] >> 8) | (c[2] << 16);
+    rgb[g * 3 + 2] = (c[2] >> 16) | (c[3] << 8);
+}
+
+} // namespace
+
+void sph_launch_render_edges(const RenderParams &R, uint32_t *edge, hipStream_t s) {
+    const int npix = R.width * R.height;
+    (void)hipMemsetAsync(edge, 0xFF, (size_t)npix * sizeof(uint32_t), s);
+    k_render_edges<<<(12 * 4096) / 256, 256, 0, s>>>(R, edge);
+}
+
+void sph_launch_render(const RenderParams &R, const float4 *pos4, int n, bool plain, uint32_t *depth, uint32_t *count,
+                       const uint32_t *edge, uint32_t *rgb, hipStream_t s) {
+    const int npix = R.width * R.height;
+    k_render_clear<<<(npix + 255) / 256, 256, 0, s>>>(depth, count, npix);
+    if (n > 0) {
+        if (plain) k_splat_plain<<<(n + 255) / 256, 256, 0, s>>>(pos4, n, R, depth, count);
+        else k_splat_tile<<<(n + kSplatBlock - 1) / kSplatBlock, kSplatThreads, 0, s>>>(pos4, n, R, depth, count);
+    }
+    const int quads = (npix + 3) / 4;
+    k_render_compose<<<(quads + 255) / 256, 256, 0, s>>>(depth, count, edge, npix, R.shade, rgb);
+}

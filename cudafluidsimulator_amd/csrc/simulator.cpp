@@ -122,6 +122,18 @@ void Simulator::simulateAndTime(Times *times) {
     check(impl, sph_step(impl, reinterpret_cast<SphTimes *>(times)), "sph_step");
 }
 
+const unsigned char *Simulator::renderFrame(int *width, int *height) {
+    if (multi) {
+        fprintf(stderr, "sph: renderFrame: frames of a multi-GPU run (SPH_GPUS > 1) are not rendered\n");
+        return NULL;
+    }
+    if (!impl) return NULL;
+    check(impl, sph_render_frame(impl, NULL), "sph_render_frame");
+    const unsigned char *f = sph_frame_host(impl, width, height);
+    if (!f) check(impl, SPH_EHIP, "sph_frame_host");
+    return f;
+}
+
 void Simulator::moveParticles(int2 mouse_pos) {
     if (multi) { // multi-GPU: the impulse needs the slabs' grids of a step: it rides on the next simulate()
         mcheck(multi, sph_mgpu_queue_click(multi, mouse_pos.x, mouse_pos.y), "sph_mgpu_queue_click");

@@ -154,6 +154,16 @@ struct sph_handle {
     int tileChunkEnv = -1;  // SPH_TILE_CHUNK: -1 auto, 0 contiguous eighths, >0 tiles per chunk
     int tileRotate = -1;    // SPH_XCD_ROTATE: xcd_tile()'s rotation period in groups (z-layers), 0 = off;
                             // -1 (default): off for the single domain, every layer for a slab (see slab_rotate)
+    // The visualiser's frame (render.hip), allocated by the first sph_render_frame: per-pixel depth bits,
+    // hit count and the static box-edge layer on the device, the RGB8 frame on the device and in pinned memory.
+    RenderParams rp{};               // size / point radius / shade of the last render (width 0: none yet)
+    uint32_t *rDepth = nullptr, *rCount = nullptr, *rEdge = nullptr, *rRgb = nullptr;
+    uint8_t *frameHost = nullptr;
+    hipEvent_t frameDrawn = nullptr, frameCopied = nullptr;
+    bool framePending = false;       // a frame copy is queued on the copy stream
+    bool frameValid = false;         // the buffers hold a rendered frame of the size in rp
+    double renderSeconds = 0;        // clear + splat + compose, from HIP events (PairEvent ring)
+    long long renderFrames = 0;
     bool ready = false;     // state uploaded
     bool gridValid = false; // sorted streams + cell table match `sorted`
     int phase = 0;          // 0 idle, 1 grid done, 2 density done, 3 force done
@@ -1304,6 +1314,10 @@ void sph_destroy(sph_handle *h) {
     if (h->calm) (void)hipFree(h->calm);
     if (h->initPos4) (void)hipFree(h->initPos4);
     if (h->oobHost) (void)hipHostFree(h->oobHost);
+    for (uint32_t *b : {h->rDepth, h->rCount, h->rEdge, h->rRgb}) if (b) (void)hipFree(b);
+    if (h->frameHost) (void)hipHostFree(h->frameHost);
+    if (h->frameDrawn) (void)hipEventDestroy(h->frameDrawn);
+    if (h->frameCopied) (void)hipEventDestroy(h->frameCopied);
     if (h->boundsDev) (void)hipFree(h->boundsDev);
     if (h->partTiles) (void)hipFree(h->partTiles);
     if (h->boundsHost) (void)hipHostFree(h->boundsHost);
@@ -1979,6 +1993,139 @@ int sph_debug_counters(sph_handle *h, uint64_t *out16) {
         for (int k = 0; k < 16; ++k) out16[k] += h->pairHost[16 + sh * 16 + k];
     return SPH_OK;
 }
+
+// ---- the visualiser's frame ----
+namespace {
+
+// (re)allocate the frame buffers for a width x height image and draw the static edge layer
+int render_resize(sph_handle *h, int width, int height) {
+    if (h->rp.width == width && h->rp.height == height && h->rDepth) return SPH_OK;
+    // the old buffers may still be read by a queued compose / frame copy
+    HIPCHK(h, hipStreamSynchronize(h->compute));
+    HIPCHK(h, hipStreamSynchronize(h->copy));
+    h->framePending = false;
+    h->frameValid = false;
+    for (uint32_t **b : {&h->rDepth, &h->rCount, &h->rEdge, &h->rRgb}) {
+        if (*b) (void)hipFree(*b);
+        *b = nullptr;
+    }
+    if (h->frameHost) (void)hipHostFree(h->frameHost);
+    h->frameHost = nullptr;
+    h->rp.width = h->rp.height = 0;
+    const size_t npix = (size_t)width * (size_t)height;
+    const size_t rgbBytes = (npix + 3) / 4 * 12; // whole groups of four pixels (k_render_compose)
+    HIPCHK(h, hipMalloc(&h->rDepth, npix * sizeof(uint32_t)));
+    HIPCHK(h, hipMalloc(&h->rCount, npix * sizeof(uint32_t)));
+    HIPCHK(h, hipMalloc(&h->rEdge, npix * sizeof(uint32_t)));
+    HIPCHK(h, hipMalloc(&h->rRgb, rgbBytes));
+    HIPCHK(h, hipHostMalloc(&h->frameHost, rgbBytes, hipHostMallocDefault));
+    memset(h->frameHost, 0, rgbBytes);
+    if (!h->frameDrawn) HIPCHK(h, hipEventCreateWithFlags(&h->frameDrawn, hipEventDisableTiming));
+    if (!h->frameCopied) HIPCHK(h, hipEventCreateWithFlags(&h->frameCopied, hipEventDisableTiming));
+    RenderParams R = h->rp;
+    R.width = width;
+    R.height = height;
+    R.Wf = (float)width;
+    R.Hf = (float)height;
+    sph_launch_render_edges(R, h->rEdge, h->compute);
+    HIPCHK(h, hipGetLastError());
+    h->rp = R;
+    return SPH_OK;
+}
+
+} // namespace
+
+int sph_render_frame(sph_handle *h, const SphRenderOptions *opt) {
+    if (!h) return SPH_EINVAL;
+    SPH_ON_DEVICE(h);
+    if (h->external) return fail(h, SPH_ESTATE, "handle is in slab mode (external state): multi-GPU frames are not rendered");
+    if (!h->ready) return fail(h, SPH_ESTATE, "setup()/upload_state() must come first");
+    SphRenderOptions o{};
+    if (opt) {
+        if (opt->struct_size <= 0) return fail(h, SPH_EINVAL, "SphRenderOptions.struct_size is not set");
+        const size_t sz = (size_t)opt->struct_size;
+        memcpy(&o, opt, sz < sizeof o ? sz : sizeof o);
+    }
+    const int width = o.width == 0 ? 800 : o.width, height = o.height == 0 ? 600 : o.height;
+    const int pointSize = o.point_size == 0 ? 3 : o.point_size;
+    if (width < 1 || width > 4096 || height < 1 || height > 4096) return fail(h, SPH_EINVAL, "frame size must be 1..4096 x 1..4096");
+    if (pointSize < 1 || pointSize > 9 || (pointSize & 1) == 0) return fail(h, SPH_EINVAL, "point_size must be odd, 1..9");
+    if (o.shade != SPH_SHADE_FLAT && o.shade != SPH_SHADE_COUNT) return fail(h, SPH_EINVAL, "unknown shade");
+    int rc = render_resize(h, width, height);
+    if (rc) return rc;
+    h->rp.radius = (pointSize - 1) / 2;
+    h->rp.shade = o.shade;
+    bool plain = false;
+    if (const char *e = getenv("SPH_RENDER_PLAIN")) plain = atoi(e) != 0;
+    hipStream_t s = h->compute;
+    if (h->framePending) { // the previous frame's copy still reads the device frame the compose is about to rewrite
+        HIPCHK(h, hipStreamWaitEvent(s, h->frameCopied, 0));
+        h->framePending = false;
+    }
+    PairEvent *pe = nullptr;
+    if ((rc = pair_begin(h, &h->renderSeconds, &pe))) return rc;
+    // The current state: after a step the rows the force sweep wrote, still in that step's cell-sorted order;
+    // after setup / upload / load (and always with SPH_SWEEP_LINKED) in particle-id order.  A grid built
+    // ahead for the next step only reads these rows.
+    sph_launch_render(h->rp, h->pos4[h->cur], h->n, plain, h->rDepth, h->rCount, h->rEdge, h->rRgb, s);
+    HIPCHK(h, hipEventRecord(pe->b, s));
+    HIPCHK(h, hipGetLastError());
+    h->renderFrames += 1;
+    h->frameValid = true;
+    // the frame leaves on the copy stream, behind an event, like the positions do
+    HIPCHK(h, hipEventRecord(h->frameDrawn, s));
+    HIPCHK(h, hipStreamWaitEvent(h->copy, h->frameDrawn, 0));
+    HIPCHK(h, hipMemcpyAsync(h->frameHost, h->rRgb, (size_t)width * height * 3, hipMemcpyDeviceToHost, h->copy));
+    HIPCHK(h, hipEventRecord(h->frameCopied, h->copy));
+    h->framePending = true;
+    return SPH_OK;
+}
+
+const uint8_t *sph_frame_host(sph_handle *h, int *width, int *height) {
+    if (!h) return nullptr;
+    if (!h->frameValid) {
+        h->err = "sph_render_frame must come first";
+        return nullptr;
+    }
+    if (h->framePending && hipEventSynchronize(h->frameCopied) != hipSuccess) {
+        h->err = "frame copy failed";
+        return nullptr;
+    }
+    if (width) *width = h->rp.width;
+    if (height) *height = h->rp.height;
+    return h->frameHost;
+}
+
+int sph_download_frame_buffers(sph_handle *h, uint32_t *depth_bits, uint32_t *count, uint32_t *edge_depth_bits) {
+    if (!h) return SPH_EINVAL;
+    SPH_ON_DEVICE(h);
+    if (!h->frameValid) return fail(h, SPH_ESTATE, "sph_render_frame must come first");
+    HIPCHK(h, hipStreamSynchronize(h->compute));
+    const size_t bytes = (size_t)h->rp.width * h->rp.height * sizeof(uint32_t);
+    if (depth_bits) HIPCHK(h, hipMemcpy(depth_bits, h->rDepth, bytes, hipMemcpyDeviceToHost));
+    if (count) HIPCHK(h, hipMemcpy(count, h->rCount, bytes, hipMemcpyDeviceToHost));
+    if (edge_depth_bits) HIPCHK(h, hipMemcpy(edge_depth_bits, h->rEdge, bytes, hipMemcpyDeviceToHost));
+    return SPH_OK;
+}
+
+int sph_get_render_time(sph_handle *h, double *seconds, int64_t *frames, int reset) {
+    if (!h) return SPH_EINVAL;
+    SPH_ON_DEVICE(h);
+    for (auto &pe : h->pairs)
+        if (pe.used && pe.target == &h->renderSeconds) {
+            int rc = resolve_pair(h, pe);
+            if (rc) return rc;
+        }
+    if (seconds) *seconds = h->renderSeconds;
+    if (frames) *frames = h->renderFrames;
+    if (reset) {
+        h->renderSeconds = 0;
+        h->renderFrames = 0;
+    }
+    return SPH_OK;
+}
+
+int sph_api_version(void) { return SPH_API_VERSION; }
 
 const char *sph_last_error(const sph_handle *h) {
     return h ? h->err.c_str() : g_create_error.c_str();

@@ -205,3 +205,17 @@ void sph_launch_density(const DevParams &P, const SweepArgs &A, int mathMode,
                         int sweep, hipStream_t s);
 void sph_launch_force(const DevParams &P, const SweepArgs &A, int mathMode,
                       int sweep, hipStream_t s);
+
+// ---- the visualiser's frame (render.hip; the image is defined in DESIGN.md section 10) ----
+struct RenderParams {
+    int width, height;
+    float Wf, Hf; // width and height as floats
+    int radius;   // (point_size - 1) / 2
+    int shade;    // SPH_SHADE_*
+};
+// the static layer: 12 box edges x 4096 samples, minimum depth bits per pixel (clears `edge` first)
+void sph_launch_render_edges(const RenderParams &R, uint32_t *edge, hipStream_t s);
+// clear + splat of pos4[0, n) + compose into rgb (3 bytes per pixel, padded to a multiple of 4 pixels);
+// plain = the one-atomic-per-hit check path
+void sph_launch_render(const RenderParams &R, const float4 *pos4, int n, bool plain, uint32_t *depth, uint32_t *count,
+                       const uint32_t *edge, uint32_t *rgb, hipStream_t s);

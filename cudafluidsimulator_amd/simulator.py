@@ -157,6 +157,49 @@ class Simulator:
     def load_state(self, path):
         self._check(self._L.sph_load_state(self._h, str(path).encode()), "sph_load_state")
 
+    # -- the visualiser's frame (display.cpp:35-90), drawn on the device --
+    def render_frame(self, width=0, height=0, point_size=0, shade="flat"):
+        """Queue one frame of the current state (sph_render_frame); does not block."""
+        o = _lib.SphRenderOptions()
+        o.struct_size = C.sizeof(_lib.SphRenderOptions)
+        o.width, o.height, o.point_size = int(width), int(height), int(point_size)
+        o.shade = _lib.SHADES[shade] if isinstance(shade, str) else int(shade)
+        self._check(self._L.sph_render_frame(self._h, C.byref(o)), "sph_render_frame")
+
+    def frame_host(self):
+        """(H, W, 3) uint8 view of the last rendered frame, row 0 = top of the window; blocks until
+        it has landed, valid until the next render."""
+        w, h = C.c_int(0), C.c_int(0)
+        p = self._L.sph_frame_host(self._h, C.byref(w), C.byref(h))
+        if not p:
+            raise SphError("sph_frame_host failed: " + self._L.sph_last_error(self._h).decode())
+        return np.ctypeslib.as_array(p, shape=(h.value, w.value, 3))
+
+    def render(self, width=0, height=0, point_size=0, shade="flat"):
+        """The frame display.cpp would draw (defaults: 800 x 600, points of size 3, flat blue) as an
+        (H, W, 3) uint8 array of its own."""
+        self.render_frame(width, height, point_size, shade)
+        return np.array(self.frame_host(), copy=True)
+
+    def frame_buffers(self):
+        """depth bits, covering-particle count and box-edge depth bits of the last frame: three
+        (H, W) uint32 arrays."""
+        w, h = C.c_int(0), C.c_int(0)
+        if not self._L.sph_frame_host(self._h, C.byref(w), C.byref(h)):
+            raise SphError("sph_frame_host failed: " + self._L.sph_last_error(self._h).decode())
+        out = [np.zeros((h.value, w.value), np.uint32) for _ in range(3)]
+        u32p = C.POINTER(C.c_uint32)
+        self._check(self._L.sph_download_frame_buffers(self._h, *[a.ctypes.data_as(u32p) for a in out]),
+                    "sph_download_frame_buffers")
+        return dict(depth=out[0], count=out[1], edge=out[2])
+
+    def render_time(self, reset=False):
+        """(seconds, frames): GPU time of clear + splat + compose summed over `frames` renders."""
+        sec, fr = C.c_double(0), C.c_int64(0)
+        self._check(self._L.sph_get_render_time(self._h, C.byref(sec), C.byref(fr), 1 if reset else 0),
+                    "sph_get_render_time")
+        return sec.value, fr.value
+
     def phase(self, name):
         self._check(getattr(self._L, "sph_phase_" + name)(self._h), "sph_phase_" + name)
 

@@ -83,6 +83,11 @@ class Simulator {
     void simulate();
     void simulateAndTime(Times *times);
     void moveParticles(int2 mouse_pos);
+
+    // Not in the reference: the frame display.cpp would draw of the current state -- 800 x 600, RGB8,
+    // row 0 = top of the window -- rendered on the GPU (sph_render_frame in sph_c_api.h).  Owned by the
+    // simulator, valid until the next call.  NULL (with a message on stderr) with SPH_GPUS > 1.
+    const unsigned char *renderFrame(int *width, int *height);
 };
 
 #endif

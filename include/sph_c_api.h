@@ -23,7 +23,9 @@
 extern "C" {
 #endif
 
-#define SPH_API_VERSION 2 /* 2: + sph_slab_apply_click, sph_slab_records (additive; every v1 entry point unchanged) */
+#define SPH_API_VERSION 3 /* 2: + sph_slab_apply_click, sph_slab_records; 3: + sph_render_frame, sph_frame_host,
+                             sph_download_frame_buffers, sph_get_render_time, sph_api_version (additive; every
+                             earlier entry point unchanged) */
 
 #define SPH_OK 0
 #define SPH_EINVAL (-1)  /* bad argument / state outside the box       */
@@ -266,6 +268,48 @@ int sph_slab_apply_click(sph_handle *h, int buf, int mouse_x, int mouse_y, int z
  * launch; hip_stream NULL = the handle's stream. */
 int sph_slab_force_ranges(sph_handle *h, int buf, int i_origin, int a0, int b0, int a1, int b1,
                           int n_all, int last_launch_of_the_step, void *hip_stream);
+
+/* ---- the visualiser's frame (display.cpp:35-90), drawn on the device ----
+ * The scene is display.cpp's: glFrustum(-2, 2, -2, 2, 1, 100) x glTranslatef(-5, -5, -15), identity
+ * model-view, the 12 edges of the box [0, 10]^3 in white, the particles as square points.  GL leaves
+ * rasterisation to the implementation; this one is fixed to the bit: all fp32,
+ * w = 15 - z, xw = ((0.5 (x - 5)) / w + 1) (0.5 W), column floor(xw), row (H - 1) - floor(yw) -- row 0
+ * is the TOP of the window, so sph_apply_click(h, x, y) addresses pixel (x, y) of this image.  Per pixel
+ * the library keeps the minimum depth (the bits of w) and the number of covering particles; the frame
+ * is RGB8, row 0 first: white where a box edge is not behind the nearest particle, else the particle
+ * colour, else black. */
+enum {
+    SPH_SHADE_FLAT = 0, /* the reference's: every particle pixel (0, 0, 255) */
+    SPH_SHADE_COUNT = 1 /* (32 L, 32 L, 255), L = min(7, floor(log2(covering particles))) */
+};
+typedef struct SphRenderOptions {
+    int32_t struct_size;   /* = sizeof(SphRenderOptions) */
+    int32_t width, height; /* 0 = 800 x 600; at most 4096 x 4096 */
+    int32_t point_size;    /* 0 = 3; odd, 1..9 */
+    int32_t shade;         /* SPH_SHADE_* */
+} SphRenderOptions;
+/* Draws the state the handle holds NOW (after sph_step the positions sph_positions_host would return;
+ * sph_apply_click changes velocities only; after sph_setup / sph_upload_state / sph_load_state the
+ * uploaded state) and queues the copy of the frame to pinned host memory.  opt == NULL: display.cpp's
+ * 800 x 600, points of size 3, flat blue.  Reads the device-resident particle stream, never the
+ * id-ordered read-back: works with SPH_FLAG_NO_READBACK.  Queued on the handle's streams; does not
+ * block.  Before any state, and for SPH_FLAG_EXTERNAL_STATE handles (slabs): SPH_ESTATE.  Bad sizes,
+ * an even point_size, an unknown shade: SPH_EINVAL.  With SPH_SWEEP_LINKED the frame is drawn from the
+ * particle-id-ordered state array that backend keeps (same image, no cell-sorted stream to exploit).
+ * SPH_RENDER_PLAIN=1 in the environment selects the check path of the splat (one global atomic per
+ * covered pixel and particle; identical buffers). */
+int sph_render_frame(sph_handle *h, const SphRenderOptions *opt);
+/* width x height x 3 bytes of the last sph_render_frame, owned by the handle, valid until the next
+ * render.  Blocks until the copy has landed.  NULL before the first render. */
+const uint8_t *sph_frame_host(sph_handle *h, int *width, int *height);
+/* The buffers behind the last frame, width x height each, row 0 first; any pointer may be NULL.
+ * depth_bits: minimum over covering particles of the bit pattern of w (0xFFFFFFFF = empty); count:
+ * covering particles; edge_depth_bits: the static box-edge layer (0xFFFFFFFF = no edge). */
+int sph_download_frame_buffers(sph_handle *h, uint32_t *depth_bits, uint32_t *count, uint32_t *edge_depth_bits);
+/* GPU time of clear + splat + compose (HIP events on the compute stream), summed over `frames` renders. */
+int sph_get_render_time(sph_handle *h, double *seconds, int64_t *frames, int reset);
+/* SPH_API_VERSION of the library that is actually loaded. */
+int sph_api_version(void);
 
 const char *sph_build_info(void);
 
