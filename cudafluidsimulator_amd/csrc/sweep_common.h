@@ -199,7 +199,8 @@ __device__ __forceinline__ void force_pair(const DevParams &P, float pix, float 
 // ---- SPH_MATH_FAST variants: same formulas, FMA-contracted, with the hardware's
 // approximate reciprocal / reciprocal square root (~1 ulp) instead of the
 // correctly rounded divide and sqrt.  Not bit-identical to the oracle; checked
-// against it at the north star's 1e-5 relative tolerance (tests).
+// against it at the north star's 1e-5 relative tolerance, and kernel by kernel against
+// a float64 evaluation at four times the oracle's own error (tests/test_gpu_fast_math.py).
 __device__ __forceinline__ float fast_dist2(float pix, float piy, float piz, float4 pj,
                                             float &dx, float &dy, float &dz) {
     dx = pix - pj.x;
@@ -218,8 +219,14 @@ __device__ __forceinline__ void force_pair_fast(const DevParams &P, float pix, f
     const float inv_rho = __builtin_amdgcn_rcpf(rho_j);
     const float prs_j = fmaxf(0.f, rho_j - SPH_REST_DENSITY);
     const float inv_dist = __builtin_amdgcn_rsqf(dist2);
-    const float dist = dist2 * inv_dist;
-    const bool ok = !(dist2 > P.h2) && !(dist < SPH_EPS_F) && dist2 > 0.f;
+    // dist2 * rsq(dist2) is off by up to 1.5 ulp, three times the strict sqrtf, and the terms below are made of
+    // h - dist: for a neighbour near the rim of the support (dist = 0.98 h: h - dist amplifies an error in dist
+    // 58 times, its square twice that) a row's whole force was six times further from the float64 value than the
+    // strict body's (tests/test_gpu_fast_math.py, the sparse rows of "cloud").  One Newton step -- the residual
+    // dist2 - d0*d0 is exact in an fma -- brings dist back to half an ulp for two fmas and a multiply.
+    const float d0 = dist2 * inv_dist;
+    const float dist = __builtin_fmaf(__builtin_fmaf(-d0, d0, dist2), 0.5f * inv_dist, d0);
+    const bool ok =!(dist2 > P.h2) && !(dist < SPH_EPS_F) && dist2 > 0.f;
     if (ok) {
         const float hd = P.h - dist;
         // fPressure * scale = (-MASS (p_i+p_j) / (2 rho_j)) * (-vcoef (h-r)^2 / r)
