@@ -24,10 +24,14 @@ EXPORTED_SYMBOLS = [
     "sph_debug_counters", "sph_get_stream", "sph_slab_partition_async", "sph_slab_sort_async",
     "sph_slab_patch_halo", "sph_slab_force_ranges", "sph_num_table_cells", "sph_slab_apply_click", "sph_slab_records",
     "sph_render_frame", "sph_frame_host", "sph_download_frame_buffers", "sph_get_render_time", "sph_api_version",
+    "sph_render_field", "sph_download_field_buffer", "sph_field_range",
 ]
 SPH_API_VERSION = 3
 SPH_SHADE_FLAT, SPH_SHADE_COUNT = 0, 1
 SHADES = {"flat": SPH_SHADE_FLAT, "count": SPH_SHADE_COUNT}
+SPH_HAS_FIELD_FRAME = 1
+SPH_FIELD_SPEED, SPH_FIELD_DENSITY, SPH_FIELD_PRESSURE = 0, 1, 2
+FIELDS = {"speed": SPH_FIELD_SPEED, "density": SPH_FIELD_DENSITY, "pressure": SPH_FIELD_PRESSURE}
 
 
 class SphError(RuntimeError):
@@ -56,6 +60,12 @@ class SphOptions(C.Structure):
 class SphRenderOptions(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
                 ("point_size", C.c_int32), ("shade", C.c_int32)]
+
+
+class SphFieldFrameOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("point_size", C.c_int32), ("field", C.c_int32),
+                ("value_lo", C.c_float), ("value_hi", C.c_float)]
 
 
 class SphKernelTimes(C.Structure):
@@ -129,5 +139,8 @@ def load_library():
     L.sph_download_frame_buffers.argtypes = [hp, u32p, u32p, u32p]
     L.sph_get_render_time.argtypes = [hp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]
     L.sph_api_version.argtypes = []
+    L.sph_render_field.argtypes = [hp, C.POINTER(SphFieldFrameOptions)]
+    L.sph_download_field_buffer.argtypes = [hp, u32p]
+    L.sph_field_range.argtypes = [hp, fp, fp]
     _lib = L
     return L

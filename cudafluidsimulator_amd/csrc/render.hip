@@ -9,6 +9,7 @@
 // atomics) and sends ONE global atomic per touched pixel and buffer.  A workgroup whose rectangle
 // does not fit the tile (unsorted state right after an upload, very large images) issues the plain
 // per-hit global atomics instead.  Minimum and sum commute, so every path gives the same buffers.
+#include "sph_c_api.h"
 #include "sph_device.h"
 
 namespace {
@@ -205,6 +206,231 @@ __global__ __launch_bounds__(256) void k_render_compose(const uint32_t *__restri
     rgb[g * 3 + 2] = (c[2] >> 16) | (c[3] << 8);
 }
 
+// ---- the field frame ("The field frame"): the same splat carrying a value ----
+// Per pixel the minimum of (bits(w) << 32) | bits(s) over the covering particles, s >= +0 the scalar of
+// the particle's vel4 row (xyz = velocity, w = density): the high word IS the depth buffer of the flat
+// frame, the low word the value of the nearest particle (the smallest among several at that depth).
+
+constexpr int kFieldTilePixels = 8192;                         // 12 B per pixel: minima, then counts; 96 KB of dynamic LDS
+constexpr int kFieldPerThread = 4;
+constexpr int kFieldBlock = kSplatThreads * kFieldPerThread;   // particles per workgroup
+constexpr size_t kFieldTileBytes = (size_t)kFieldTilePixels * 12;
+constexpr unsigned long long kFieldEmpty = 0xFFFFFFFFFFFFFFFFull;
+
+__device__ __forceinline__ uint32_t field_bits(const float4 v, int field) {
+    float s;
+    if (field == SPH_FIELD_SPEED) s = sqrtf((v.x * v.x + v.y * v.y) + v.z * v.z);
+    else if (field == SPH_FIELD_DENSITY) s = v.w;
+    else s = fmaxf(0.f, SPH_GAS_CONSTANT * (v.w - SPH_REST_DENSITY)); // as sph_download_state
+    return __float_as_uint(s);
+}
+
+__device__ __forceinline__ unsigned long long field_word(uint32_t wbits, uint32_t sbits) {
+    return ((unsigned long long)wbits << 32) | sbits;
+}
+
+// range[0] / range[1]: the bits of lo / hi compose will read -- the fixed range, or the identities of the reduction
+__global__ __launch_bounds__(256) void k_field_clear(unsigned long long *__restrict__ packed, uint32_t *__restrict__ count,
+                                                     int npix, uint32_t *__restrict__ range, uint32_t lo, uint32_t hi) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < npix) {
+        packed[i] = kFieldEmpty;
+        count[i] = 0u;
+    }
+    if (i == 0) {
+        range[0] = lo;
+        range[1] = hi;
+    }
+}
+
+// automatic range: minimum and maximum of the bit patterns of s over ALL n rows (s >= +0: bit order = value order);
+// wave64 shuffles, one LDS step across the four waves, then at most one atomic per workgroup and word
+__global__ __launch_bounds__(256) void k_field_range(const float4 *__restrict__ vel4, int n, int field,
+                                                     uint32_t *__restrict__ range) {
+    __shared__ uint32_t wlo[4], whi[4];
+    uint32_t lo = 0xFFFFFFFFu, hi = 0u;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+        const uint32_t b = field_bits(vel4[i], field);
+        lo = min(lo, b);
+        hi = max(hi, b);
+    }
+    for (int m = 32; m > 0; m >>= 1) {
+        lo = min(lo, (uint32_t)__shfl_xor((int)lo, m, 64));
+        hi = max(hi, (uint32_t)__shfl_xor((int)hi, m, 64));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        wlo[threadIdx.x >> 6] = lo;
+        whi[threadIdx.x >> 6] = hi;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        lo = min(min(wlo[0], wlo[1]), min(wlo[2], wlo[3]));
+        hi = max(max(whi[0], whi[1]), max(whi[2], whi[3]));
+        // (lo only falls and hi only rises: a stale load that already is past ours settles it)
+        if (range[0] > lo) atomicMin(&range[0], lo);
+        if (range[1] < hi) atomicMax(&range[1], hi);
+    }
+}
+
+// the check path (SPH_RENDER_PLAIN=1)
+__global__ __launch_bounds__(256) void k_field_splat_plain(const float4 *__restrict__ pos4, const float4 *__restrict__ vel4,
+                                                           int n, RenderParams R, int field,
+                                                           unsigned long long *__restrict__ packed, uint32_t *__restrict__ count) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float4 p = pos4[i];
+    const Pixel q = project(p.x, p.y, p.z, R);
+    const unsigned long long m = field_word(q.wbits, field_bits(vel4[i], field));
+    const int r = R.radius;
+    for (int y = max(q.py - r, 0); y <= min(q.py + r, R.height - 1); ++y)
+        for (int x = max(q.px - r, 0); x <= min(q.px + r, R.width - 1); ++x) {
+            atomicAdd(&count[y * R.width + x], 1u);
+            atomicMin(&packed[y * R.width + x], m);
+        }
+}
+
+// k_splat_tile with the packed minimum in the tile: same rectangle, same fallback
+__global__ __launch_bounds__(kSplatThreads) void k_field_splat_tile(const float4 *__restrict__ pos4, const float4 *__restrict__ vel4,
+                                                                    int n, RenderParams R, int field,
+                                                                    unsigned long long *__restrict__ packed,
+                                                                    uint32_t *__restrict__ count) {
+    extern __shared__ unsigned long long tMin[];                    // kFieldTilePixels minima ...
+    uint32_t *tCount = reinterpret_cast<uint32_t *>(tMin + kFieldTilePixels); // ... then as many counts
+    __shared__ int box[4];
+    const int t = threadIdx.x;
+    const int base = blockIdx.x * kFieldBlock;
+    const int r = R.radius;
+    if (t < 2) box[t] = 0x7fffffff;
+    else if (t < 4) box[t] = -0x7fffffff;
+
+    int qx[kFieldPerThread], qy[kFieldPerThread];
+    unsigned long long qm[kFieldPerThread];
+    int lox = 0x7fffffff, loy = 0x7fffffff, hix = -0x7fffffff, hiy = -0x7fffffff;
+#pragma unroll
+    for (int k = 0; k < kFieldPerThread; ++k) {
+        const int i = base + k * kSplatThreads + t;
+        qx[k] = qy[k] = -0x40000000; // (no particle, or one whose square misses the viewport: covers nothing)
+        qm[k] = kFieldEmpty;
+        if (i < n) {
+            const float4 p = pos4[i];
+            const Pixel q = project(p.x, p.y, p.z, R);
+            if (q.px + r >= 0 && q.px - r < R.width && q.py + r >= 0 && q.py - r < R.height) {
+                qx[k] = q.px;
+                qy[k] = q.py;
+                qm[k] = field_word(q.wbits, field_bits(vel4[i], field));
+                lox = min(lox, q.px);
+                hix = max(hix, q.px);
+                loy = min(loy, q.py);
+                hiy = max(hiy, q.py);
+            }
+        }
+    }
+    lox = wave_min(lox);
+    loy = wave_min(loy);
+    hix = wave_max(hix);
+    hiy = wave_max(hiy);
+    __syncthreads();
+    if ((t & 63) == 0) {
+        atomicMin(&box[0], lox);
+        atomicMin(&box[1], loy);
+        atomicMax(&box[2], hix);
+        atomicMax(&box[3], hiy);
+    }
+    __syncthreads();
+    if (box[2] < box[0]) return; // nothing of this workgroup is on screen (uniform)
+    const int x0 = max(box[0] - r, 0), y0 = max(box[1] - r, 0);
+    const int x1 = min(box[2] + r, R.width - 1), y1 = min(box[3] + r, R.height - 1);
+    const int bw = x1 - x0 + 1, bh = y1 - y0 + 1;
+    const long long area = (long long)bw * bh;
+
+    if (area > kFieldTilePixels) { // (uniform) the rectangle does not fit: per-hit global atomics
+#pragma unroll
+        for (int k = 0; k < kFieldPerThread; ++k) {
+            if (qx[k] == -0x40000000) continue;
+            for (int y = max(qy[k] - r, 0); y <= min(qy[k] + r, R.height - 1); ++y)
+                for (int x = max(qx[k] - r, 0); x <= min(qx[k] + r, R.width - 1); ++x) {
+                    atomicAdd(&count[y * R.width + x], 1u);
+                    atomicMin(&packed[y * R.width + x], qm[k]);
+                }
+        }
+        return;
+    }
+
+    const int tile = (int)area;
+    for (int e = t; e < tile; e += kSplatThreads) {
+        tCount[e] = 0u;
+        tMin[e] = kFieldEmpty;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < kFieldPerThread; ++k) {
+        if (qx[k] == -0x40000000) continue;
+        // (every pixel of the clipped square lies inside [x0, x1] x [y0, y1] by construction)
+        for (int y = max(qy[k] - r, 0); y <= min(qy[k] + r, R.height - 1); ++y)
+            for (int x = max(qx[k] - r, 0); x <= min(qx[k] + r, R.width - 1); ++x) {
+                const int e = (y - y0) * bw + (x - x0);
+                atomicAdd(&tCount[e], 1u);
+                atomicMin(&tMin[e], qm[k]);
+            }
+    }
+    __syncthreads();
+    for (int e = t; e < tile; e += kSplatThreads) {
+        const uint32_t c = tCount[e];
+        if (c == 0u) continue;
+        const int ey = e / bw;
+        const int g = (y0 + ey) * R.width + x0 + (e - ey * bw);
+        atomicAdd(&count[g], c);
+        // The packed word only ever decreases during the splat, so a plain (aligned, single 8-byte) load,
+        // however stale, is >= the final one: if it is already <= ours, ours cannot change the result.
+        const unsigned long long m = tMin[e];
+        if (packed[g] > m) atomicMin(&packed[g], m);
+    }
+}
+
+// (r, g, b) = bytes 0, 1, 2: blue - cyan - green - yellow - red over q = 0..255, integers only
+__device__ __forceinline__ uint32_t field_ramp(uint32_t q) {
+    if (q < 64u) return ((4u * q) << 8) | 0xFF0000u;
+    if (q < 128u) return 0x00FF00u | ((255u - 4u * (q - 64u)) << 16);
+    if (q < 192u) return (4u * (q - 128u)) | 0x00FF00u;
+    return 0xFFu | ((255u - 4u * (q - 192u)) << 8);
+}
+
+__device__ __forceinline__ uint32_t field_rgb(unsigned long long m, uint32_t c, uint32_t e, float lo, float hi) {
+    const uint32_t d = (uint32_t)(m >> 32);
+    if (e != 0xFFFFFFFFu && e <= d) return 0xFFFFFFu; // GL_LESS, lines drawn first
+    if (c == 0u) return 0u;
+    uint32_t q = 0u;
+    if (hi != lo) {
+        const float u = ((__uint_as_float((uint32_t)m) - lo) / (hi - lo)) * 256.f;
+        if (u == u) q = (uint32_t)(int)fminf(fmaxf(floorf(u), 0.f), 255.f); // (NaN: q = 0)
+    }
+    return field_ramp(q);
+}
+
+// as k_render_compose; also leaves the high words in `depth`, the depth buffer sph_download_frame_buffers serves
+__global__ __launch_bounds__(256) void k_field_compose(const unsigned long long *__restrict__ packed,
+                                                       const uint32_t *__restrict__ count, const uint32_t *__restrict__ edge,
+                                                       const uint32_t *__restrict__ range, int npix,
+                                                       uint32_t *__restrict__ depth, uint32_t *__restrict__ rgb) {
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    const int p0 = g * 4;
+    if (p0 >= npix) return;
+    const float lo = __uint_as_float(range[0]), hi = __uint_as_float(range[1]);
+    uint32_t c[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        c[k] = 0u;
+        if (p0 + k < npix) {
+            const unsigned long long m = packed[p0 + k];
+            depth[p0 + k] = (uint32_t)(m >> 32);
+            c[k] = field_rgb(m, count[p0 + k], edge[p0 + k], lo, hi);
+        }
+    }
+    rgb[g * 3 + 0] = c[0] | (c[1] << 24);
+    rgb[g * 3 + 1] = (c[1] >> 8) | (c[2] << 16);
+    rgb[g * 3 + 2] = (c[2] >> 16) | (c[3] << 8);
+}
+
 } // namespace
 
 void sph_launch_render_edges(const RenderParams &R, uint32_t *edge, hipStream_t s) {
@@ -223,4 +449,28 @@ void sph_launch_render(const RenderParams &R, const float4 *pos4, int n, bool pl
     }
     const int quads = (npix + 3) / 4;
     k_render_compose<<<(quads + 255) / 256, 256, 0, s>>>(depth, count, edge, npix, R.shade, rgb);
+}
+
+int sph_prepare_render_field() {
+    // (above 64 KB of dynamic LDS a kernel has to be told; the attribute is per device)
+    return (int)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_field_splat_tile),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFieldTileBytes);
+}
+
+void sph_launch_render_field(const RenderParams &R, const float4 *pos4, const float4 *vel4, int n, bool plain, int field,
+                            bool autoRange, float lo, float hi, unsigned long long *packed, uint32_t *depth, uint32_t *count,
+                            const uint32_t *edge, uint32_t *range, uint32_t *rgb, hipStream_t s) {
+    const int npix = R.width * R.height;
+    const bool reduce = autoRange && n > 0;
+    k_field_clear<<<(npix + 255) / 256, 256, 0, s>>>(packed, count, npix, range, reduce ? 0xFFFFFFFFu : __builtin_bit_cast(uint32_t, lo),
+                                                     reduce ? 0u : __builtin_bit_cast(uint32_t, hi));
+    if (reduce) k_field_range<<<min((n + 255) / 256, 1024), 256, 0, s>>>(vel4, n, field, range);
+    if (n > 0) {
+        if (plain) k_field_splat_plain<<<(n + 255) / 256, 256, 0, s>>>(pos4, vel4, n, R, field, packed, count);
+        else
+            k_field_splat_tile<<<(n + kFieldBlock - 1) / kFieldBlock, kSplatThreads, kFieldTileBytes, s>>>(pos4, vel4, n, R, field,
+                                                                                                          packed, count);
+    }
+    const int quads = (npix + 3) / 4;
+    k_field_compose<<<(quads + 255) / 256, 256, 0, s>>>(packed, count, edge, range, npix, depth, rgb);
 }

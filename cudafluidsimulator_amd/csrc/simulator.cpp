@@ -134,6 +134,21 @@ const unsigned char *Simulator::renderFrame(int *width, int *height) {
     return f;
 }
 
+const unsigned char *Simulator::renderField(int field, int *width, int *height) {
+    if (multi) {
+        fprintf(stderr, "sph: renderField: frames of a multi-GPU run (SPH_GPUS > 1) are not rendered\n");
+        return NULL;
+    }
+    if (!impl) return NULL;
+    SphFieldFrameOptions o{};
+    o.struct_size = (int32_t)sizeof o;
+    o.field = field;
+    check(impl, sph_render_field(impl, &o), "sph_render_field");
+    const unsigned char *f = sph_frame_host(impl, width, height);
+    if (!f) check(impl, SPH_EHIP, "sph_frame_host");
+    return f;
+}
+
 void Simulator::moveParticles(int2 mouse_pos) {
     if (multi) { // multi-GPU: the impulse needs the slabs' grids of a step: it rides on the next simulate()
         mcheck(multi, sph_mgpu_queue_click(multi, mouse_pos.x, mouse_pos.y), "sph_mgpu_queue_click");

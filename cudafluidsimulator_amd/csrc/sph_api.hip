@@ -164,6 +164,11 @@ struct sph_handle {
     bool frameValid = false;         // the buffers hold a rendered frame of the size in rp
     double renderSeconds = 0;        // clear + splat + compose, from HIP events (PairEvent ring)
     long long renderFrames = 0;
+    // The field frame (sph_render_field) adds the packed (depth bits << 32 | value bits) minimum per pixel and
+    // the range of the colour scale: two words on the device, copied to pinned memory with the frame.
+    unsigned long long *rPacked = nullptr;
+    uint32_t *rRange = nullptr, *rangeHost = nullptr;
+    bool fieldFrame = false;         // the last render was a field frame
     bool ready = false;     // state uploaded
     bool gridValid = false; // sorted streams + cell table match `sorted`
     int phase = 0;          // 0 idle, 1 grid done, 2 density done, 3 force done
@@ -1316,6 +1321,9 @@ void sph_destroy(sph_handle *h) {
     if (h->oobHost) (void)hipHostFree(h->oobHost);
     for (uint32_t *b : {h->rDepth, h->rCount, h->rEdge, h->rRgb}) if (b) (void)hipFree(b);
     if (h->frameHost) (void)hipHostFree(h->frameHost);
+    if (h->rPacked) (void)hipFree(h->rPacked);
+    if (h->rRange) (void)hipFree(h->rRange);
+    if (h->rangeHost) (void)hipHostFree(h->rangeHost);
     if (h->frameDrawn) (void)hipEventDestroy(h->frameDrawn);
     if (h->frameCopied) (void)hipEventDestroy(h->frameCopied);
     if (h->boundsDev) (void)hipFree(h->boundsDev);
@@ -2011,6 +2019,9 @@ int render_resize(sph_handle *h, int width, int height) {
     }
     if (h->frameHost) (void)hipHostFree(h->frameHost);
     h->frameHost = nullptr;
+    if (h->rPacked) (void)hipFree(h->rPacked); // (sized by the image: the next field frame allocates it again)
+    h->rPacked = nullptr;
+    h->fieldFrame = false;
     h->rp.width = h->rp.height = 0;
     const size_t npix = (size_t)width * (size_t)height;
     const size_t rgbBytes = (npix + 3) / 4 * 12; // whole groups of four pixels (k_render_compose)
@@ -2072,6 +2083,7 @@ int sph_render_frame(sph_handle *h, const SphRenderOptions *opt) {
     HIPCHK(h, hipGetLastError());
     h->renderFrames += 1;
     h->frameValid = true;
+    h->fieldFrame = false;
     // the frame leaves on the copy stream, behind an event, like the positions do
     HIPCHK(h, hipEventRecord(h->frameDrawn, s));
     HIPCHK(h, hipStreamWaitEvent(h->copy, h->frameDrawn, 0));
@@ -2122,6 +2134,81 @@ int sph_get_render_time(sph_handle *h, double *seconds, int64_t *frames, int res
         h->renderSeconds = 0;
         h->renderFrames = 0;
     }
+    return SPH_OK;
+}
+
+int sph_render_field(sph_handle *h, const SphFieldFrameOptions *opt) {
+    if (!h) return SPH_EINVAL;
+    SPH_ON_DEVICE(h);
+    if (h->external) return fail(h, SPH_ESTATE, "handle is in slab mode (external state): multi-GPU frames are not rendered");
+    if (!h->ready) return fail(h, SPH_ESTATE, "setup()/upload_state() must come first");
+    SphFieldFrameOptions o{};
+    if (opt) {
+        if (opt->struct_size <= 0) return fail(h, SPH_EINVAL, "SphFieldFrameOptions.struct_size is not set");
+        const size_t sz = (size_t)opt->struct_size;
+        memcpy(&o, opt, sz < sizeof o ? sz : sizeof o);
+    }
+    const int width = o.width == 0 ? 800 : o.width, height = o.height == 0 ? 600 : o.height;
+    const int pointSize = o.point_size == 0 ? 3 : o.point_size;
+    if (width < 1 || width > 4096 || height < 1 || height > 4096) return fail(h, SPH_EINVAL, "frame size must be 1..4096 x 1..4096");
+    if (pointSize < 1 || pointSize > 9 || (pointSize & 1) == 0) return fail(h, SPH_EINVAL, "point_size must be odd, 1..9");
+    if (o.field != SPH_FIELD_SPEED && o.field != SPH_FIELD_DENSITY && o.field != SPH_FIELD_PRESSURE)
+        return fail(h, SPH_EINVAL, "unknown field");
+    if (!std::isfinite(o.value_lo) || !std::isfinite(o.value_hi)) return fail(h, SPH_EINVAL, "value_lo / value_hi must be finite");
+    if (o.value_hi < o.value_lo) return fail(h, SPH_EINVAL, "value_hi < value_lo");
+    const bool autoRange = o.value_lo == 0.f && o.value_hi == 0.f;
+    int rc = render_resize(h, width, height);
+    if (rc) return rc;
+    if (!h->rPacked) HIPCHK(h, hipMalloc(&h->rPacked, (size_t)width * height * sizeof(unsigned long long)));
+    if (!h->rRange) HIPCHK(h, hipMalloc(&h->rRange, 2 * sizeof(uint32_t)));
+    if (!h->rangeHost) HIPCHK(h, hipHostMalloc(&h->rangeHost, 2 * sizeof(uint32_t), hipHostMallocDefault));
+    HIPCHK(h, (hipError_t)sph_prepare_render_field());
+    h->rp.radius = (pointSize - 1) / 2;
+    bool plain = false;
+    if (const char *e = getenv("SPH_RENDER_PLAIN")) plain = atoi(e) != 0;
+    hipStream_t s = h->compute;
+    if (h->framePending) { // the previous frame's copy still reads the device frame the compose is about to rewrite
+        HIPCHK(h, hipStreamWaitEvent(s, h->frameCopied, 0));
+        h->framePending = false;
+    }
+    PairEvent *pe = nullptr;
+    if ((rc = pair_begin(h, &h->renderSeconds, &pe))) return rc;
+    // pos4[cur] / vel4[cur]: the rows sph_render_frame draws and the rows sph_download_state reads
+    sph_launch_render_field(h->rp, h->pos4[h->cur], h->vel4[h->cur], h->n, plain, o.field, autoRange, o.value_lo, o.value_hi,
+                            h->rPacked, h->rDepth, h->rCount, h->rEdge, h->rRange, h->rRgb, s);
+    HIPCHK(h, hipEventRecord(pe->b, s));
+    HIPCHK(h, hipGetLastError());
+    h->renderFrames += 1;
+    h->frameValid = true;
+    h->fieldFrame = true;
+    HIPCHK(h, hipEventRecord(h->frameDrawn, s));
+    HIPCHK(h, hipStreamWaitEvent(h->copy, h->frameDrawn, 0));
+    HIPCHK(h, hipMemcpyAsync(h->frameHost, h->rRgb, (size_t)width * height * 3, hipMemcpyDeviceToHost, h->copy));
+    HIPCHK(h, hipMemcpyAsync(h->rangeHost, h->rRange, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, h->copy));
+    HIPCHK(h, hipEventRecord(h->frameCopied, h->copy));
+    h->framePending = true;
+    return SPH_OK;
+}
+
+int sph_download_field_buffer(sph_handle *h, uint32_t *value_bits) {
+    if (!h || !value_bits) return SPH_EINVAL;
+    SPH_ON_DEVICE(h);
+    if (!h->frameValid || !h->fieldFrame) return fail(h, SPH_ESTATE, "the last render was not a field frame (sph_render_field)");
+    HIPCHK(h, hipStreamSynchronize(h->compute));
+    const size_t npix = (size_t)h->rp.width * h->rp.height;
+    std::vector<unsigned long long> packed(npix);
+    HIPCHK(h, hipMemcpy(packed.data(), h->rPacked, npix * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < npix; ++i) value_bits[i] = (uint32_t)packed[i]; // the low words
+    return SPH_OK;
+}
+
+int sph_field_range(sph_handle *h, float *lo, float *hi) {
+    if (!h) return SPH_EINVAL;
+    SPH_ON_DEVICE(h);
+    if (!h->frameValid || !h->fieldFrame) return fail(h, SPH_ESTATE, "the last render was not a field frame (sph_render_field)");
+    if (h->framePending) HIPCHK(h, hipEventSynchronize(h->frameCopied));
+    if (lo) memcpy(lo, &h->rangeHost[0], sizeof(float));
+    if (hi) memcpy(hi, &h->rangeHost[1], sizeof(float));
     return SPH_OK;
 }
 

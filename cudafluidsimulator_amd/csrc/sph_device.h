@@ -219,3 +219,11 @@ void sph_launch_render_edges(const RenderParams &R, uint32_t *edge, hipStream_t 
 // plain = the one-atomic-per-hit check path
 void sph_launch_render(const RenderParams &R, const float4 *pos4, int n, bool plain, uint32_t *depth, uint32_t *count,
                        const uint32_t *edge, uint32_t *rgb, hipStream_t s);
+// The field frame: clear + (autoRange: min / max of the field over vel4[0, n) into range[0..1], else the bits of
+// lo / hi) + splat of (pos4, vel4)[0, n) into `packed` (depth bits << 32 | value bits) and `count` + compose into
+// rgb, which also leaves the depth words in `depth`.  field = SPH_FIELD_*.  sph_prepare_render_field() comes first on
+// the device that will run it (allows the tiled splat its LDS; returns a hipError_t).
+int sph_prepare_render_field();
+void sph_launch_render_field(const RenderParams &R, const float4 *pos4, const float4 *vel4, int n, bool plain, int field,
+                            bool autoRange, float lo, float hi, unsigned long long *packed, uint32_t *depth, uint32_t *count,
+                            const uint32_t *edge, uint32_t *range, uint32_t *rgb, hipStream_t s);

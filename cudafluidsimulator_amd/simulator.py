@@ -193,6 +193,35 @@ class Simulator:
                     "sph_download_frame_buffers")
         return dict(depth=out[0], count=out[1], edge=out[2])
 
+    # -- the field frame: particles coloured by a field of the nearest one (sph_render_field) --
+    def render_field(self, field="speed", lo=0.0, hi=0.0, width=0, height=0, point_size=0):
+        """Queue one frame coloured by `field` ("speed", "density", "pressure") over the scale lo..hi
+        (both 0: the minimum and maximum over all particles, reduced on the device); does not block.
+        frame_host() / frame_buffers() serve it like a flat frame."""
+        o = _lib.SphFieldFrameOptions()
+        o.struct_size = C.sizeof(_lib.SphFieldFrameOptions)
+        o.width, o.height, o.point_size = int(width), int(height), int(point_size)
+        o.field = _lib.FIELDS[field] if isinstance(field, str) else int(field)
+        o.value_lo, o.value_hi = float(lo), float(hi)
+        self._check(self._L.sph_render_field(self._h, C.byref(o)), "sph_render_field")
+
+    def field_buffer(self):
+        """(H, W) uint32: the bits of the field value of the particle that colours each pixel of the
+        last field frame, 0xFFFFFFFF where none covers it."""
+        w, h = C.c_int(0), C.c_int(0)
+        if not self._L.sph_frame_host(self._h, C.byref(w), C.byref(h)):
+            raise SphError("sph_frame_host failed: " + self._L.sph_last_error(self._h).decode())
+        out = np.zeros((h.value, w.value), np.uint32)
+        self._check(self._L.sph_download_field_buffer(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32))),
+                    "sph_download_field_buffer")
+        return out
+
+    def field_range(self):
+        """(lo, hi) as np.float32: the colour scale the last field frame used; blocks until it is known."""
+        lo, hi = C.c_float(0), C.c_float(0)
+        self._check(self._L.sph_field_range(self._h, C.byref(lo), C.byref(hi)), "sph_field_range")
+        return np.float32(lo.value), np.float32(hi.value)
+
     def render_time(self, reset=False):
         """(seconds, frames): GPU time of clear + splat + compose summed over `frames` renders."""
         sec, fr = C.c_double(0), C.c_int64(0)

@@ -88,6 +88,10 @@ class Simulator {
     // row 0 = top of the window -- rendered on the GPU (sph_render_frame in sph_c_api.h).  Owned by the
     // simulator, valid until the next call.  NULL (with a message on stderr) with SPH_GPUS > 1.
     const unsigned char *renderFrame(int *width, int *height);
+    // The same frame with the particles coloured by a field of the nearest one: field = SPH_FIELD_SPEED (0),
+    // SPH_FIELD_DENSITY (1) or SPH_FIELD_PRESSURE (2), the colour scale over the frame's own minimum and maximum
+    // (sph_render_field in sph_c_api.h).
+    const unsigned char *renderField(int field, int *width, int *height);
 };
 
 #endif

@@ -311,6 +311,44 @@ int sph_get_render_time(sph_handle *h, double *seconds, int64_t *frames, int res
 /* SPH_API_VERSION of the library that is actually loaded. */
 int sph_api_version(void);
 
+/* ---- the field frame: the same picture, the particles coloured by a field of the nearest one ----
+ * Additive to version 3: test for SPH_HAS_FIELD_FRAME.  Defined to the bit in DESIGN.md section 10 ("The field
+ * frame").  The scalar s of a particle comes from the values sph_download_state returns for it, all fp32, every
+ * operation rounded on its own: SPEED sqrtf((vx vx + vy vy) + vz vz), DENSITY rho, PRESSURE
+ * fmaxf(0, GAS_CONSTANT (rho - REST_DENSITY)).  Per pixel the library keeps the minimum over the covering
+ * particles of the 64-bit word (bits(w) << 32) | bits(s): the nearest particle, among several at the same depth
+ * the one with the smallest s.  q = (int)fminf(fmaxf(floorf(((s - lo) / (hi - lo)) * 256), 0), 255), q = 0 where
+ * hi == lo or the quotient is NaN; the colour runs blue - cyan - green - yellow - red over q = 0..255.  Box edges
+ * and empty pixels as in sph_render_frame; depth and count buffers are those sph_render_frame produces. */
+#define SPH_HAS_FIELD_FRAME 1
+enum {
+    SPH_FIELD_SPEED = 0,
+    SPH_FIELD_DENSITY = 1,
+    SPH_FIELD_PRESSURE = 2
+};
+typedef struct SphFieldFrameOptions {
+    int32_t struct_size;   /* = sizeof(SphFieldFrameOptions) */
+    int32_t width, height; /* 0 = 800 x 600; at most 4096 x 4096 */
+    int32_t point_size;    /* 0 = 3; odd, 1..9 */
+    int32_t field;         /* SPH_FIELD_* */
+    float value_lo;        /* the colour scale runs from value_lo (blue) to value_hi (red); both 0: the minimum */
+    float value_hi;        /* and maximum of s over ALL particles of this frame, reduced on the device */
+} SphFieldFrameOptions;
+/* sph_render_frame's queueing, streams and state rules (SPH_ESTATE before any state and for
+ * SPH_FLAG_EXTERNAL_STATE handles; works with SPH_FLAG_NO_READBACK; with SPH_SWEEP_LINKED drawn from the arrays
+ * sph_download_state reads; SPH_RENDER_PLAIN=1 selects the check path).  opt == NULL: 800 x 600, points of size
+ * 3, speed, automatic range.  An unknown field, a non-finite value_lo / value_hi, value_hi < value_lo:
+ * SPH_EINVAL.  Does not block: the automatic range stays on the device, where the compose reads it.
+ * sph_frame_host and sph_download_frame_buffers serve the last frame of either kind; sph_get_render_time counts
+ * both kinds. */
+int sph_render_field(sph_handle *h, const SphFieldFrameOptions *opt);
+/* The low words behind the last field frame, width x height, row 0 first: the bits of s of the particle that
+ * colours the pixel, 0xFFFFFFFF where no particle covers it.  SPH_ESTATE if the last render was not a field frame. */
+int sph_download_field_buffer(sph_handle *h, uint32_t *value_bits);
+/* The range the last field frame used (the options' or the reduced one).  Blocks until it is on the host.
+ * SPH_ESTATE if the last render was not a field frame. */
+int sph_field_range(sph_handle *h, float *lo, float *hi);
+
 const char *sph_build_info(void);
 
 #ifdef __cplusplus
