@@ -634,11 +634,12 @@ __global__ __launch_bounds__(256) void k_count_hits(SweepArgs A) {
     const int i = A.i_begin + blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t n = 0, dropped = 0;
     if (i < A.i_end) {
-        const int wv = (i - A.i_origin) >> 6;
+        // the density sweep's waves are numbered from i_origin, not from i_begin (slabs: i_begin is any row)
+        const int rel = i - A.i_origin, wv = rel >> 6;
         const uint32_t baseq = A.maskOff[2 * (size_t)wv];
         const int Q = (int)A.maskOff[2 * (size_t)wv + 1];
         if (baseq != SL_NONE) {
-            const uint4 *q4 = reinterpret_cast<const uint4 *>(A.maskPool) + baseq + (threadIdx.x & 63);
+            const uint4 *q4 = reinterpret_cast<const uint4 *>(A.maskPool) + baseq + (rel & 63);
             const bool qi = A.quiet && ((A.quiet[i >> 5] >> (i & 31)) & 1u);
             for (int q = 0; q < Q; ++q) {
                 const uint4 t = q4[(size_t)q * SPH_WAVE];

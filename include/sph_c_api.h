@@ -110,14 +110,9 @@ typedef struct SphOptions {
  * compute stream (seconds).  `steps` = number of steps accumulated. */
 typedef struct SphKernelTimes {
     double hash, sort, gather, density, force, readback;
-    uint64_t pair_tests; /* sum over steps, if SPH_FLAG_COUNT_PAIRS */
+    uint64_t pair_tests; /* candidate pair tests (see "What the pair counters report" below) */
     int64_t steps;
-    uint64_t pair_hits;  /* SPH_FLAG_COUNT_PAIRS + SPH_SWEEP_LIST: pair bodies the force sweep
-                            evaluates = candidates inside the support radius (popcount of the
-                            recorded hit masks) minus the pairs its zero-pair filter drops
-                            (neither row under pressure, same velocity: the pair adds exactly
-                            +-0), summed over steps; 0 for the other sweeps.  The unfiltered
-                            count is word 15 of sph_debug_counters() */
+    uint64_t pair_hits;  /* pair bodies the force sweep evaluated (SPH_SWEEP_LIST; 0 for the other sweeps) */
 } SphKernelTimes;
 
 typedef struct sph_handle sph_handle;
@@ -180,8 +175,53 @@ int sph_num_particles(const sph_handle *h);
 int sph_num_table_cells(const sph_handle *h);
 int sph_get_kernel_times(sph_handle *h, SphKernelTimes *out, int reset);
 const char *sph_last_error(const sph_handle *h); /* h may be NULL: create errors */
-/* Diagnostics: [0] = pair tests; [1..13] reserved, always zero; [14] = pair bodies the
- * force sweep evaluated, [15] = hits recorded (SPH_FLAG_COUNT_PAIRS + SPH_SWEEP_LIST). */
+/* ---- What the pair counters report (SPH_FLAG_COUNT_PAIRS; without the flag all of them stay 0) ----
+ * Three integers, exact and reproducible, held to a CPU count by tests/test_gpu_pair_counts.py.  All three are sums
+ * over the steps since the handle was created or since the last sph_get_kernel_times(reset = 1); reading does not
+ * consume them, and a new state (sph_setup / sph_upload_state / sph_load_state) or a click neither resets them nor
+ * adds to them.  A step counts the same whether it is launched, replayed from a graph (SPH_GRAPH=1), timed, or
+ * runs on a grid built ahead (SPH_PIPELINE=1).
+ *
+ * pair_tests (= word 0 of sph_debug_counters): for every particle, the occupancy of its existing neighbour cells
+ *   -- up to 27, fewer at the walls, the own cell and the particle itself included -- summed over the particles:
+ *   the candidates ONE 27-cell sweep tests (a step runs two such sweeps; the number is not doubled).  The cell of a
+ *   position is (int)(x / h) per axis in fp32.  A property of the state: every sweep (LIST, LDS, DIRECT, LINKED,
+ *   either key order) reports the same number, whatever it stages, shares or walks to get there.
+ * hits (word 15 of sph_debug_counters; SPH_SWEEP_LIST, 0 for the other sweeps): the ordered candidate pairs (i, j),
+ *   i == j included, that the density sweep records in its hit masks.  Strict mode, fp32, every operation rounded
+ *   on its own: dx = xi - xj, ..., d2 = (dx dx + dy dy) + dz dz; the pair is a hit when d2 <= h h OR sqrtf(d2) <= h
+ *   (the force terms test r^2 and r, simulator.cu:105,125; the union is "d2 <= the largest float whose sqrtf is <=
+ *   h").  For h = 0.1f and 0.2f the two conditions coincide; for h = 0.25f the second admits d2 = h h + 1 ulp.
+ * pair_hits (= word 14 of sph_debug_counters; SPH_SWEEP_LIST, 0 for the other sweeps): hits minus the pairs the
+ *   zero-pair filter drops.  The filter drops the pair (i, j) when BOTH rows are "quiet": pressure
+ *   fmaxf(0, GAS_CONSTANT (rho - REST_DENSITY)) == 0 with this step's rho, and velocity equal (three float
+ *   compares) to the step's reference velocity.  The reference velocity is the most common bit pattern among the
+ *   velocities of the 64 rows floor(k n / 64), k = 0..63, of the order the step's grid build starts from (particle-id
+ *   order after sph_setup / sph_upload_state; otherwise the previous step's cell-sorted order, which a snapshot
+ *   keeps); ties go to the lowest k.  This is NARROWER than "neither row under pressure, same velocity": such a
+ *   pair adds exactly +-0 whatever the common velocity is, but only pairs moving with the reference velocity are
+ *   dropped.  When every row of a single domain is quiet the force sweep skips its hit stream, and pair_hits
+ *   counts 0 for that step by the same rule (every hit is a pair of two quiet rows).
+ *   With SPH_ZERO_PAIR_FILTER=0 nothing is dropped: pair_hits == hits.
+ * Pool exhaustion: the hit-stream pool is cut into 64 equal sub-pools.  Wave w -- rows [64 w, 64 w + 64) of the
+ *   cell-sorted order -- reserves 64 Q quads (16 bytes) from sub-pool w mod 64, Q = ceil(W / 2), W = the largest
+ *   over its rows of the sum over the row's nine runs (the three x-adjacent cells of one (y, z)) of
+ *   ceil(candidates / 32).  Reservations are served in arrival order and every arrival advances the sub-pool's
+ *   cursor, whether it fits or not; when a sub-pool is too small for all its waves, WHICH of them fit is not
+ *   determined.  A wave that does not fit records no stream: it adds 0 to hits and 0 to pair_hits (its rows are
+ *   swept by the fallback, which tests every candidate again), and its candidates still count in pair_tests.
+ *   With the default pool size no wave of the reference's runs falls back, and the three numbers are exact.
+ * Slabs (sph_slab_density / sph_slab_force*): each handle counts its OWNED rows [i_begin, i_end); halo rows are
+ *   candidates only.  pair_tests and hits therefore sum over the slabs to the single domain's numbers.  Each slab
+ *   draws its own reference velocity, by the rule above, from the n_all rows sph_slab_sort starts from (halo rows
+ *   included), and only OWNED rows can be quiet: a halo row's density arrives after the sweep.  pair_hits of a
+ *   slab is therefore its hits minus the pairs of two of its owned quiet rows; a quiet row's pairs with halo rows
+ *   are counted.  That also holds while the slab driver's "every row is quiet" shortcut (owned and halo rows)
+ *   skips the hit stream: pair_hits is what the rule counts, not 0, although no body is evaluated in such a step.
+ *   Summed over the slabs, hits - (pairs of two quiet rows) <= pair_hits <= hits, with equality on the right
+ *   when the filter is off.
+ *   include/sph_mgpu.h's driver does not expose the counters.
+ * sph_debug_counters: [0] = pair_tests, [1..13] reserved, always zero, [14] = pair_hits, [15] = hits. */
 int sph_debug_counters(sph_handle *h, uint64_t *out16);
 
 /* ---- the step split into its phases (tests, profiling, slab driver) ---- */

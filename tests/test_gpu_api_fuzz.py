@@ -8,7 +8,7 @@ import pytest
 
 import cudafluidsimulator_amd as sph
 from cudafluidsimulator_amd import _lib
-from helpers import assert_bit_equal, clustered_state, random_state
+from helpers import assert_bit_equal, clustered_state, nasty_state, random_state
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -142,29 +142,6 @@ def test_random_call_sequences_over_slabs_stay_on_the_oracle(seed, monkeypatch):
             assert_bit_equal(g[k], r[k], f"{tag}: {k}")
         assert_bit_equal(np.array(mg.getPosition()), r["pos"], f"{tag}: getPosition()")
     mg.close()
-
-
-def nasty_state(n, seed, fast_factor=30.0):
-    """Positions on the box faces and in the corner cells, on exact multiples of the cell size, coincident,
-    several hundred in one cell, a thin sheet; velocities up to 30 (three cells per step)."""
-    rng = np.random.default_rng(seed)
-    pos = rng.uniform(0.1, 9.9, (n, 3)).astype(np.float32)
-    kind = rng.integers(0, 8, n)
-    face = kind == 0
-    pos[face] = np.where(rng.random((int(face.sum()), 3)) < 0.5, np.float32(0.1), np.float32(9.9))
-    onh = kind == 1                                              # exact multiples of h = 0.1f
-    pos[onh] = (rng.integers(1, 99, (int(onh.sum()), 3)).astype(np.float32) * np.float32(0.1))
-    same = kind == 2                                             # coincident (dist = 0: every term gated out)
-    pos[same] = np.float32(5.0)
-    crowd = kind == 3                                            # one crowded cell and its neighbours
-    pos[crowd] = (3.0 + 0.25 * rng.random((int(crowd.sum()), 3))).astype(np.float32)
-    sheet = kind == 4                                            # a sheet one cell thick
-    pos[sheet, 1] = (0.1 + 0.09 * rng.random(int(sheet.sum()))).astype(np.float32)
-    pos = np.clip(pos, np.float32(0.1), np.float32(9.9))
-    vel = rng.uniform(-1.0, 1.0, (n, 3)).astype(np.float32)
-    fast = rng.random(n) < 0.02
-    vel[fast] *= np.float32(fast_factor)
-    return pos, vel
 
 
 @pytest.mark.parametrize("seed", range(12))

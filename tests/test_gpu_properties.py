@@ -29,10 +29,15 @@ def test_config2_262144_all_sweeps_equal_and_oracle():
         assert_bit_equal(sa[k], sc[k], k + " (lds)")
     c.close()
     ref = O.OracleSim(262144, True)
-    ref.setup(); ref.step(12)
+    ref.setup()
+    want_tests = 0
+    for _ in range(12):
+        ref.step()
+        want_tests += ref.last_pair_tests()
     assert_bit_equal(sa["pos"], ref.download()["pos"], "oracle")
     kt = a.kernel_times()
-    assert kt.steps == 12 and kt.pair_tests > 12 * 3.5e6
+    assert kt.steps == 12 and kt.pair_tests == want_tests   # exact: the oracle's count, step by step
+    assert kt.pair_tests > 12 * 3.5e6
     a.close(); b.close()
 
 
@@ -56,9 +61,17 @@ def test_config3_4194304_invariants_and_determinism():
     b.close()
     # bounded oracle comparison at full size: 2 steps
     ref = O.OracleSim(n, True)
-    ref.setup(); ref.step(2)
+    ref.setup()
+    want_tests = 0
+    for _ in range(2):
+        ref.step()
+        want_tests += ref.last_pair_tests()
     c = run(n, 2)
     assert_bit_equal(c.download_state()["pos"], ref.download()["pos"], "oracle 2 steps @4M")
+    d = run(n, 2, flags=_lib.SPH_FLAG_COUNT_PAIRS)          # (a handle of its own: the parity run above keeps flags = 0)
+    assert d.kernel_times().pair_tests == want_tests        # exact: the oracle's count of the first two sweeps
+    d.close()
+    assert 8.5e8 * 2 < want_tests < 9.6e8 * 2
     a.close(); c.close()
 
 
