@@ -25,33 +25,12 @@ __device__ __forceinline__ int3 grid_cell(const DevParams &P, float x, float y,
     return c;
 }
 
-__global__ __launch_bounds__(256) void k_hash(DevParams P,
-                                              const float4 *__restrict__ pos4,
-                                              uint32_t *__restrict__ keys,
-                                              uint32_t *__restrict__ vals, int n) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    float4 p = pos4[i];
-    int3 c = grid_cell(P, p.x, p.y, p.z);
-    keys[i] = sph_cell_key(P, c.x, c.y, c.z);
-    vals[i] = (uint32_t)i;
-}
-
-void sph_launch_hash(const DevParams &P, const float4 *pos4, uint32_t *keys,
-                     uint32_t *vals, int n, hipStream_t s) {
-    if (n <= 0) return;
-    k_hash<<<(n + 255) / 256, 256, 0, s>>>(P, pos4, keys, vals, n);
-}
-
 // One pass over the sorted (key, source slot) pairs: move both float4 streams
 // into sorted order (16-B gathers, 16-B coalesced stores) and write cell
 // boundaries.  A lane compares its key with its wave neighbours through DPP
 // shuffles; only lanes 0 and 63 touch memory for the key next door.
 // cellRange must have been cleared beforehand (the first sort pass does it): empty cells
 // keep {0,0}.
-void sph_launch_lower_bounds(const uint32_t *sorted_keys, int n, Thresholds thr, int nthr,
-                             int *bounds_dev, hipStream_t s);
-
 __global__ __launch_bounds__(256) void k_gather_cells(
     const float4 *__restrict__ pos_in, const float4 *__restrict__ vel_in,
     const uint32_t *__restrict__ perm, const uint32_t *__restrict__ skeys,
@@ -124,28 +103,6 @@ void sph_launch_gather(const float4 *pos_in, const float4 *vel_in,
 // thresholds <= key; the one-pass radix sort on that small key keeps the previous
 // order inside every class, which is all the exchange needs (the combined array is
 // sorted by the full key afterwards).
-__global__ __launch_bounds__(256) void k_classify(DevParams P, const float4 *__restrict__ pos4,
-                                                  Thresholds thr, int nthr,
-                                                  uint32_t *__restrict__ keys,
-                                                  uint32_t *__restrict__ vals, int n) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    float4 p = pos4[i];
-    int3 c = grid_cell(P, p.x, p.y, p.z);
-    const uint32_t key = sph_cell_key(P, c.x, c.y, c.z);
-    uint32_t cls = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) cls += (k < nthr && key >= thr.v[k]) ? 1u : 0u;
-    keys[i] = cls;
-    vals[i] = (uint32_t)i;
-}
-
-void sph_launch_classify(const DevParams &P, const float4 *pos4, Thresholds thr, int nthr,
-                         uint32_t *keys, uint32_t *vals, int n, hipStream_t s) {
-    if (n <= 0) return;
-    k_classify<<<(n + 255) / 256, 256, 0, s>>>(P, pos4, thr, nthr, keys, vals, n);
-}
-
 // ---- slab path: the same stable partition in TWO launches instead of seven (classify, one
 // radix pass = histogram + row scan + scatter, gather, segment bounds, header copy).  At the
 // slab sizes this path sees (a few 10^5 particles per GPU) every launch costs its latency, not
@@ -279,24 +236,6 @@ void sph_launch_partition(const DevParams &P, const float4 *pos_in, const float4
 }
 
 size_t sph_partition_tiles(int n) { return (size_t)((n + PT_TILE - 1) / PT_TILE + 1); }
-
-__global__ __launch_bounds__(256) void k_gather_plain(const float4 *__restrict__ pos_in,
-                                                      const float4 *__restrict__ vel_in,
-                                                      const uint32_t *__restrict__ perm,
-                                                      float4 *__restrict__ pos_out,
-                                                      float4 *__restrict__ vel_out, int n) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t src = perm[i];
-    pos_out[i] = pos_in[src];
-    vel_out[i] = vel_in[src];
-}
-
-void sph_launch_gather_plain(const float4 *pos_in, const float4 *vel_in, const uint32_t *perm,
-                             float4 *pos_out, float4 *vel_out, int n, hipStream_t s) {
-    if (n <= 0) return;
-    k_gather_plain<<<(n + 255) / 256, 256, 0, s>>>(pos_in, vel_in, perm, pos_out, vel_out, n);
-}
 
 // Assembly of a slab's combined array: up to 8 (pos4, vel4) row ranges copied to their
 // places in ONE launch (they are small -- a boundary layer, a handful of migrants --

@@ -89,7 +89,6 @@ size_t sph_sort_workspace_blocks(int n);
 // Stable LSD sort of (keys[0], vals[0]) on `bits` key bits; returns the index
 // (0/1) of the buffer pair that holds the result.
 int sph_sort_pairs(const SortWorkspace &ws, int n, int bits, hipStream_t s);
-struct DevParams;
 // Same, for the grid build: the keys are the flattened cell indices of pos4[0..n), computed
 // inside the first histogram pass (no separate hash kernel, no iota of values in memory);
 // that pass also zeroes cellRange[0..numCells) (kernelResetGrid) for k_gather_cells.
@@ -97,8 +96,6 @@ int sph_sort_cells(const SortWorkspace &ws, const DevParams &P, const float4 *po
                    hipStream_t s, int2 *cellRange, int numCells);
 
 // ---- grid build (grid.hip) ----
-void sph_launch_hash(const DevParams &P, const float4 *pos4, uint32_t *keys,
-                     uint32_t *vals, int n, hipStream_t s);
 // bounds[k] = #keys < thr[k] over sorted keys (one binary search per lane)
 struct Thresholds { uint32_t v[8]; };
 // work that rides on the gather launch instead of a launch of its own (all optional)
@@ -121,15 +118,11 @@ void sph_launch_gather(const float4 *pos_in, const float4 *vel_in,
                        hipStream_t s, const GatherExtras &X = GatherExtras());
 void sph_launch_lower_bounds(const uint32_t *sorted_keys, int n, Thresholds thr, int nthr,
                              int *bounds_dev, hipStream_t s);
-void sph_launch_classify(const DevParams &P, const float4 *pos4, Thresholds thr, int nthr,
-                         uint32_t *keys, uint32_t *vals, int n, hipStream_t s);
 // stable partition of [0, n) by key class in two launches (tileCount: sph_partition_tiles(n) x 9 ints)
 void sph_launch_partition(const DevParams &P, const float4 *pos_in, const float4 *vel_in, float4 *pos_out,
                           float4 *vel_out, Thresholds thr, int nthr, int n, int *tileCount, int *bounds_dev,
                           hipStream_t s);
 size_t sph_partition_tiles(int n);
-void sph_launch_gather_plain(const float4 *pos_in, const float4 *vel_in, const uint32_t *perm,
-                             float4 *pos_out, float4 *vel_out, int n, hipStream_t s);
 struct SegmentTable {
     const float4 *spos[8];
     const float4 *svel[8];

@@ -1,0 +1,218 @@
+// The visualiser's frame: sph_render_frame / sph_render_field and what reads their results (kernels: render.hip).
+#include "sph_handle.h"
+
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+using namespace sph_host;
+
+namespace {
+
+// (re)allocate the frame buffers for a width x height image and draw the static edge layer
+int render_resize(sph_handle *h, int width, int height) {
+    if (h->rp.width == width && h->rp.height == height && h->rDepth) return SPH_OK;
+    // the old buffers may still be read by a queued compose / frame copy
+    HIPCHK(h, hipStreamSynchronize(h->compute));
+    HIPCHK(h, hipStreamSynchronize(h->copy));
+    h->framePending = false;
+    h->frameValid = false;
+    for (uint32_t **b : {&h->rDepth, &h->rCount, &h->rEdge, &h->rRgb}) {
+        if (*b) (void)hipFree(*b);
+        *b = nullptr;
+    }
+    if (h->frameHost) (void)hipHostFree(h->frameHost);
+    h->frameHost = nullptr;
+    if (h->rPacked) (void)hipFree(h->rPacked); // (sized by the image: the next field frame allocates it again)
+    h->rPacked = nullptr;
+    h->fieldFrame = false;
+    h->rp.width = h->rp.height = 0;
+    const size_t npix = (size_t)width * (size_t)height;
+    const size_t rgbBytes = (npix + 3) / 4 * 12; // whole groups of four pixels (k_render_compose)
+    HIPCHK(h, hipMalloc(&h->rDepth, npix * sizeof(uint32_t)));
+    HIPCHK(h, hipMalloc(&h->rCount, npix * sizeof(uint32_t)));
+    HIPCHK(h, hipMalloc(&h->rEdge, npix * sizeof(uint32_t)));
+    HIPCHK(h, hipMalloc(&h->rRgb, rgbBytes));
+    HIPCHK(h, hipHostMalloc(&h->frameHost, rgbBytes, hipHostMallocDefault));
+    memset(h->frameHost, 0, rgbBytes);
+    if (!h->frameDrawn) HIPCHK(h, hipEventCreateWithFlags(&h->frameDrawn, hipEventDisableTiming));
+    if (!h->frameCopied) HIPCHK(h, hipEventCreateWithFlags(&h->frameCopied, hipEventDisableTiming));
+    RenderParams R = h->rp;
+    R.width = width;
+    R.height = height;
+    R.Wf = (float)width;
+    R.Hf = (float)height;
+    sph_launch_render_edges(R, h->rEdge, h->compute);
+    HIPCHK(h, hipGetLastError());
+    h->rp = R;
+    return SPH_OK;
+}
+
+// a caller's option struct into `o` (zero: defaults): as many bytes as its struct_size says, at most all of `o`
+template <class Opt>
+int copy_options(sph_handle *h, const Opt *opt, Opt &o, const char *unset) {
+    if (!opt) return SPH_OK;
+    if (opt->struct_size <= 0) return fail(h, SPH_EINVAL, unset);
+    const size_t sz = (size_t)opt->struct_size;
+    memcpy(&o, opt, sz < sizeof o ? sz : sizeof o);
+    return SPH_OK;
+}
+
+// Both renderers up to their launch: state and option checks (`rest(o)`: the entry point's own, a message or
+// null), the buffers, the wait for the previous frame's copy, the start of the timed section.
+template <class Opt, class Rest>
+int frame_begin(sph_handle *h, const Opt *opt, const char *unset, Rest rest, bool field, Opt &o, bool &plain, PairEvent *&pe) {
+    SPH_ON_DEVICE(h);
+    if (h->external) return reject_slab_mode(h, ": multi-GPU frames are not rendered");
+    if (!h->ready) return fail(h, SPH_ESTATE, "setup()/upload_state() must come first");
+    int rc = copy_options(h, opt, o, unset);
+    if (rc) return rc;
+    const int width = o.width == 0 ? 800 : o.width, height = o.height == 0 ? 600 : o.height;
+    const int pointSize = o.point_size == 0 ? 3 : o.point_size;
+    if (width < 1 || width > 4096 || height < 1 || height > 4096) return fail(h, SPH_EINVAL, "frame size must be 1..4096 x 1..4096");
+    if (pointSize < 1 || pointSize > 9 || (pointSize & 1) == 0) return fail(h, SPH_EINVAL, "point_size must be odd, 1..9");
+    if (const char *bad = rest(o)) return fail(h, SPH_EINVAL, bad);
+    if ((rc = render_resize(h, width, height))) return rc;
+    if (field) {
+        if (!h->rPacked) HIPCHK(h, hipMalloc(&h->rPacked, (size_t)width * height * sizeof(unsigned long long)));
+        if (!h->rRange) HIPCHK(h, hipMalloc(&h->rRange, 2 * sizeof(uint32_t)));
+        if (!h->rangeHost) HIPCHK(h, hipHostMalloc(&h->rangeHost, 2 * sizeof(uint32_t), hipHostMallocDefault));
+        HIPCHK(h, (hipError_t)sph_prepare_render_field());
+    }
+    h->rp.radius = (pointSize - 1) / 2;
+    plain = false;
+    if (const char *e = getenv("SPH_RENDER_PLAIN")) plain = atoi(e) != 0;
+    if (h->framePending) { // the previous frame's copy still reads the device frame the compose is about to rewrite
+        HIPCHK(h, hipStreamWaitEvent(h->compute, h->frameCopied, 0));
+        h->framePending = false;
+    }
+    return pair_begin(h, &h->renderSeconds, &pe);
+}
+
+// ... and after it: the end of the timed section, the counters, the frame (a field frame: and the range of its
+// colour scale) on its way to pinned memory
+int frame_finish(sph_handle *h, PairEvent *pe, bool field) {
+    HIPCHK(h, hipEventRecord(pe->b, h->compute));
+    HIPCHK(h, hipGetLastError());
+    h->renderFrames += 1;
+    h->frameValid = true;
+    h->fieldFrame = field;
+    // the frame leaves on the copy stream, behind an event, like the positions do
+    HIPCHK(h, hipEventRecord(h->frameDrawn, h->compute));
+    HIPCHK(h, hipStreamWaitEvent(h->copy, h->frameDrawn, 0));
+    HIPCHK(h, hipMemcpyAsync(h->frameHost, h->rRgb, (size_t)h->rp.width * h->rp.height * 3, hipMemcpyDeviceToHost, h->copy));
+    if (field) HIPCHK(h, hipMemcpyAsync(h->rangeHost, h->rRange, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, h->copy));
+    HIPCHK(h, hipEventRecord(h->frameCopied, h->copy));
+    h->framePending = true;
+    return SPH_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int sph_render_frame(sph_handle *h, const SphRenderOptions *opt) {
+    if (!h) return SPH_EINVAL;
+    SphRenderOptions o{};
+    bool plain = false;
+    PairEvent *pe = nullptr;
+    auto rest = [](const SphRenderOptions &o) -> const char * {
+        return o.shade != SPH_SHADE_FLAT && o.shade != SPH_SHADE_COUNT ? "unknown shade" : nullptr;
+    };
+    int rc = frame_begin(h, opt, "SphRenderOptions.struct_size is not set", rest, false, o, plain, pe);
+    if (rc) return rc;
+    h->rp.shade = o.shade;
+    // The current state: after a step the rows the force sweep wrote, still in that step's cell-sorted order;
+    // after setup / upload / load (and always with SPH_SWEEP_LINKED) in particle-id order.  A grid built
+    // ahead for the next step only reads these rows.
+    sph_launch_render(h->rp, h->pos4[h->cur], h->n, plain, h->rDepth, h->rCount, h->rEdge, h->rRgb, h->compute);
+    return frame_finish(h, pe, false);
+}
+
+const uint8_t *sph_frame_host(sph_handle *h, int *width, int *height) {
+    if (!h) return nullptr;
+    if (!h->frameValid) {
+        h->err = "sph_render_frame must come first";
+        return nullptr;
+    }
+    if (h->framePending && hipEventSynchronize(h->frameCopied) != hipSuccess) {
+        h->err = "frame copy failed";
+        return nullptr;
+    }
+    if (width) *width = h->rp.width;
+    if (height) *height = h->rp.height;
+    return h->frameHost;
+}
+
+int sph_download_frame_buffers(sph_handle *h, uint32_t *depth_bits, uint32_t *count, uint32_t *edge_depth_bits) {
+    if (!h) return SPH_EINVAL;
+    SPH_ON_DEVICE(h);
+    if (!h->frameValid) return fail(h, SPH_ESTATE, "sph_render_frame must come first");
+    HIPCHK(h, hipStreamSynchronize(h->compute));
+    const size_t bytes = (size_t)h->rp.width * h->rp.height * sizeof(uint32_t);
+    if (depth_bits) HIPCHK(h, hipMemcpy(depth_bits, h->rDepth, bytes, hipMemcpyDeviceToHost));
+    if (count) HIPCHK(h, hipMemcpy(count, h->rCount, bytes, hipMemcpyDeviceToHost));
+    if (edge_depth_bits) HIPCHK(h, hipMemcpy(edge_depth_bits, h->rEdge, bytes, hipMemcpyDeviceToHost));
+    return SPH_OK;
+}
+
+int sph_get_render_time(sph_handle *h, double *seconds, int64_t *frames, int reset) {
+    if (!h) return SPH_EINVAL;
+    SPH_ON_DEVICE(h);
+    for (auto &pe : h->pairs)
+        if (pe.used && pe.target == &h->renderSeconds) {
+            int rc = resolve_pair(h, pe);
+            if (rc) return rc;
+        }
+    if (seconds) *seconds = h->renderSeconds;
+    if (frames) *frames = h->renderFrames;
+    if (reset) {
+        h->renderSeconds = 0;
+        h->renderFrames = 0;
+    }
+    return SPH_OK;
+}
+
+int sph_render_field(sph_handle *h, const SphFieldFrameOptions *opt) {
+    if (!h) return SPH_EINVAL;
+    SphFieldFrameOptions o{};
+    bool plain = false;
+    PairEvent *pe = nullptr;
+    auto rest = [](const SphFieldFrameOptions &o) -> const char * {
+        if (o.field != SPH_FIELD_SPEED && o.field != SPH_FIELD_DENSITY && o.field != SPH_FIELD_PRESSURE) return "unknown field";
+        if (!std::isfinite(o.value_lo) || !std::isfinite(o.value_hi)) return "value_lo / value_hi must be finite";
+        return o.value_hi < o.value_lo ? "value_hi < value_lo" : nullptr;
+    };
+    int rc = frame_begin(h, opt, "SphFieldFrameOptions.struct_size is not set", rest, true, o, plain, pe);
+    if (rc) return rc;
+    const bool autoRange = o.value_lo == 0.f && o.value_hi == 0.f;
+    // pos4[cur] / vel4[cur]: the rows sph_render_frame draws and the rows sph_download_state reads
+    sph_launch_render_field(h->rp, h->pos4[h->cur], h->vel4[h->cur], h->n, plain, o.field, autoRange, o.value_lo, o.value_hi,
+                            h->rPacked, h->rDepth, h->rCount, h->rEdge, h->rRange, h->rRgb, h->compute);
+    return frame_finish(h, pe, true);
+}
+
+int sph_download_field_buffer(sph_handle *h, uint32_t *value_bits) {
+    if (!h || !value_bits) return SPH_EINVAL;
+    SPH_ON_DEVICE(h);
+    if (!h->frameValid || !h->fieldFrame) return fail(h, SPH_ESTATE, "the last render was not a field frame (sph_render_field)");
+    HIPCHK(h, hipStreamSynchronize(h->compute));
+    const size_t npix = (size_t)h->rp.width * h->rp.height;
+    std::vector<unsigned long long> packed(npix);
+    HIPCHK(h, hipMemcpy(packed.data(), h->rPacked, npix * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < npix; ++i) value_bits[i] = (uint32_t)packed[i]; // the low words
+    return SPH_OK;
+}
+
+int sph_field_range(sph_handle *h, float *lo, float *hi) {
+    if (!h) return SPH_EINVAL;
+    SPH_ON_DEVICE(h);
+    if (!h->frameValid || !h->fieldFrame) return fail(h, SPH_ESTATE, "the last render was not a field frame (sph_render_field)");
+    if (h->framePending) HIPCHK(h, hipEventSynchronize(h->frameCopied));
+    if (lo) memcpy(lo, &h->rangeHost[0], sizeof(float));
+    if (hi) memcpy(hi, &h->rangeHost[1], sizeof(float));
+    return SPH_OK;
+}
+
+} // extern "C"

@@ -1,0 +1,221 @@
+// The handle behind include/sph_c_api.h and the few helpers its host translation units share (sph_api.hip,
+// sph_step.hip, sph_readback.hip, sph_slab.hip, sph_snapshot.hip, sph_frame.hip).  Host code only.
+#pragma once
+
+#include "sph_c_api.h"
+#include "sph_device.h"
+
+#include <chrono>
+#include <string>
+
+namespace sph_host {
+
+constexpr int kEventRing = 64;
+constexpr int kCounterWords = 16 + 256 * 16; // 16 spare words, then 256 shards x 16: [0] pair tests,
+                                             // [1..13] reserved (always zero), [14] bodies, [15] hits
+constexpr size_t kCursorBytes = (size_t)SL_POOL_SHARDS * SL_CURSOR_STRIDE * sizeof(unsigned long long);
+
+struct PairEvent { // one timed section of the slab path
+    hipEvent_t a = nullptr, b = nullptr;
+    double *target = nullptr;
+    bool used = false;
+};
+constexpr int kPairRing = 48;
+
+struct StepEvents {
+    hipEvent_t e[6] = {}; // start, hash, sort, gather, density, force
+    hipEvent_t c[2] = {}; // copy start / end
+    bool used = false, hasCopy = false, counted = false;
+};
+
+} // namespace sph_host
+
+struct sph_handle {
+    // ---- sph_api.hip: settings, the particle streams and the grid's buffers, state flags ----
+    SphSettings settings{};
+    SphOptions opt{};
+    DevParams P{};
+    int n = 0, cap = 0, device = 0;
+    hipStream_t compute = nullptr, copy = nullptr;
+    float4 *pos4[2] = {nullptr, nullptr};
+    float4 *vel4[2] = {nullptr, nullptr};
+    int cur = 0;     // buffers holding the current state
+    int sorted = -1; // buffers holding the sorted streams of the last grid build
+    SortWorkspace ws{};
+    int sortedKeyBuf = 0;
+    int2 *cellRange = nullptr;       // the cell table of the LAST grid build (= cellTable[cellCur])
+    int2 *cellTable[2] = {nullptr, nullptr}; // two tables: a grid built ahead (below) must not clobber the last step's
+    int cellCur = 0;
+    float *devPos[2] = {nullptr, nullptr};
+    float *hostPos = nullptr; // pinned, n*3
+    bool hostPosIsInit = false; // setup() restored the initial state on the device: getPosition() fetches it on demand
+    // Pinned staging for state uploads (two halves, ping-pong).  A hipMemcpy from pageable
+    // memory makes the runtime pin and later unpin the caller's pages; the unpin is deferred
+    // and stalls the GPU's queues for 6-28 ms some time AFTER the call returned -- inside the
+    // first steps of the run that follows (measured).
+    float4 *stage[2] = {nullptr, nullptr};
+    hipEvent_t stageFree[2] = {nullptr, nullptr};
+    bool mappedPos = false;   // SPH_FLAG_MAPPED_POSITIONS: devPos[] alias hostPos (host-mapped)
+    float4 *force4 = nullptr;
+    unsigned long long *pairCounter = nullptr; // device
+    unsigned long long *pairHost = nullptr;    // pinned
+    SphKernelTimes kt{};
+    float4 *pv8 = nullptr;
+    uint32_t *maskPool = nullptr, *maskOff = nullptr; // SPH_SWEEP_LIST
+    uint32_t *noneList = nullptr;    // SPH_SWEEP_LIST: waves without a stream this step (pool exhausted)
+    uint32_t *hitCount = nullptr;    // SPH_SWEEP_LIST: recorded hits per sorted row
+    uint32_t *quiet = nullptr;       // SPH_SWEEP_LIST: one bit per sorted row, the force sweep's zero-pair filter
+    float4 *quietVref = nullptr;     // ... its reference velocity (device; picked by the first sort pass) ...
+    unsigned long long *calm = nullptr; // ... and one bit per sorted row "moves with it" (written by the gather launch)
+    float4 *initPos4 = nullptr;      // setup()'s initial positions (+ids), kept on the device for the next setup()
+    SphOobLog *oobHost = nullptr;    // host-mapped: positions outside the grid met by the cell hash
+    uint32_t oobSeen = 0;            // how many of them were already reported
+    int initZLayers = 0;
+    bool useQuiet = true;            // SPH_ZERO_PAIR_FILTER=0 switches the filter off (A/B; same results)
+    uint64_t hitsRecorded = 0;       // SPH_FLAG_COUNT_PAIRS: hits in the stream, before the filter
+    unsigned long long *maskCursor = nullptr;
+    unsigned long long maskCapacity = 0; // quads (16 B)
+    int zLayers = 0;        // occupied z-layers of the (owned) particles: sizes xcd_tile()'s chunks
+    int tileChunkEnv = -1;  // SPH_TILE_CHUNK: -1 auto, 0 contiguous eighths, >0 tiles per chunk
+    int tileRotate = -1;    // SPH_XCD_ROTATE: xcd_tile()'s rotation period in groups (z-layers), 0 = off;
+                            // -1 (default): off for the single domain, every layer for a slab (see slab_rotate)
+    bool ready = false;     // state uploaded
+    bool gridValid = false; // sorted streams + cell table match `sorted`
+    int phase = 0;          // 0 idle, 1 grid done, 2 density done, 3 force done
+    std::string err;
+
+    // ---- sph_step.hip: the step pipeline, its events and the host-side trace ----
+    // Step pipelining (timed steps): simulateAndTime() has to wait for its step, and between that wait and the
+    // first launch of the next call the GPU idled ~0.12 ms per step (host: two event queries, the return to the
+    // caller -- Python in bench.py --, the next call's first launches).  A timed step therefore queues the NEXT
+    // step's grid build (which only needs the state this step leaves behind) BEFORE it waits, and waits for its
+    // own force event instead of the whole stream; the next step finds its grid built.  Anything that changes
+    // or replaces the state in between (click, upload, load) simply drops the grid built ahead.
+    bool gridAhead = false;
+    int2 *clickTable = nullptr;      // cell table of the last COMPLETED step (what sph_apply_click walks)
+    bool clickValid = false;
+    bool aheadEnabled = true;        // default: below 1.5 M particles; SPH_PIPELINE=0/1 forces it (same results)
+    sph_host::StepEvents *aheadEv = nullptr;
+    hipEvent_t computeDone[2] = {nullptr, nullptr}, copyDone[2] = {nullptr, nullptr};
+    bool copyPending[2] = {false, false};
+    bool stepTimed = false;          // sph_step(times != NULL) is running (the read-back phase picks the copy path by it)
+    int rbDeferredSlot = -1;         // the read-back phase left this slot's copy to sph_step
+    bool cursorClean = false; // the gather launch of this grid build cleared the hit-stream cursors
+    long long stepIndex = 0;
+    sph_host::StepEvents ring[sph_host::kEventRing];
+    int ringHead = 0;
+    sph_host::StepEvents *curEv = nullptr;
+    sph_host::PairEvent pairs[sph_host::kPairRing];
+    int pairHead = 0;
+    // SPH_STEP_TRACE=1 (diagnostic): where the HOST spends a timed step, printed by sph_destroy
+    bool trace = false;
+    double trEnqueue = 0, trSync = 0, trPost = 0, trBetween = 0, trPh[5] = {0, 0, 0, 0, 0};
+    long long trSteps = 0;
+    std::chrono::steady_clock::time_point trLastReturn{};
+    hipEvent_t trBase = nullptr;     // first traced step's start: GPU-side timeline of every later step
+
+    // ---- sph_readback.hip ----
+    // Read-back of a TIMED step through an SDMA engine (hsa_amd_memory_async_copy) instead of the HIP runtime's
+    // copy, which on this platform is a blit KERNEL: beside it the first histogram pass takes 84 instead of
+    // 27 us, the density sweep +30 us, the force sweep +50 us.  The engine moves the
+    // same 56 GB/s and occupies no CU.  HIP offers no way to order an HSA copy behind a kernel, so the copy
+    // is issued by the host right after it has seen the step's force sweep finish -- which a timed step
+    // waits for anyway; untimed steps (simulate()) keep the stream-ordered HIP copy.  SPH_READBACK_SDMA=0: off.
+    bool sdmaOk = false;
+    uint64_t hsaGpu = 0, hsaCpu = 0; // hsa_agent_t::handle
+    uint64_t rbSig[2] = {0, 0};      // hsa_signal_t::handle
+    bool rbPending[2] = {false, false};
+    uint32_t sdmaEngine = 0;         // hsa_amd_sdma_engine_id_t picked by sdma_init (0: the HSA runtime's own choice)
+    double hsaTickSeconds = 0;
+
+    // ---- sph_slab.hip ----
+    int slabOwnedBegin = 0, slabOwnedEnd = 0; // rows of the last sph_slab_density (the rest of [0, n_all) is halo)
+    bool external = false;  // pos4/vel4 are caller-owned (sph_bind_buffers)
+    hipStream_t ownCompute = nullptr;
+    int *boundsDev = nullptr, *boundsHost = nullptr;
+    int *partTiles = nullptr; // slab partition: class counts per 1024-particle tile
+
+    // ---- sph_frame.hip ----
+    // The visualiser's frame (render.hip), allocated by the first sph_render_frame: per-pixel depth bits,
+    // hit count and the static box-edge layer on the device, the RGB8 frame on the device and in pinned memory.
+    RenderParams rp{};               // size / point radius / shade of the last render (width 0: none yet)
+    uint32_t *rDepth = nullptr, *rCount = nullptr, *rEdge = nullptr, *rRgb = nullptr;
+    uint8_t *frameHost = nullptr;
+    hipEvent_t frameDrawn = nullptr, frameCopied = nullptr;
+    bool framePending = false;       // a frame copy is queued on the copy stream
+    bool frameValid = false;         // the buffers hold a rendered frame of the size in rp
+    double renderSeconds = 0;        // clear + splat + compose, from HIP events (PairEvent ring)
+    long long renderFrames = 0;
+    // The field frame (sph_render_field) adds the packed (depth bits << 32 | value bits) minimum per pixel and
+    // the range of the colour scale: two words on the device, copied to pinned memory with the frame.
+    unsigned long long *rPacked = nullptr;
+    uint32_t *rRange = nullptr, *rangeHost = nullptr;
+    bool fieldFrame = false;         // the last render was a field frame
+};
+
+#define HIPCHK(h, call)                                                               \
+    do {                                                                              \
+        hipError_t e__ = (call);                                                      \
+        if (e__ != hipSuccess) {                                                      \
+            (h)->err = std::string(#call) + ": " + hipGetErrorString(e__);            \
+            return SPH_EHIP;                                                          \
+        }                                                                             \
+    } while (0)
+
+// Every entry point that queues work makes the handle's device current first: a host
+// thread that drives several GPUs (include/sph_mgpu.h) or switched devices since
+// sph_create would otherwise launch on the wrong one.
+#define SPH_ON_DEVICE(h)                                                              \
+    do {                                                                              \
+        int d__ = -1;                                                                 \
+        if (hipGetDevice(&d__) != hipSuccess || d__ != (h)->device)                    \
+            HIPCHK(h, hipSetDevice((h)->device));                                     \
+    } while (0)
+
+namespace sph_host {
+
+// sph_api.hip
+int fail(sph_handle *h, int code, const std::string &msg);
+// SPH_ESTATE for a single-domain entry point on a slab handle; `hint` ends the message ("" or ": use ...")
+int reject_slab_mode(sph_handle *h, const char *hint = ": use the sph_slab_* entry points");
+// sph_step.hip
+void report_oob(sph_handle *h);
+int key_bits(const sph_handle *h);
+void state_replaced(sph_handle *h);
+SweepArgs make_sweep_args(sph_handle *h);
+GatherExtras gather_extras(sph_handle *h);
+int tile_chunk(const sph_handle *h, int count, int layers);
+int launch_density(sph_handle *h, SweepArgs &A, hipStream_t stream);
+int pair_begin(sph_handle *h, double *target, PairEvent **out, hipStream_t stream = nullptr);
+int resolve_pair(sph_handle *h, PairEvent &pe);
+int begin_step_events(sph_handle *h);
+int resolve_events(sph_handle *h, StepEvents &se);
+void drop_grid_ahead(sph_handle *h);
+// sph_readback.hip
+void sdma_init(sph_handle *h);
+int sdma_wait(sph_handle *h, int slot);
+int sdma_issue(sph_handle *h, int slot);
+void sdma_destroy(sph_handle *h);
+
+// rows -> device through the handle's pinned staging halves; `fill(k, dst, count)` packs rows
+// [k, k+count) into dst.  Returns when every row is on the device.
+constexpr size_t kStageRows = (size_t)1 << 19; // 8 MB per half
+template <class Fill>
+int staged_upload(sph_handle *h, float4 *dev, size_t n, Fill fill) {
+    for (int b = 0; b < 2; ++b) {
+        if (!h->stage[b]) HIPCHK(h, hipHostMalloc(&h->stage[b], kStageRows * sizeof(float4), hipHostMallocDefault));
+        if (!h->stageFree[b]) HIPCHK(h, hipEventCreateWithFlags(&h->stageFree[b], hipEventDisableTiming));
+    }
+    int b = 0;
+    for (size_t k = 0; k < n; k += kStageRows, b ^= 1) {
+        const size_t cnt = n - k < kStageRows ? n - k : kStageRows;
+        HIPCHK(h, hipEventSynchronize(h->stageFree[b])); // (a never-recorded event is complete)
+        fill(k, h->stage[b], cnt);
+        HIPCHK(h, hipMemcpyAsync(dev + k, h->stage[b], cnt * sizeof(float4), hipMemcpyHostToDevice, h->compute));
+        HIPCHK(h, hipEventRecord(h->stageFree[b], h->compute));
+    }
+    HIPCHK(h, hipStreamSynchronize(h->compute));
+    return SPH_OK;
+}
+
+} // namespace sph_host

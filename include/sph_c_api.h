@@ -179,8 +179,8 @@ const char *sph_last_error(const sph_handle *h); /* h may be NULL: create errors
  * Three integers, exact and reproducible, held to a CPU count by tests/test_gpu_pair_counts.py.  All three are sums
  * over the steps since the handle was created or since the last sph_get_kernel_times(reset = 1); reading does not
  * consume them, and a new state (sph_setup / sph_upload_state / sph_load_state) or a click neither resets them nor
- * adds to them.  A step counts the same whether it is launched, replayed from a graph (SPH_GRAPH=1), timed, or
- * runs on a grid built ahead (SPH_PIPELINE=1).
+ * adds to them.  A step counts the same whether it is timed or not and whether or not it runs on a grid built ahead
+ * (SPH_PIPELINE=1).
  *
  * pair_tests (= word 0 of sph_debug_counters): for every particle, the occupancy of its existing neighbour cells
  *   -- up to 27, fewer at the walls, the own cell and the particle itself included -- summed over the particles:

@@ -1,7 +1,6 @@
 """Random sequences of the C-ABI's calls under random library knobs, against the oracle after every step.
 Each seed draws the sweep family, the handle flags, the environment knobs that change the step's control flow
-(graph replay, the grid build queued ahead, the read-back path, the zero-pair filter, the pair body's divide
-chains) and ~30 operations: simulate / simulateAndTime / the four phases by hand / click / getPosition /
+(the grid build queued ahead, the read-back path, the zero-pair filter, the pair body's divide chains) and ~30 operations: simulate / simulateAndTime / the four phases by hand / click / getPosition /
 upload of a new state / setup() / save + load of a snapshot.  Strict mode: every comparison is bit-exact."""
 import numpy as np
 import pytest
@@ -12,7 +11,7 @@ from helpers import assert_bit_equal, clustered_state, nasty_state, random_state
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
-KNOBS = {"SPH_GRAPH": ("0", "1"), "SPH_PIPELINE": ("0", "1"), "SPH_READBACK_SDMA": ("0", "1"),
+KNOBS = {"SPH_PIPELINE": ("0", "1"), "SPH_READBACK_SDMA": ("0", "1"),
          "SPH_ZERO_PAIR_FILTER": ("0", "1"), "SPH_SLIM_DIV": ("0", "1"), "SPH_XCD_ROTATE": ("0", "1", "5")}
 
 
@@ -30,6 +29,7 @@ def test_random_call_sequences_stay_on_the_oracle(seed, monkeypatch, tmp_path):
     rng = np.random.default_rng(1000 + seed)
     sweep = ["list", "list", "lds", "direct"][rng.integers(4)]
     flags = int(rng.choice([0, 0, _lib.SPH_FLAG_MAPPED_POSITIONS])) if sweep != "direct" else 0
+    rng.choice(("0", "1"))  # (discarded: the draw of a knob that is gone; keeps every seed's sequence what it was)
     env = {k: str(rng.choice(v)) for k, v in KNOBS.items()}
     for k, v in env.items():
         monkeypatch.setenv(k, v)

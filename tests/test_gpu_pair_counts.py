@@ -179,10 +179,9 @@ def test_unreset_counters_are_the_sum_over_steps():
     sim.close()
 
 
-def test_graph_replays_count_like_launches(monkeypatch):
-    monkeypatch.setenv("SPH_GRAPH", "1")
+def test_six_plain_steps_on_the_second_nasty_state():
     sim, ref, h, cells = make("nasty2")
-    check_steps(sim, ref, h, cells, 6, what="graph")
+    check_steps(sim, ref, h, cells, 6, what="nasty2")
     sim.close()
 
 

@@ -511,12 +511,10 @@ def test_zero_pair_filter_free_fall_drops_every_pair():
 # ---- reachable product paths that had no test ----
 
 @pytest.mark.parametrize("n", [4096, 262144])
-def test_step_graphs_equal_the_oracle(n, monkeypatch):
-    """SPH_GRAPH=1: the three phases of a step replayed as hipGraphs (captured once per
-    read-back slot, sph_api.hip capture_step_graph).  Ten steps, bit-equal to the oracle after
-    every one of them (getPosition() included: the read-back runs beside the replays), and the
-    per-kernel event bookkeeping of the replays still adds up to ten steps."""
-    monkeypatch.setenv("SPH_GRAPH", "1")
+def test_ten_mixed_steps_with_getposition_after_each(n):
+    """Ten steps, untimed and timed in turn (the timed ones queue the next step's grid build ahead at these
+    sizes), bit-equal to the oracle after every one of them (getPosition() included: the read-back runs
+    beside the next step), and the per-kernel event bookkeeping still adds up to ten steps."""
     sim, ref = make_pair(n, True)
     t = sph.Times()
     for k in range(1, 11):
@@ -525,27 +523,24 @@ def test_step_graphs_equal_the_oracle(n, monkeypatch):
         else:
             sim.simulateAndTime(t)
         ref.step()
-        assert_bit_equal(np.array(sim.getPosition()), ref.download()["pos"], f"graph replay, step {k}: getPosition")
-    compare_state(sim, ref, "graph replay, step 10")
+        assert_bit_equal(np.array(sim.getPosition()), ref.download()["pos"], f"step {k}: getPosition")
+    compare_state(sim, ref, "step 10")
     kt = sim.kernel_times()
     assert kt.steps == 10 and kt.density > 0 and kt.force > 0 and t.iters == 5
-    # a new state drops the captured graphs (their launches carry the old tile map)
+    # a new state: the launches after it carry the new tile map
     pos, vel = random_state(n, 4)
     sim.upload_state(pos, vel)
     ref.upload(pos, vel)
     for _ in range(3):
         sim.simulate()
         ref.step()
-    compare_state(sim, ref, "graph replay after a re-upload")
+    compare_state(sim, ref, "after a re-upload")
     sim.close()
 
 
-def test_click_after_graph_replays_walks_that_steps_grid(monkeypatch):
-    """SPH_GRAPH=1 and the click impulse: the two read-back slots' graphs were captured with different
-    cell tables (the grid build alternates between two), so after a REPLAY the click has to walk the
-    table of the replayed slot, not the one the last capture left behind.  Clicks after steps 3, 4 and 7
-    (both slots, all replays) against the oracle."""
-    monkeypatch.setenv("SPH_GRAPH", "1")
+def test_clicks_after_steps_on_either_cell_table():
+    """The click impulse walks the cell table of the step that just ran, and the grid build alternates
+    between two tables.  Clicks after steps 3, 4 and 7 (both tables) against the oracle."""
     pos, vel = random_state(30000, 21, lo=1.0, hi=9.0, vmax=0.1)
     sim, ref = make_pair(len(pos), False, pos=pos, vel=vel)
     clicks = {3: (420, 333), 4: (250, 200), 7: (590, 440)}
@@ -556,7 +551,7 @@ def test_click_after_graph_replays_walks_that_steps_grid(monkeypatch):
         ref.step()
         if step in clicks:
             ref.click(*clicks[step])
-        compare_state(sim, ref, f"graph mode, step {step}")
+        compare_state(sim, ref, f"clicks, step {step}")
     sim.close()
 
 

@@ -190,7 +190,7 @@ def _run_ten_steps(render, timed, click):
     return out, host, frame
 
 
-@pytest.mark.parametrize("env", [{}, {"SPH_PIPELINE": "1"}, {"SPH_PIPELINE": "0"}, {"SPH_GRAPH": "1"}])
+@pytest.mark.parametrize("env", [{}, {"SPH_PIPELINE": "1"}, {"SPH_PIPELINE": "0"}])
 @pytest.mark.parametrize("timed", [False, True])
 @pytest.mark.parametrize("click", [False, True])
 def test_rendering_changes_nothing(env, timed, click, monkeypatch):
