@@ -2,6 +2,7 @@
 // It defines the two globals the simulator links against (display.cpp:19-20)
 // and a startVisualization() that steps the simulation without a window.
 // Never linked together with display.cpp (duplicate symbols by design).
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -15,17 +16,20 @@ int2 clickCoords;
 
 extern "C" void glutInit(int *, char **) {}
 
-// SPH_FREE_SHADE=speed|density|pressure: the field (SPH_FIELD_* of sph_c_api.h) that colours the frames;
-// unset: -1, the reference's flat blue.  An unknown name is reported and gives the flat frame.
-static int shade_field() {
-    const char *e = getenv("SPH_FREE_SHADE");
+// speed|density|pressure in the environment variable `var`: the field (SPH_FIELD_* of sph_c_api.h), -1 if it is
+// unset.  An unknown name is reported with what happens instead, and gives -1.
+static int env_field(const char *var, const char *instead) {
+    const char *e = getenv(var);
     if (!e) return -1;
     const char *names[3] = {"speed", "density", "pressure"};
     for (int k = 0; k < 3; ++k)
         if (!strcmp(e, names[k])) return k;
-    fprintf(stderr, "sph: SPH_FREE_SHADE=%s is not speed, density or pressure -- writing flat frames\n", e);
+    fprintf(stderr, "sph: %s=%s is not speed, density or pressure -- %s\n", var, e, instead);
     return -1;
 }
+
+// SPH_FREE_SHADE: the field that colours the frames; unset: the reference's flat blue
+static int shade_field() { return env_field("SPH_FREE_SHADE", "writing flat frames"); }
 
 // SPH_FREE_FRAMES_DIR=<dir>: what the window would have shown after frame f, as <dir>/frame_%04d.ppm (binary P6)
 static bool write_frame(Simulator *simulator, const char *dir, int f, int field) {
@@ -46,6 +50,47 @@ static bool write_frame(Simulator *simulator, const char *dir, int f, int field)
     return (fclose(out) == 0) && ok;
 }
 
+// SPH_FREE_SLICE=speed|density|pressure: beside each frame the cut plane z = 5 of that field, sampled on 400 x 400
+// lattice points over [0, 10)^2 (sph_sample_field), as <dir>/slice_%04d.ppm: row 0 = largest y, coloured with
+// the field frame's quantiser and ramp over the slice's own minimum and maximum.
+static bool write_slice(Simulator *simulator, const char *dir, int f, int field) {
+    const int N = 400;
+    const float origin[3] = {0.f, 0.f, 5.f}, spacing[3] = {10.f / N, 10.f / N, 1.f};
+    const float *v = simulator->sampleField(field, origin, spacing, N, N, 1);
+    if (!v) return false;
+    float lo = v[0], hi = v[0];
+    for (int i = 1; i < N * N; ++i) {
+        lo = v[i] < lo ? v[i] : lo;
+        hi = v[i] > hi ? v[i] : hi;
+    }
+    std::string rgb((size_t)N * N * 3, '\0');
+    for (int r = 0; r < N; ++r)
+        for (int x = 0; x < N; ++x) {
+            const float s = v[(N - 1 - r) * N + x];
+            unsigned q = 0;
+            if (hi != lo) {
+                const float u = ((s - lo) / (hi - lo)) * 256.f;
+                if (u == u) q = (unsigned)(int)fminf(fmaxf(floorf(u), 0.f), 255.f);
+            }
+            unsigned char *p = reinterpret_cast<unsigned char *>(&rgb[((size_t)r * N + x) * 3]);
+            if (q < 64u) p[0] = 0, p[1] = (unsigned char)(4u * q), p[2] = 255;
+            else if (q < 128u) p[0] = 0, p[1] = 255, p[2] = (unsigned char)(255u - 4u * (q - 64u));
+            else if (q < 192u) p[0] = (unsigned char)(4u * (q - 128u)), p[1] = 255, p[2] = 0;
+            else p[0] = 255, p[1] = (unsigned char)(255u - 4u * (q - 192u)), p[2] = 0;
+        }
+    char name[32];
+    snprintf(name, sizeof name, "/slice_%04d.ppm", f);
+    const std::string path = std::string(dir) + name;
+    FILE *out = fopen(path.c_str(), "wb");
+    if (!out) {
+        fprintf(stderr, "sph: cannot write %s\n", path.c_str());
+        return false;
+    }
+    fprintf(out, "P6\n%d %d\n255\n", N, N);
+    const bool ok = fwrite(rgb.data(), 1, rgb.size(), out) == rgb.size();
+    return (fclose(out) == 0) && ok;
+}
+
 void startVisualization(Simulator *simulator) {
     int frames = 100;
     if (const char *e = getenv("SPH_FREE_FRAMES")) frames = atoi(e);
@@ -54,6 +99,7 @@ void startVisualization(Simulator *simulator) {
     int every = 1;
     if (const char *e = getenv("SPH_FREE_FRAME_EVERY")) every = atoi(e) > 0 ? atoi(e) : 1;
     const int field = framesDir ? shade_field() : -1;
+    int slice = framesDir ? env_field("SPH_FREE_SLICE", "writing no slices") : -1;
     fprintf(stderr, "sph: built without GLUT -- running %d frames headless\n", frames);
     for (int f = 0; f < frames; ++f) {
         if (f == frames / 2 && getenv("SPH_FREE_CLICK")) {
@@ -62,6 +108,7 @@ void startVisualization(Simulator *simulator) {
         }
         simulator->simulate();
         if (framesDir && f % every == 0 && !write_frame(simulator, framesDir, f, field)) framesDir = NULL;
+        if (framesDir && slice >= 0 && f % every == 0 && !write_slice(simulator, framesDir, f, slice)) slice = -1;
     }
     const float3 *p = simulator->getPosition();
     if (p && simulator->settings->numParticles > 0)

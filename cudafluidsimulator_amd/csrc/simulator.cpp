@@ -149,6 +149,28 @@ const unsigned char *Simulator::renderField(int field, int *width, int *height) 
     return f;
 }
 
+const float *Simulator::sampleField(int field, const float origin[3], const float spacing[3], int nx, int ny, int nz) {
+    if (multi) {
+        fprintf(stderr, "sph: sampleField: a multi-GPU run (SPH_GPUS > 1) is not sampled\n");
+        return NULL;
+    }
+    if (!impl) return NULL;
+    SphSampleLattice l{};
+    l.struct_size = (int32_t)sizeof l;
+    l.nx = nx, l.ny = ny, l.nz = nz;
+    for (int k = 0; k < 3; ++k) l.origin[k] = origin[k], l.spacing[k] = spacing[k];
+    l.field = field;
+    const int rc = sph_sample_field(impl, &l);
+    if (rc == SPH_ESTATE) { // (SPH_SWEEP=linked, a step split into phases, ...): nothing to sample, nothing broken
+        fprintf(stderr, "sph: sampleField: %s\n", sph_last_error(impl));
+        return NULL;
+    }
+    check(impl, rc, "sph_sample_field");
+    const float *v = sph_sample_host(impl, NULL, NULL, NULL);
+    if (!v) check(impl, SPH_EHIP, "sph_sample_host");
+    return v;
+}
+
 void Simulator::moveParticles(int2 mouse_pos) {
     if (multi) { // multi-GPU: the impulse needs the slabs' grids of a step: it rides on the next simulate()
         mcheck(multi, sph_mgpu_queue_click(multi, mouse_pos.x, mouse_pos.y), "sph_mgpu_queue_click");

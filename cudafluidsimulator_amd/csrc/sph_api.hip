@@ -1,7 +1,7 @@
 // C-ABI implementation (include/sph_c_api.h) of the MI355X SPH step path.
 // Host logic only; the kernels live in sort.hip / grid.hip / sweeps.hip.
 // This unit: settings and initialisers, the handle's life cycle, uploads, downloads and counters; the step is
-// in sph_step.hip, the rest in sph_readback / sph_slab / sph_snapshot / sph_frame.hip (shared: sph_handle.h).
+// in sph_step.hip, the rest in sph_readback / sph_slab / sph_snapshot / sph_frame / sph_sample.hip (shared: sph_handle.h).
 // Compile with -ffp-contract=off (host initialisers must round like the
 // reference's g++ -O3 x86-64 build, Makefile:22-23).
 #include "sph_handle.h"
@@ -423,6 +423,8 @@ void sph_destroy(sph_handle *h) {
                 h->trSync / h->trSteps * 1e6, h->trPost / h->trSteps * 1e6, h->trBetween / (h->trSteps > 1 ? h->trSteps - 1 : 1) * 1e6),
         fprintf(stderr, "  enqueue split: events %.1f | grid %.1f | density %.1f | force %.1f | read-back %.1f\n", h->trPh[0] / h->trSteps * 1e6,
                 h->trPh[1] / h->trSteps * 1e6, h->trPh[2] / h->trSteps * 1e6, h->trPh[3] / h->trSteps * 1e6, h->trPh[4] / h->trSteps * 1e6);
+    if (h->trace && h->sampleTileCalls + h->samplePlainCalls > 0)
+        fprintf(stderr, "sph sample trace: %lld samples by k_sample_tile, %lld by k_sample_plain\n", h->sampleTileCalls, h->samplePlainCalls);
     if (h->compute) (void)hipStreamSynchronize(h->compute);
     if (h->copy) (void)hipStreamSynchronize(h->copy);
     sdma_destroy(h);
@@ -434,13 +436,13 @@ void sph_destroy(sph_handle *h) {
                     (void *)h->force4, (void *)h->pairCounter, (void *)h->pv8, (void *)h->maskPool, (void *)h->maskOff,
                     (void *)h->noneList, (void *)h->hitCount, (void *)h->maskCursor, (void *)h->quiet, (void *)h->quietVref,
                     (void *)h->calm, (void *)h->initPos4, (void *)h->rDepth, (void *)h->rCount, (void *)h->rEdge, (void *)h->rRgb,
-                    (void *)h->rPacked, (void *)h->rRange, (void *)h->boundsDev, (void *)h->partTiles})
+                    (void *)h->rPacked, (void *)h->rRange, (void *)h->boundsDev, (void *)h->partTiles, (void *)h->sampleDev})
         if (p) (void)hipFree(p);
     for (void *p : {(void *)h->hostPos, (void *)h->stage[0], (void *)h->stage[1], (void *)h->pairHost, (void *)h->oobHost,
-                    (void *)h->frameHost, (void *)h->rangeHost, (void *)h->boundsHost})
+                    (void *)h->frameHost, (void *)h->rangeHost, (void *)h->boundsHost, (void *)h->sampleHost})
         if (p) (void)hipHostFree(p);
     for (hipEvent_t e : {h->computeDone[0], h->computeDone[1], h->copyDone[0], h->copyDone[1], h->stageFree[0], h->stageFree[1],
-                         h->frameDrawn, h->frameCopied})
+                         h->frameDrawn, h->frameCopied, h->sampleDone, h->sampleCopied})
         if (e) (void)hipEventDestroy(e);
     for (auto &se : h->ring) {
         for (auto &e : se.e) if (e) (void)hipEventDestroy(e);

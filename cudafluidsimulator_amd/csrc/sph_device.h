@@ -220,3 +220,18 @@ int sph_prepare_render_field();
 void sph_launch_render_field(const RenderParams &R, const float4 *pos4, const float4 *vel4, int n, bool plain, int field,
                             bool autoRange, float lo, float hi, unsigned long long *packed, uint32_t *depth, uint32_t *count,
                             const uint32_t *edge, uint32_t *range, uint32_t *rgb, hipStream_t s);
+
+// ---- the field sample (sample.hip; defined in DESIGN.md section 10b) ----
+struct SampleArgs {
+    int nx, ny, nz;          // lattice points per axis; point (ix, iy, iz) -> out[(iz ny + iy) nx + ix]
+    float ox, oy, oz;        // origin
+    float sx, sy, sz;        // spacing
+    int field;               // SPH_FIELD_*
+    const float4 *pos;       // sorted row j: pos[j stride] = (x, y, z, id) and vel[j stride] = (vx, vy, vz, rho) --
+    const float4 *vel;       // the sorted pos4 / vel4 streams (stride 1) or the interleaved records (pv8, pv8 + 1; stride 2)
+    int stride;
+    const int2 *cellRange;   // {start, end} per flattened cell (SPH_KEY_FLATTENED only)
+    int n;                   // rows of the stream
+};
+// one value per lattice point into out[0, nx ny nz); plain = the one-thread-per-point check path
+void sph_launch_sample(const DevParams &P, const SampleArgs &A, bool plain, float *out, hipStream_t s);

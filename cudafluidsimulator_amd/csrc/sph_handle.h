@@ -1,5 +1,5 @@
 // The handle behind include/sph_c_api.h and the few helpers its host translation units share (sph_api.hip,
-// sph_step.hip, sph_readback.hip, sph_slab.hip, sph_snapshot.hip, sph_frame.hip).  Host code only.
+// sph_step.hip, sph_readback.hip, sph_slab.hip, sph_snapshot.hip, sph_frame.hip, sph_sample.hip).  Host code only.
 #pragma once
 
 #include "sph_c_api.h"
@@ -151,6 +151,19 @@ struct sph_handle {
     unsigned long long *rPacked = nullptr;
     uint32_t *rRange = nullptr, *rangeHost = nullptr;
     bool fieldFrame = false;         // the last render was a field frame
+
+    // ---- sph_sample.hip ----
+    // The field sample (sample.hip): one float per lattice point on the device and in pinned memory, both grown
+    // on demand by sph_sample_field.
+    float *sampleDev = nullptr, *sampleHost = nullptr;
+    size_t sampleCap = 0;            // floats either buffer holds
+    int sampleDim[3] = {0, 0, 0};    // nx, ny, nz of the last sample
+    hipEvent_t sampleDone = nullptr, sampleCopied = nullptr;
+    bool samplePending = false;      // a copy of the values is queued on the copy stream
+    bool sampleValid = false;
+    double sampleSeconds = 0;        // the sampling kernel, from HIP events (PairEvent ring)
+    long long sampleCount = 0;
+    long long sampleTileCalls = 0, samplePlainCalls = 0; // which kernel ran (SPH_STEP_TRACE=1: printed by sph_destroy)
 };
 
 #define HIPCHK(h, call)                                                               \
@@ -189,6 +202,7 @@ int launch_density(sph_handle *h, SweepArgs &A, hipStream_t stream);
 int pair_begin(sph_handle *h, double *target, PairEvent **out, hipStream_t stream = nullptr);
 int resolve_pair(sph_handle *h, PairEvent &pe);
 int begin_step_events(sph_handle *h);
+int build_grid_ahead(sph_handle *h);
 int resolve_events(sph_handle *h, StepEvents &se);
 void drop_grid_ahead(sph_handle *h);
 // sph_readback.hip

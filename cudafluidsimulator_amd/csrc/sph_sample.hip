@@ -1,0 +1,144 @@
+// The field sample: sph_sample_field and what reads its results (kernels: sample.hip).
+#include "sph_handle.h"
+
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+
+using namespace sph_host;
+
+namespace {
+
+// (re)allocate the value buffers for `points` floats
+int sample_reserve(sph_handle *h, size_t points) {
+    if (!h->sampleDone) HIPCHK(h, hipEventCreateWithFlags(&h->sampleDone, hipEventDisableTiming));
+    if (!h->sampleCopied) HIPCHK(h, hipEventCreateWithFlags(&h->sampleCopied, hipEventDisableTiming));
+    if (points <= h->sampleCap) return SPH_OK;
+    // the old buffers may still be read by a queued copy
+    HIPCHK(h, hipStreamSynchronize(h->compute));
+    HIPCHK(h, hipStreamSynchronize(h->copy));
+    h->samplePending = false;
+    h->sampleValid = false;
+    if (h->sampleDev) (void)hipFree(h->sampleDev);
+    if (h->sampleHost) (void)hipHostFree(h->sampleHost);
+    h->sampleDev = h->sampleHost = nullptr;
+    h->sampleCap = 0;
+    HIPCHK(h, hipMalloc(&h->sampleDev, points * sizeof(float)));
+    HIPCHK(h, hipHostMalloc(&h->sampleHost, points * sizeof(float), hipHostMallocDefault));
+    h->sampleCap = points;
+    return SPH_OK;
+}
+
+const char *bad_lattice(const SphSampleLattice &L) {
+    for (int d : {L.nx, L.ny, L.nz})
+        if (d < 1 || d > 4096) return "lattice dimensions must be 1..4096";
+    if ((long long)L.nx * L.ny * L.nz > (1ll << 24)) return "lattice holds more than 1 << 24 points";
+    for (float o : L.origin)
+        if (!std::isfinite(o)) return "origin must be finite";
+    for (float s : L.spacing)
+        if (!std::isfinite(s) || !(s > 0.f)) return "spacing must be finite and > 0";
+    if (L.field != SPH_FIELD_SPEED && L.field != SPH_FIELD_DENSITY && L.field != SPH_FIELD_PRESSURE) return "unknown field";
+    return nullptr;
+}
+
+} // namespace
+
+extern "C" {
+
+int sph_sample_field(sph_handle *h, const SphSampleLattice *lat) {
+    if (!h) return SPH_EINVAL;
+    SPH_ON_DEVICE(h);
+    if (h->external) return reject_slab_mode(h, ": multi-GPU runs are not sampled");
+    if (!h->ready) return fail(h, SPH_ESTATE, "setup()/upload_state() must come first");
+    if (h->opt.sweep == SPH_SWEEP_LINKED) return fail(h, SPH_ESTATE, "the field sample needs a cell table: not available with SPH_SWEEP_LINKED");
+    if (h->P.morton) return fail(h, SPH_ESTATE, "the field sample walks rows of cells as runs of the stream: not available with SPH_KEY_MORTON");
+    if (h->phase != 0 && h->phase != 1) return fail(h, SPH_ESTATE, "a step split into phases is still open");
+    if (!lat || lat->struct_size <= 0) return fail(h, SPH_EINVAL, "SphSampleLattice.struct_size is not set");
+    SphSampleLattice L{};
+    const size_t sz = (size_t)lat->struct_size;
+    memcpy(&L, lat, sz < sizeof L ? sz : sizeof L);
+    if (const char *bad = bad_lattice(L)) return fail(h, SPH_EINVAL, bad);
+    const size_t points = (size_t)L.nx * L.ny * L.nz;
+    int rc = sample_reserve(h, points);
+    if (rc) return rc;
+    // A grid of the state the handle holds NOW.  Phase 1: it exists (sph_phase_grid, or built ahead by a timed
+    // step).  Phase 0: the table of the last step is the pre-integration one; the next step's grid is built
+    // here, ahead, and that step consumes it.
+    if (h->phase == 0 && h->n > 0 && (rc = build_grid_ahead(h))) return rc;
+    bool plain = false;
+    if (const char *e = getenv("SPH_SAMPLE_PLAIN")) plain = atoi(e) != 0;
+    if (h->samplePending) { // the previous sample's copy still reads the device buffer
+        HIPCHK(h, hipStreamWaitEvent(h->compute, h->sampleCopied, 0));
+        h->samplePending = false;
+    }
+    SampleArgs A{};
+    A.nx = L.nx, A.ny = L.ny, A.nz = L.nz;
+    A.ox = L.origin[0], A.oy = L.origin[1], A.oz = L.origin[2];
+    A.sx = L.spacing[0], A.sy = L.spacing[1], A.sz = L.spacing[2];
+    A.field = L.field;
+    A.n = h->n;
+    if (h->n > 0) {
+        A.cellRange = h->cellRange;
+        if (h->opt.sweep == SPH_SWEEP_LIST && h->pv8) { // the gather left no sorted vel4 in this mode
+            A.pos = h->pv8;
+            A.vel = h->pv8 + 1;
+            A.stride = 2;
+        } else {
+            A.pos = h->pos4[h->sorted];
+            A.vel = h->vel4[h->sorted];
+            A.stride = 1;
+        }
+    }
+    PairEvent *pe = nullptr;
+    if ((rc = pair_begin(h, &h->sampleSeconds, &pe))) return rc;
+    sph_launch_sample(h->P, A, plain, h->sampleDev, h->compute);
+    HIPCHK(h, hipEventRecord(pe->b, h->compute));
+    HIPCHK(h, hipGetLastError());
+    h->sampleCount += 1;
+    (plain ? h->samplePlainCalls : h->sampleTileCalls) += 1;
+    h->sampleValid = false; // (until the copy is queued: the pinned buffer still holds the previous sample)
+    // the values leave on the copy stream, behind an event, like the frame does
+    HIPCHK(h, hipEventRecord(h->sampleDone, h->compute));
+    HIPCHK(h, hipStreamWaitEvent(h->copy, h->sampleDone, 0));
+    HIPCHK(h, hipMemcpyAsync(h->sampleHost, h->sampleDev, points * sizeof(float), hipMemcpyDeviceToHost, h->copy));
+    HIPCHK(h, hipEventRecord(h->sampleCopied, h->copy));
+    h->samplePending = true;
+    h->sampleDim[0] = L.nx, h->sampleDim[1] = L.ny, h->sampleDim[2] = L.nz;
+    h->sampleValid = true;
+    return SPH_OK;
+}
+
+const float *sph_sample_host(sph_handle *h, int *nx, int *ny, int *nz) {
+    if (!h) return nullptr;
+    if (!h->sampleValid) {
+        h->err = "sph_sample_field must come first";
+        return nullptr;
+    }
+    if (h->samplePending && hipEventSynchronize(h->sampleCopied) != hipSuccess) {
+        h->err = "sample copy failed";
+        return nullptr;
+    }
+    if (nx) *nx = h->sampleDim[0];
+    if (ny) *ny = h->sampleDim[1];
+    if (nz) *nz = h->sampleDim[2];
+    return h->sampleHost;
+}
+
+int sph_get_sample_time(sph_handle *h, double *seconds, int64_t *samples, int reset) {
+    if (!h) return SPH_EINVAL;
+    SPH_ON_DEVICE(h);
+    for (auto &pe : h->pairs)
+        if (pe.used && pe.target == &h->sampleSeconds) {
+            int rc = resolve_pair(h, pe);
+            if (rc) return rc;
+        }
+    if (seconds) *seconds = h->sampleSeconds;
+    if (samples) *samples = h->sampleCount;
+    if (reset) {
+        h->sampleSeconds = 0;
+        h->sampleCount = 0;
+    }
+    return SPH_OK;
+}
+
+} // extern "C"

@@ -159,6 +159,19 @@ int begin_step_events(sph_handle *h) {
     return SPH_OK;
 }
 
+// Queue the grid build of the state the handle holds now, for the step that comes next (sph_handle::gridAhead):
+// that step finds phase 1 and goes on with this build's events.
+int build_grid_ahead(sph_handle *h) {
+    int rc;
+    if ((rc = begin_step_events(h))) return rc;
+    StepEvents *nextEv = h->curEv;
+    if ((rc = sph_phase_grid(h))) return rc;
+    h->curEv = nullptr;
+    h->aheadEv = nextEv;
+    h->gridAhead = true;
+    return SPH_OK;
+}
+
 int resolve_pair(sph_handle *h, PairEvent &pe) {
     if (!pe.used) return SPH_OK;
     float ms = 0.f;
@@ -259,7 +272,11 @@ int sph_phase_grid(sph_handle *h) {
     // kernelResetGrid (simulator.cu:321-326,492-495) and the cell hash are both part of the
     // first sort pass: no launch of their own
     if (ev) HIPCHK(h, hipEventRecord(ev->e[1], s));
-    h->cellCur ^= 1; // the previous build's table stays intact (a click after a step pipelined ahead needs it)
+    // The table of the last completed step stays intact: a click after a grid built ahead walks it.  Normally that
+    // is the previous build's table and the build takes the other one; after a build that was dropped (click after
+    // a grid built ahead) it IS the other one, and the dropped build's table is written again.
+    h->cellCur ^= 1;
+    if (h->clickValid && h->cellTable[h->cellCur] == h->clickTable) h->cellCur ^= 1;
     h->cellRange = h->cellTable[h->cellCur];
     h->ws.velSample = (h->quiet && h->useQuiet) ? h->vel4[c] : nullptr; // the zero-pair filter's reference velocity
     h->ws.vrefOut = h->quietVref;
@@ -409,12 +426,7 @@ int sph_step(sph_handle *h, SphTimes *times) {
         const auto trA = std::chrono::steady_clock::now();
         if (h->aheadEnabled && h->opt.sweep != SPH_SWEEP_LINKED && h->n > 0) {
             // queue the next step's grid build before waiting for this one (see sph_handle::gridAhead)
-            if ((rc = begin_step_events(h))) return rc;
-            StepEvents *nextEv = h->curEv;
-            if ((rc = sph_phase_grid(h))) return rc;
-            h->curEv = nullptr;
-            h->aheadEv = nextEv;
-            h->gridAhead = true;
+            if ((rc = build_grid_ahead(h))) return rc;
             HIPCHK(h, hipEventSynchronize(ev->e[5])); // this step's force sweep (not the grid queued behind it)
         } else {
             HIPCHK(h, hipStreamSynchronize(h->compute));

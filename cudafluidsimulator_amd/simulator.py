@@ -229,6 +229,31 @@ class Simulator:
                     "sph_get_render_time")
         return sec.value, fr.value
 
+    # -- the field sample: the SPH-interpolated field on a regular lattice (sph_sample_field) --
+    def sample_field(self, field="density", origin=(0.0, 0.0, 0.0), spacing=(0.1, 0.1, 0.1), shape=(1, 1, 1)):
+        """`field` ("density", "speed", "pressure") of the current state at the lattice points
+        origin + (ix, iy, iz) * spacing -- origin and spacing as (x, y, z), spacing also as one number --
+        as an np.float32 array of its own of `shape` = (nz, ny, nx).  Points outside the grid give 0."""
+        nz, ny, nx = (int(d) for d in shape)
+        lat = _lib.SphSampleLattice()
+        lat.struct_size = C.sizeof(_lib.SphSampleLattice)
+        lat.nx, lat.ny, lat.nz = nx, ny, nz
+        lat.origin[:] = [float(o) for o in origin]
+        lat.spacing[:] = [float(s) for s in (spacing if np.ndim(spacing) else (spacing,) * 3)]
+        lat.field = _lib.FIELDS[field] if isinstance(field, str) else int(field)
+        self._check(self._L.sph_sample_field(self._h, C.byref(lat)), "sph_sample_field")
+        p = self._L.sph_sample_host(self._h, None, None, None)
+        if not p:
+            raise SphError("sph_sample_host failed: " + self._L.sph_last_error(self._h).decode())
+        return np.array(np.ctypeslib.as_array(p, shape=(nz, ny, nx)), copy=True)
+
+    def sample_time(self, reset=False):
+        """(seconds, samples): GPU time of the sampling kernel summed over `samples` calls."""
+        sec, cnt = C.c_double(0), C.c_int64(0)
+        self._check(self._L.sph_get_sample_time(self._h, C.byref(sec), C.byref(cnt), 1 if reset else 0),
+                    "sph_get_sample_time")
+        return sec.value, cnt.value
+
     def phase(self, name):
         self._check(getattr(self._L, "sph_phase_" + name)(self._h), "sph_phase_" + name)
 

@@ -389,6 +389,45 @@ int sph_download_field_buffer(sph_handle *h, uint32_t *value_bits);
  * SPH_ESTATE if the last render was not a field frame. */
 int sph_field_range(sph_handle *h, float *lo, float *hi);
 
+/* ---- the field sample: SPH-interpolated density, speed or pressure on a regular lattice ----
+ * Additive to version 3: test for SPH_HAS_FIELD_SAMPLE.  Defined to the bit in DESIGN.md section 10b ("The field
+ * sample"); all fp32, every operation rounded on its own, in both math modes.  Point (ix, iy, iz) lies at
+ * origin + (float)i * spacing per axis and lands at index (iz ny + iy) nx + ix.  Its cell is (int)(p / h) per axis;
+ * a point with !(p >= 0) or a cell >= numCellsPerDim on any axis is outside and samples +0.  The walk is the density
+ * sweep's: the 27 cells dz, dy, dx = -1..1 in that nesting, each cell's rows in the order of the grid's sorted
+ * stream; candidate j with d2 = (dx dx + dy dy) + dz dz <= h h weighs m = MASS (((d_kernel_coeff diff) diff) diff),
+ * diff = h h - d2.  DENSITY: the sum of m from 0 (no EPS_F clamp: empty space is 0) -- what kernelUpdatePressureAndDensity
+ * forms for a particle at that point.  SPEED, PRESSURE: sum(m a_j) / sum(m), 0 where sum(m) is not > 0, a_j the field
+ * frame's scalar of row j (from the values sph_download_state returns). */
+#define SPH_HAS_FIELD_SAMPLE 1
+typedef struct SphSampleLattice {
+    int32_t struct_size;     /* = sizeof(SphSampleLattice) */
+    int32_t nx, ny, nz;      /* each 1..4096, nx*ny*nz <= 1<<24 */
+    float origin[3];
+    float spacing[3];        /* finite, > 0 */
+    int32_t field;           /* SPH_FIELD_* */
+} SphSampleLattice;
+/* Samples the state the handle holds NOW and queues the copy of the values to pinned host memory; does not block.
+ * The walk needs a grid of that state.  With a grid phase done (sph_phase_grid, or the grid a timed step built
+ * ahead) that grid is used as it is.  Otherwise the grid is built here exactly as a timed sph_step builds the next
+ * step's grid ahead: the next step, timed or not, consumes it, and a click, upload or load drops it; no result of
+ * any step changes.  sph_download_grid after the call returns the grid that was walked.  SPH_ESTATE: before any
+ * state, inside a step split into phases (after sph_phase_density or sph_phase_force), for SPH_FLAG_EXTERNAL_STATE
+ * handles, with SPH_SWEEP_LINKED (no cell table) and with SPH_KEY_MORTON (a row of cells is not one run of the
+ * stream).  SPH_EINVAL: struct_size not set, dimensions out of range, a non-finite origin, a spacing that is not
+ * finite and > 0, an unknown field.  No particles: all zeros.  Results only: the sampling kernel runs on the compute
+ * stream behind the grid build whose events the next step takes over, so that step's SphKernelTimes.density, and
+ * SphTimes.sphUpdate of a timed step, include the GPU time of every sample taken before it (as they include a frame
+ * rendered behind a grid built ahead); sph_get_sample_time says how much that was.  SPH_SAMPLE_PLAIN=1 in the environment selects the
+ * check path (one thread per point, every candidate loaded from global memory; identical values). */
+int sph_sample_field(sph_handle *h, const SphSampleLattice *lat);
+/* nx*ny*nz floats of the last sph_sample_field, owned by the handle, valid until the next sample.  Blocks until
+ * the copy has landed.  NULL before the first sample. */
+const float *sph_sample_host(sph_handle *h, int *nx, int *ny, int *nz);
+/* GPU time of the sampling kernel alone (HIP events on the compute stream; not the grid build, which belongs to
+ * the step that consumes it), summed over `samples` calls. */
+int sph_get_sample_time(sph_handle *h, double *seconds, int64_t *samples, int reset);
+
 const char *sph_build_info(void);
 
 #ifdef __cplusplus
