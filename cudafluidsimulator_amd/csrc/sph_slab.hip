@@ -1,4 +1,4 @@
-// The sph_slab_* entry points: one z-slab of a multi-GPU run on caller-owned buffers (driver: mgpu.cpp).
+// The sph_slab_* entry points: one z-slab of a multi-GPU run on caller-owned buffers (driver: mgpu_step.cpp).
 #include "sph_handle.h"
 
 using namespace sph_host;

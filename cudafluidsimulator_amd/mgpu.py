@@ -21,7 +21,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 MAX_LOCAL = 8
 TRANSPORTS = {"loopback": 0, "rccl": 1, "rccl_self": 2, "mailbox": 3, "streams": 4}
 
-# every symbol include/sph_mgpu.h declares (checked by tests/test_abi.py)
+# every symbol include/sph_mgpu.h declares (checked by tests/test_mgpu.py)
 EXPORTED_SYMBOLS = [
     "sph_mgpu_unique_id", "sph_mgpu_create", "sph_mgpu_destroy", "sph_mgpu_setup",
     "sph_mgpu_upload_state", "sph_mgpu_step", "sph_mgpu_step_phase", "sph_mgpu_positions_host",

@@ -4,7 +4,7 @@
  * MI355X, halo layers exchanged with RCCL send/recv over xGMI.
  *
  * No reference counterpart: the reference is single-GPU (simulator.cu:462-546 is the
- * step being distributed).  Host code is C++ (csrc/mgpu.cpp): one host
+ * step being distributed).  Host code is C++ (csrc/mgpu_*.cpp): one host
  * thread drives every local slab; the data path never goes through Python.  Two ways
  * to run it:
  *   - one process drives all GPUs of the node (`./sph` with SPH_GPUS=N):

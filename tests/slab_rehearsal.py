@@ -1,5 +1,5 @@
 """REHEARSAL ONLY (test infrastructure, lives under tests/): the z-slab protocol of
-cudafluidsimulator_amd/csrc/mgpu.cpp restated over torch.distributed so that it can run on
+cudafluidsimulator_amd/csrc/mgpu_step.cpp restated over torch.distributed so that it can run on
 CPU ranks (gloo, world 2/3) against the oracle backend.  The product's multi-GPU driver is
 the C++ library libsph_mgpu.so (include/sph_mgpu.h); nothing in the package or bench.py
 imports this file.

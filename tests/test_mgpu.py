@@ -250,19 +250,22 @@ def test_click_impulse_in_multi_gpu_mode(world, transport, recut):
 
 
 @pytest.mark.gpu
-def test_one_rank_failing_stops_its_neighbours_with_an_error_not_a_hang():
+@pytest.mark.parametrize("sweep", ["list", "lds"])
+def test_one_rank_failing_stops_its_neighbours_with_an_error_not_a_hang(sweep):
     """One process per GPU (here: one driver object per rank, mailbox transport, stepped phase by
     phase): a particle that crosses a whole slab in one step makes ONE rank's check fail.  That
     rank finishes the step's message rounds, says farewell (an exchange A whose header carries
     status = 1) and returns the error; its neighbours read the status in their next step, do the
     same and return an error too -- nobody is left waiting for a message (the mailbox would report
-    "the sending rank has not run this phase yet", RCCL would hang).  A fresh state then runs."""
+    "the sending rank has not run this phase yet", RCCL would hang).  A fresh state then runs.
+    Both sweeps: the exchange B of a failed step ships records under `list`, vel4 rows otherwise."""
     n, world = 60000, 3
     pos, vel = moving_state(n, 21, vz=3.0)
     k = int(np.argmin(pos[:, 2]))
     vel[k] = (0.0, 0.0, 650.0)          # 65 cells per step: from slab 0 across slab 1 into slab 2
     settings = sph.default_settings(n, False)
-    ranks = [M.MultiGpuSimulator(settings, world=world, rank=r, devices=[0], transport="mailbox") for r in range(world)]
+    ranks = [M.MultiGpuSimulator(settings, world=world, rank=r, devices=[0], transport="mailbox", sweep=sweep)
+             for r in range(world)]
     for mg in ranks:
         mg.upload_state(pos, vel)
     died = {}
@@ -288,7 +291,7 @@ def test_one_rank_failing_stops_its_neighbours_with_an_error_not_a_hang():
         ranks[1].step_phase(1)
     # a fresh state: the same objects run again, bit-equal to the single domain
     pos2, vel2 = moving_state(n, 22, vz=8.0)
-    want, _ = single_domain(settings, pos2, vel2, 3)
+    want, _ = single_domain(settings, pos2, vel2, 3, sweep=sweep)
     for mg in ranks:
         mg.upload_state(pos2, vel2)
     for _ in range(3):
