@@ -17,7 +17,7 @@ namespace {
 constexpr int kSplatThreads = 256;
 constexpr int kSplatPerThread = 4;
 constexpr int kSplatBlock = kSplatThreads * kSplatPerThread; // particles per workgroup
-constexpr int kTilePixels = 8192;                            // 2 x 32 KB of LDS
+constexpr int kTilePixels = 8192;                            // a count and a minimum each: 64 KB (flat) or 96 KB (field) of LDS
 
 struct Pixel {
     int px, py;
@@ -39,42 +39,91 @@ __device__ __forceinline__ Pixel project(float x, float y, float z, const Render
     return p;
 }
 
-__global__ __launch_bounds__(256) void k_render_clear(uint32_t *__restrict__ depth, uint32_t *__restrict__ count, int npix) {
+// ---- the splat, once for two payloads ----
+// The flat frame keeps the minimum of the depth bits per pixel.  The field frame ("The field
+// frame") keeps the minimum of (bits(w) << 32) | bits(s), s >= +0 the scalar of the particle's vel4 row (xyz =
+// velocity, w = density): the high word IS the depth buffer of the flat frame, the low word the value of the nearest
+// particle (the smallest among several at that depth).  A payload gives the per-pixel word, its "empty", the word of
+// particle i and the global buffer the minima go to.
+
+__device__ __forceinline__ uint32_t field_bits(const float4 v, int field) {
+    float s;
+    if (field == SPH_FIELD_SPEED) s = sqrtf((v.x * v.x + v.y * v.y) + v.z * v.z);
+    else if (field == SPH_FIELD_DENSITY) s = v.w;
+    else s = fmaxf(0.f, SPH_GAS_CONSTANT * (v.w - SPH_REST_DENSITY)); // as sph_download_state
+    return __float_as_uint(s);
+}
+
+__device__ __forceinline__ unsigned long long field_word(uint32_t wbits, uint32_t sbits) {
+    return ((unsigned long long)wbits << 32) | sbits;
+}
+
+struct FlatPayload {
+    using Word = uint32_t;
+    static constexpr Word kEmpty = 0xFFFFFFFFu;
+    static constexpr bool kRange = false;
+    Word *least; // depth
+    __device__ __forceinline__ Word word(uint32_t wbits, int) const { return wbits; }
+};
+
+struct FieldPayload {
+    using Word = unsigned long long;
+    static constexpr Word kEmpty = 0xFFFFFFFFFFFFFFFFull;
+    static constexpr bool kRange = true;
+    Word *least; // packed
+    const float4 *vel4;
+    int field;
+    __device__ __forceinline__ Word word(uint32_t wbits, int i) const { return field_word(wbits, field_bits(vel4[i], field)); }
+};
+
+// range[0] / range[1] (field frame only): the bits of lo / hi compose will read -- the fixed range, or the identities of the reduction
+template <class Pay>
+__global__ __launch_bounds__(256) void k_render_clear(typename Pay::Word *__restrict__ least, uint32_t *__restrict__ count, int npix,
+                                                      uint32_t *__restrict__ range, uint32_t lo, uint32_t hi) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < npix) {
-        depth[i] = 0xFFFFFFFFu;
+        least[i] = Pay::kEmpty;
         count[i] = 0u;
+    }
+    if (Pay::kRange && i == 0) {
+        range[0] = lo;
+        range[1] = hi;
     }
 }
 
+// one particle's hits: every pixel of its square, clipped to the viewport, counts one more and takes the minimum
+// with `word`.  Pixel (x, y) is entry (y - y0) * pitch + (x - x0) of both targets: the global buffers (0, 0, width)
+// or a tile over the rectangle that starts at (x0, y0) and is `pitch` wide.
+template <class Word>
+__device__ __forceinline__ void splat_hits(const RenderParams &R, int px, int py, Word word, uint32_t *count, Word *least,
+                                           int x0, int y0, int pitch) {
+    const int r = R.radius;
+    for (int y = max(py - r, 0); y <= min(py + r, R.height - 1); ++y)
+        for (int x = max(px - r, 0); x <= min(px + r, R.width - 1); ++x) {
+            const int e = (y - y0) * pitch + (x - x0);
+            atomicAdd(&count[e], 1u);
+            atomicMin(&least[e], word);
+        }
+}
+
 // the check path (SPH_RENDER_PLAIN=1): one thread per particle, one atomic per hit and buffer
-__global__ __launch_bounds__(256) void k_splat_plain(const float4 *__restrict__ pos4, int n, RenderParams R,
-                                                     uint32_t *__restrict__ depth, uint32_t *__restrict__ count) {
+template <class Pay>
+__global__ __launch_bounds__(256) void k_splat_plain(const float4 *__restrict__ pos4, int n, RenderParams R, Pay pay,
+                                                     uint32_t *__restrict__ count) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const float4 p = pos4[i];
     const Pixel q = project(p.x, p.y, p.z, R);
-    const int r = R.radius;
-    for (int y = max(q.py - r, 0); y <= min(q.py + r, R.height - 1); ++y)
-        for (int x = max(q.px - r, 0); x <= min(q.px + r, R.width - 1); ++x) {
-            atomicAdd(&count[y * R.width + x], 1u);
-            atomicMin(&depth[y * R.width + x], q.wbits);
-        }
+    splat_hits(R, q.px, q.py, pay.word(q.wbits, i), count, pay.least, 0, 0, R.width);
 }
 
-__device__ __forceinline__ int wave_min(int v) {
-    for (int m = 32; m > 0; m >>= 1) v = min(v, __shfl_xor(v, m, 64));
-    return v;
-}
-__device__ __forceinline__ int wave_max(int v) {
-    for (int m = 32; m > 0; m >>= 1) v = max(v, __shfl_xor(v, m, 64));
-    return v;
-}
-
-__global__ __launch_bounds__(kSplatThreads) void k_splat_tile(const float4 *__restrict__ pos4, int n, RenderParams R,
-                                                              uint32_t *__restrict__ depth, uint32_t *__restrict__ count) {
+template <class Pay>
+__global__ __launch_bounds__(kSplatThreads) void k_splat_tile(const float4 *__restrict__ pos4, int n, RenderParams R, Pay pay,
+                                                              uint32_t *__restrict__ count) {
+    using Word = typename Pay::Word;
+    constexpr int kNowhere = -0x40000000; // px of no particle, or of one whose square misses the viewport: covers nothing
+    __shared__ Word tLeast[kTilePixels];
     __shared__ uint32_t tCount[kTilePixels];
-    __shared__ uint32_t tDepth[kTilePixels];
     __shared__ int box[4]; // min x, min y, max x, max y over the workgroup's particle centres
     const int t = threadIdx.x;
     const int base = blockIdx.x * kSplatBlock;
@@ -82,31 +131,33 @@ __global__ __launch_bounds__(kSplatThreads) void k_splat_tile(const float4 *__re
     if (t < 2) box[t] = 0x7fffffff;
     else if (t < 4) box[t] = -0x7fffffff;
 
-    Pixel q[kSplatPerThread];
+    int qx[kSplatPerThread], qy[kSplatPerThread];
+    Word qw[kSplatPerThread];
     int lox = 0x7fffffff, loy = 0x7fffffff, hix = -0x7fffffff, hiy = -0x7fffffff;
 #pragma unroll
     for (int k = 0; k < kSplatPerThread; ++k) {
         const int i = base + k * kSplatThreads + t;
-        q[k].px = q[k].py = -0x40000000; // (no particle: covers nothing)
-        q[k].wbits = 0xFFFFFFFFu;
+        qx[k] = qy[k] = kNowhere;
+        qw[k] = Pay::kEmpty;
         if (i < n) {
             const float4 p = pos4[i];
-            q[k] = project(p.x, p.y, p.z, R);
+            const Pixel q = project(p.x, p.y, p.z, R);
             // a centre whose square misses the viewport draws nothing and must not stretch the rectangle
-            if (q[k].px + r >= 0 && q[k].px - r < R.width && q[k].py + r >= 0 && q[k].py - r < R.height) {
-                lox = min(lox, q[k].px);
-                hix = max(hix, q[k].px);
-                loy = min(loy, q[k].py);
-                hiy = max(hiy, q[k].py);
-            } else {
-                q[k].px = q[k].py = -0x40000000;
+            if (q.px + r >= 0 && q.px - r < R.width && q.py + r >= 0 && q.py - r < R.height) {
+                qx[k] = q.px;
+                qy[k] = q.py;
+                qw[k] = pay.word(q.wbits, i);
+                lox = min(lox, q.px);
+                hix = max(hix, q.px);
+                loy = min(loy, q.py);
+                hiy = max(hiy, q.py);
             }
         }
     }
-    lox = wave_min(lox);
-    loy = wave_min(loy);
-    hix = wave_max(hix);
-    hiy = wave_max(hiy);
+    lox = wave_min_i32(lox);
+    loy = wave_min_i32(loy);
+    hix = wave_max_i32(hix);
+    hiy = wave_max_i32(hiy);
     __syncthreads();
     if ((t & 63) == 0) {
         atomicMin(&box[0], lox);
@@ -123,34 +174,21 @@ __global__ __launch_bounds__(kSplatThreads) void k_splat_tile(const float4 *__re
 
     if (area > kTilePixels) { // (uniform) the rectangle does not fit: per-hit global atomics
 #pragma unroll
-        for (int k = 0; k < kSplatPerThread; ++k) {
-            if (q[k].px == -0x40000000) continue;
-            for (int y = max(q[k].py - r, 0); y <= min(q[k].py + r, R.height - 1); ++y)
-                for (int x = max(q[k].px - r, 0); x <= min(q[k].px + r, R.width - 1); ++x) {
-                    atomicAdd(&count[y * R.width + x], 1u);
-                    atomicMin(&depth[y * R.width + x], q[k].wbits);
-                }
-        }
+        for (int k = 0; k < kSplatPerThread; ++k)
+            if (qx[k] != kNowhere) splat_hits(R, qx[k], qy[k], qw[k], count, pay.least, 0, 0, R.width);
         return;
     }
 
     const int tile = (int)area;
     for (int e = t; e < tile; e += kSplatThreads) {
         tCount[e] = 0u;
-        tDepth[e] = 0xFFFFFFFFu;
+        tLeast[e] = Pay::kEmpty;
     }
     __syncthreads();
+    // (every pixel of a clipped square lies inside [x0, x1] x [y0, y1] by construction)
 #pragma unroll
-    for (int k = 0; k < kSplatPerThread; ++k) {
-        if (q[k].px == -0x40000000) continue;
-        // (every pixel of the clipped square lies inside [x0, x1] x [y0, y1] by construction)
-        for (int y = max(q[k].py - r, 0); y <= min(q[k].py + r, R.height - 1); ++y)
-            for (int x = max(q[k].px - r, 0); x <= min(q[k].px + r, R.width - 1); ++x) {
-                const int e = (y - y0) * bw + (x - x0);
-                atomicAdd(&tCount[e], 1u);
-                atomicMin(&tDepth[e], q[k].wbits);
-            }
-    }
+    for (int k = 0; k < kSplatPerThread; ++k)
+        if (qx[k] != kNowhere) splat_hits(R, qx[k], qy[k], qw[k], tCount, tLeast, x0, y0, bw);
     __syncthreads();
     for (int e = t; e < tile; e += kSplatThreads) {
         const uint32_t c = tCount[e];
@@ -158,10 +196,10 @@ __global__ __launch_bounds__(kSplatThreads) void k_splat_tile(const float4 *__re
         const int ey = e / bw;
         const int g = (y0 + ey) * R.width + x0 + (e - ey * bw);
         atomicAdd(&count[g], c);
-        // Depth only ever decreases during the splat, so whatever value a plain load returns (however
-        // stale) is >= the final one: if it is already <= ours, ours cannot change the result.
-        const uint32_t d = tDepth[e];
-        if (depth[g] > d) atomicMin(&depth[g], d);
+        // The word only ever decreases during the splat, so whatever value a plain (aligned, single) load returns,
+        // however stale, is >= the final one: if it is already <= ours, ours cannot change the result.
+        const Word m = tLeast[e];
+        if (pay.least[g] > m) atomicMin(&pay.least[g], m);
     }
 }
 
@@ -191,58 +229,6 @@ __device__ __forceinline__ uint32_t pixel_rgb(uint32_t d, uint32_t c, uint32_t e
     return (32u * L) | ((32u * L) << 8) | 0xFF0000u;
 }
 
-// four pixels = 12 bytes = three dwords per thread; rgb is padded to a multiple of four pixels
-__global__ __launch_bounds__(256) void k_render_compose(const uint32_t *__restrict__ depth, const uint32_t *__restrict__ count,
-                                                        const uint32_t *__restrict__ edge, int npix, int shade,
-                                                        uint32_t *__restrict__ rgb) {
-    const int g = blockIdx.x * 256 + threadIdx.x;
-    const int p0 = g * 4;
-    if (p0 >= npix) return;
-    uint32_t c[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) c[k] = (p0 + k < npix) ? pixel_rgb(depth[p0 + k], count[p0 + k], edge[p0 + k], shade) : 0u;
-    rgb[g * 3 + 0] = c[0] | (c[1] << 24);
-    rgb[g * 3 + 1] = (c[1] >> 8) | (c[2] << 16);
-    rgb[g * 3 + 2] = (c[2] >> 16) | (c[3] << 8);
-}
-
-// ---- the field frame ("The field frame"): the same splat carrying a value ----
-// Per pixel the minimum of (bits(w) << 32) | bits(s) over the covering particles, s >= +0 the scalar of
-// the particle's vel4 row (xyz = velocity, w = density): the high word IS the depth buffer of the flat
-// frame, the low word the value of the nearest particle (the smallest among several at that depth).
-
-constexpr int kFieldTilePixels = 8192;                         // 12 B per pixel: minima, then counts; 96 KB of dynamic LDS
-constexpr int kFieldPerThread = 4;
-constexpr int kFieldBlock = kSplatThreads * kFieldPerThread;   // particles per workgroup
-constexpr size_t kFieldTileBytes = (size_t)kFieldTilePixels * 12;
-constexpr unsigned long long kFieldEmpty = 0xFFFFFFFFFFFFFFFFull;
-
-__device__ __forceinline__ uint32_t field_bits(const float4 v, int field) {
-    float s;
-    if (field == SPH_FIELD_SPEED) s = sqrtf((v.x * v.x + v.y * v.y) + v.z * v.z);
-    else if (field == SPH_FIELD_DENSITY) s = v.w;
-    else s = fmaxf(0.f, SPH_GAS_CONSTANT * (v.w - SPH_REST_DENSITY)); // as sph_download_state
-    return __float_as_uint(s);
-}
-
-__device__ __forceinline__ unsigned long long field_word(uint32_t wbits, uint32_t sbits) {
-    return ((unsigned long long)wbits << 32) | sbits;
-}
-
-// range[0] / range[1]: the bits of lo / hi compose will read -- the fixed range, or the identities of the reduction
-__global__ __launch_bounds__(256) void k_field_clear(unsigned long long *__restrict__ packed, uint32_t *__restrict__ count,
-                                                     int npix, uint32_t *__restrict__ range, uint32_t lo, uint32_t hi) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < npix) {
-        packed[i] = kFieldEmpty;
-        count[i] = 0u;
-    }
-    if (i == 0) {
-        range[0] = lo;
-        range[1] = hi;
-    }
-}
-
 // automatic range: minimum and maximum of the bit patterns of s over ALL n rows (s >= +0: bit order = value order);
 // wave64 shuffles, one LDS step across the four waves, then at most one atomic per workgroup and word
 __global__ __launch_bounds__(256) void k_field_range(const float4 *__restrict__ vel4, int n, int field,
@@ -254,10 +240,9 @@ __global__ __launch_bounds__(256) void k_field_range(const float4 *__restrict__ 
         lo = min(lo, b);
         hi = max(hi, b);
     }
-    for (int m = 32; m > 0; m >>= 1) {
-        lo = min(lo, (uint32_t)__shfl_xor((int)lo, m, 64));
-        hi = max(hi, (uint32_t)__shfl_xor((int)hi, m, 64));
-    }
+    // (the helpers compare signed values: flip the top bit around them)
+    lo = (uint32_t)wave_min_i32((int)(lo ^ 0x80000000u)) ^ 0x80000000u;
+    hi = (uint32_t)wave_max_i32((int)(hi ^ 0x80000000u)) ^ 0x80000000u;
     if ((threadIdx.x & 63) == 0) {
         wlo[threadIdx.x >> 6] = lo;
         whi[threadIdx.x >> 6] = hi;
@@ -269,121 +254,6 @@ __global__ __launch_bounds__(256) void k_field_range(const float4 *__restrict__ 
         // (lo only falls and hi only rises: a stale load that already is past ours settles it)
         if (range[0] > lo) atomicMin(&range[0], lo);
         if (range[1] < hi) atomicMax(&range[1], hi);
-    }
-}
-
-// the check path (SPH_RENDER_PLAIN=1)
-__global__ __launch_bounds__(256) void k_field_splat_plain(const float4 *__restrict__ pos4, const float4 *__restrict__ vel4,
-                                                           int n, RenderParams R, int field,
-                                                           unsigned long long *__restrict__ packed, uint32_t *__restrict__ count) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const float4 p = pos4[i];
-    const Pixel q = project(p.x, p.y, p.z, R);
-    const unsigned long long m = field_word(q.wbits, field_bits(vel4[i], field));
-    const int r = R.radius;
-    for (int y = max(q.py - r, 0); y <= min(q.py + r, R.height - 1); ++y)
-        for (int x = max(q.px - r, 0); x <= min(q.px + r, R.width - 1); ++x) {
-            atomicAdd(&count[y * R.width + x], 1u);
-            atomicMin(&packed[y * R.width + x], m);
-        }
-}
-
-// k_splat_tile with the packed minimum in the tile: same rectangle, same fallback
-__global__ __launch_bounds__(kSplatThreads) void k_field_splat_tile(const float4 *__restrict__ pos4, const float4 *__restrict__ vel4,
-                                                                    int n, RenderParams R, int field,
-                                                                    unsigned long long *__restrict__ packed,
-                                                                    uint32_t *__restrict__ count) {
-    extern __shared__ unsigned long long tMin[];                    // kFieldTilePixels minima ...
-    uint32_t *tCount = reinterpret_cast<uint32_t *>(tMin + kFieldTilePixels); // ... then as many counts
-    __shared__ int box[4];
-    const int t = threadIdx.x;
-    const int base = blockIdx.x * kFieldBlock;
-    const int r = R.radius;
-    if (t < 2) box[t] = 0x7fffffff;
-    else if (t < 4) box[t] = -0x7fffffff;
-
-    int qx[kFieldPerThread], qy[kFieldPerThread];
-    unsigned long long qm[kFieldPerThread];
-    int lox = 0x7fffffff, loy = 0x7fffffff, hix = -0x7fffffff, hiy = -0x7fffffff;
-#pragma unroll
-    for (int k = 0; k < kFieldPerThread; ++k) {
-        const int i = base + k * kSplatThreads + t;
-        qx[k] = qy[k] = -0x40000000; // (no particle, or one whose square misses the viewport: covers nothing)
-        qm[k] = kFieldEmpty;
-        if (i < n) {
-            const float4 p = pos4[i];
-            const Pixel q = project(p.x, p.y, p.z, R);
-            if (q.px + r >= 0 && q.px - r < R.width && q.py + r >= 0 && q.py - r < R.height) {
-                qx[k] = q.px;
-                qy[k] = q.py;
-                qm[k] = field_word(q.wbits, field_bits(vel4[i], field));
-                lox = min(lox, q.px);
-                hix = max(hix, q.px);
-                loy = min(loy, q.py);
-                hiy = max(hiy, q.py);
-            }
-        }
-    }
-    lox = wave_min(lox);
-    loy = wave_min(loy);
-    hix = wave_max(hix);
-    hiy = wave_max(hiy);
-    __syncthreads();
-    if ((t & 63) == 0) {
-        atomicMin(&box[0], lox);
-        atomicMin(&box[1], loy);
-        atomicMax(&box[2], hix);
-        atomicMax(&box[3], hiy);
-    }
-    __syncthreads();
-    if (box[2] < box[0]) return; // nothing of this workgroup is on screen (uniform)
-    const int x0 = max(box[0] - r, 0), y0 = max(box[1] - r, 0);
-    const int x1 = min(box[2] + r, R.width - 1), y1 = min(box[3] + r, R.height - 1);
-    const int bw = x1 - x0 + 1, bh = y1 - y0 + 1;
-    const long long area = (long long)bw * bh;
-
-    if (area > kFieldTilePixels) { // (uniform) the rectangle does not fit: per-hit global atomics
-#pragma unroll
-        for (int k = 0; k < kFieldPerThread; ++k) {
-            if (qx[k] == -0x40000000) continue;
-            for (int y = max(qy[k] - r, 0); y <= min(qy[k] + r, R.height - 1); ++y)
-                for (int x = max(qx[k] - r, 0); x <= min(qx[k] + r, R.width - 1); ++x) {
-                    atomicAdd(&count[y * R.width + x], 1u);
-                    atomicMin(&packed[y * R.width + x], qm[k]);
-                }
-        }
-        return;
-    }
-
-    const int tile = (int)area;
-    for (int e = t; e < tile; e += kSplatThreads) {
-        tCount[e] = 0u;
-        tMin[e] = kFieldEmpty;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < kFieldPerThread; ++k) {
-        if (qx[k] == -0x40000000) continue;
-        // (every pixel of the clipped square lies inside [x0, x1] x [y0, y1] by construction)
-        for (int y = max(qy[k] - r, 0); y <= min(qy[k] + r, R.height - 1); ++y)
-            for (int x = max(qx[k] - r, 0); x <= min(qx[k] + r, R.width - 1); ++x) {
-                const int e = (y - y0) * bw + (x - x0);
-                atomicAdd(&tCount[e], 1u);
-                atomicMin(&tMin[e], qm[k]);
-            }
-    }
-    __syncthreads();
-    for (int e = t; e < tile; e += kSplatThreads) {
-        const uint32_t c = tCount[e];
-        if (c == 0u) continue;
-        const int ey = e / bw;
-        const int g = (y0 + ey) * R.width + x0 + (e - ey * bw);
-        atomicAdd(&count[g], c);
-        // The packed word only ever decreases during the splat, so a plain (aligned, single 8-byte) load,
-        // however stale, is >= the final one: if it is already <= ours, ours cannot change the result.
-        const unsigned long long m = tMin[e];
-        if (packed[g] > m) atomicMin(&packed[g], m);
     }
 }
 
@@ -407,28 +277,43 @@ __device__ __forceinline__ uint32_t field_rgb(unsigned long long m, uint32_t c, 
     return field_ramp(q);
 }
 
-// as k_render_compose; also leaves the high words in `depth`, the depth buffer sph_download_frame_buffers serves
+// four pixels = 12 bytes = three dwords per thread (rgb is padded to a multiple of four pixels); colour(p) = 0xBBGGRR of pixel p
+template <class Colour>
+__device__ __forceinline__ void compose_quad(int npix, uint32_t *__restrict__ rgb, Colour colour) {
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    const int p0 = g * 4;
+    if (p0 >= npix) return;
+    uint32_t c[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) c[k] = (p0 + k < npix) ? colour(p0 + k) : 0u;
+    rgb[g * 3 + 0] = c[0] | (c[1] << 24);
+    rgb[g * 3 + 1] = (c[1] >> 8) | (c[2] << 16);
+    rgb[g * 3 + 2] = (c[2] >> 16) | (c[3] << 8);
+}
+
+__global__ __launch_bounds__(256) void k_render_compose(const uint32_t *__restrict__ depth, const uint32_t *__restrict__ count,
+                                                        const uint32_t *__restrict__ edge, int npix, int shade,
+                                                        uint32_t *__restrict__ rgb) {
+    compose_quad(npix, rgb, [&](int p) { return pixel_rgb(depth[p], count[p], edge[p], shade); });
+}
+
+// also leaves the high words in `depth`, the depth buffer sph_download_frame_buffers serves
 __global__ __launch_bounds__(256) void k_field_compose(const unsigned long long *__restrict__ packed,
                                                        const uint32_t *__restrict__ count, const uint32_t *__restrict__ edge,
                                                        const uint32_t *__restrict__ range, int npix,
                                                        uint32_t *__restrict__ depth, uint32_t *__restrict__ rgb) {
-    const int g = blockIdx.x * 256 + threadIdx.x;
-    const int p0 = g * 4;
-    if (p0 >= npix) return;
-    const float lo = __uint_as_float(range[0]), hi = __uint_as_float(range[1]);
-    uint32_t c[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        c[k] = 0u;
-        if (p0 + k < npix) {
-            const unsigned long long m = packed[p0 + k];
-            depth[p0 + k] = (uint32_t)(m >> 32);
-            c[k] = field_rgb(m, count[p0 + k], edge[p0 + k], lo, hi);
-        }
-    }
-    rgb[g * 3 + 0] = c[0] | (c[1] << 24);
-    rgb[g * 3 + 1] = (c[1] >> 8) | (c[2] << 16);
-    rgb[g * 3 + 2] = (c[2] >> 16) | (c[3] << 8);
+    compose_quad(npix, rgb, [&](int p) {
+        const unsigned long long m = packed[p];
+        depth[p] = (uint32_t)(m >> 32);
+        return field_rgb(m, count[p], edge[p], __uint_as_float(range[0]), __uint_as_float(range[1]));
+    });
+}
+
+template <class Pay>
+void launch_splat(const RenderParams &R, const float4 *pos4, int n, bool plain, Pay pay, uint32_t *count, hipStream_t s) {
+    if (n <= 0) return;
+    if (plain) k_splat_plain<<<(n + 255) / 256, 256, 0, s>>>(pos4, n, R, pay, count);
+    else k_splat_tile<<<(n + kSplatBlock - 1) / kSplatBlock, kSplatThreads, 0, s>>>(pos4, n, R, pay, count);
 }
 
 } // namespace
@@ -442,19 +327,10 @@ void sph_launch_render_edges(const RenderParams &R, uint32_t *edge, hipStream_t 
 void sph_launch_render(const RenderParams &R, const float4 *pos4, int n, bool plain, uint32_t *depth, uint32_t *count,
                        const uint32_t *edge, uint32_t *rgb, hipStream_t s) {
     const int npix = R.width * R.height;
-    k_render_clear<<<(npix + 255) / 256, 256, 0, s>>>(depth, count, npix);
-    if (n > 0) {
-        if (plain) k_splat_plain<<<(n + 255) / 256, 256, 0, s>>>(pos4, n, R, depth, count);
-        else k_splat_tile<<<(n + kSplatBlock - 1) / kSplatBlock, kSplatThreads, 0, s>>>(pos4, n, R, depth, count);
-    }
+    k_render_clear<FlatPayload><<<(npix + 255) / 256, 256, 0, s>>>(depth, count, npix, nullptr, 0u, 0u);
+    launch_splat(R, pos4, n, plain, FlatPayload{depth}, count, s);
     const int quads = (npix + 3) / 4;
     k_render_compose<<<(quads + 255) / 256, 256, 0, s>>>(depth, count, edge, npix, R.shade, rgb);
-}
-
-int sph_prepare_render_field() {
-    // (above 64 KB of dynamic LDS a kernel has to be told; the attribute is per device)
-    return (int)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_field_splat_tile),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFieldTileBytes);
 }
 
 void sph_launch_render_field(const RenderParams &R, const float4 *pos4, const float4 *vel4, int n, bool plain, int field,
@@ -462,15 +338,11 @@ void sph_launch_render_field(const RenderParams &R, const float4 *pos4, const fl
                             const uint32_t *edge, uint32_t *range, uint32_t *rgb, hipStream_t s) {
     const int npix = R.width * R.height;
     const bool reduce = autoRange && n > 0;
-    k_field_clear<<<(npix + 255) / 256, 256, 0, s>>>(packed, count, npix, range, reduce ? 0xFFFFFFFFu : __builtin_bit_cast(uint32_t, lo),
-                                                     reduce ? 0u : __builtin_bit_cast(uint32_t, hi));
+    k_render_clear<FieldPayload><<<(npix + 255) / 256, 256, 0, s>>>(packed, count, npix, range,
+                                                                   reduce ? 0xFFFFFFFFu : __builtin_bit_cast(uint32_t, lo),
+                                                                   reduce ? 0u : __builtin_bit_cast(uint32_t, hi));
     if (reduce) k_field_range<<<min((n + 255) / 256, 1024), 256, 0, s>>>(vel4, n, field, range);
-    if (n > 0) {
-        if (plain) k_field_splat_plain<<<(n + 255) / 256, 256, 0, s>>>(pos4, vel4, n, R, field, packed, count);
-        else
-            k_field_splat_tile<<<(n + kFieldBlock - 1) / kFieldBlock, kSplatThreads, kFieldTileBytes, s>>>(pos4, vel4, n, R, field,
-                                                                                                          packed, count);
-    }
+    launch_splat(R, pos4, n, plain, FieldPayload{packed, vel4, field}, count, s);
     const int quads = (npix + 3) / 4;
     k_field_compose<<<(quads + 255) / 256, 256, 0, s>>>(packed, count, edge, range, npix, depth, rgb);
 }

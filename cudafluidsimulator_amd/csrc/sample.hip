@@ -101,15 +101,6 @@ __global__ __launch_bounds__(256) void k_sample_plain(DevParams P, SampleArgs A,
     out[g] = sample_value<kShepard>(den, num);
 }
 
-__device__ __forceinline__ int wave_min_i(int v) {
-    for (int m = 32; m > 0; m >>= 1) v = min(v, __shfl_xor(v, m, 64));
-    return __builtin_amdgcn_readfirstlane(v);
-}
-__device__ __forceinline__ int wave_max_i(int v) {
-    for (int m = 32; m > 0; m >>= 1) v = max(v, __shfl_xor(v, m, 64));
-    return __builtin_amdgcn_readfirstlane(v);
-}
-
 // One wave per brick: 64 consecutive ix of the lattice row (iy, iz).  blockIdx.x = (iz ny + iy) bricks + brick.
 template <bool kShepard>
 __global__ __launch_bounds__(64) void k_sample_tile(DevParams P, SampleArgs A, int bricks, float *__restrict__ out) {
@@ -145,7 +136,8 @@ __global__ __launch_bounds__(64) void k_sample_tile(DevParams P, SampleArgs A, i
                     }
                 }
                 // the stretch the wave stages: from the first window's start to the last one's end
-                const int s0 = max(wave_min_i(ws), 0), s1 = min(wave_max_i(we), A.n);
+                const int s0 = max(__builtin_amdgcn_readfirstlane(wave_min_i32(ws)), 0);
+                const int s1 = min(__builtin_amdgcn_readfirstlane(wave_max_i32(we)), A.n);
                 for (int base = s0; base < s1; base += kSampleChunk) {
                     const int cnt = min(kSampleChunk, s1 - base);
                     __syncthreads(); // the previous chunk has been read

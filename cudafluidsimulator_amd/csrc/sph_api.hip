@@ -442,7 +442,7 @@ void sph_destroy(sph_handle *h) {
                     (void *)h->frameHost, (void *)h->rangeHost, (void *)h->boundsHost, (void *)h->sampleHost})
         if (p) (void)hipHostFree(p);
     for (hipEvent_t e : {h->computeDone[0], h->computeDone[1], h->copyDone[0], h->copyDone[1], h->stageFree[0], h->stageFree[1],
-                         h->frameDrawn, h->frameCopied, h->sampleDone, h->sampleCopied})
+                         h->frameOut.done, h->frameOut.copied, h->sampleOut.done, h->sampleOut.copied})
         if (e) (void)hipEventDestroy(e);
     for (auto &se : h->ring) {
         for (auto &e : se.e) if (e) (void)hipEventDestroy(e);

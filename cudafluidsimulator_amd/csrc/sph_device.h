@@ -57,6 +57,23 @@ __device__ __forceinline__ uint32_t sph_cell_key(const DevParams &P, int cx, int
     return (uint32_t)(cx + cy * P.D + cz * P.D * P.D);
 }
 
+// Reductions over the 64 lanes of a wave (xor butterfly: every lane ends up with the result)
+__device__ __forceinline__ int wave_min_i32(int v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off));
+    return v;
+}
+__device__ __forceinline__ int wave_max_i32(int v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off));
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
 // Particle state lives in two float4 streams, both in cell-sorted order:
 //   pos4[i] = (x, y, z, bits(original particle id))
 //   vel4[i] = (vx, vy, vz, rho_i)      rho filled by the density sweep
@@ -214,9 +231,7 @@ void sph_launch_render(const RenderParams &R, const float4 *pos4, int n, bool pl
                        const uint32_t *edge, uint32_t *rgb, hipStream_t s);
 // The field frame: clear + (autoRange: min / max of the field over vel4[0, n) into range[0..1], else the bits of
 // lo / hi) + splat of (pos4, vel4)[0, n) into `packed` (depth bits << 32 | value bits) and `count` + compose into
-// rgb, which also leaves the depth words in `depth`.  field = SPH_FIELD_*.  sph_prepare_render_field() comes first on
-// the device that will run it (allows the tiled splat its LDS; returns a hipError_t).
-int sph_prepare_render_field();
+// rgb, which also leaves the depth words in `depth`.  field = SPH_FIELD_*.
 void sph_launch_render_field(const RenderParams &R, const float4 *pos4, const float4 *vel4, int n, bool plain, int field,
                             bool autoRange, float lo, float hi, unsigned long long *packed, uint32_t *depth, uint32_t *count,
                             const uint32_t *edge, uint32_t *range, uint32_t *rgb, hipStream_t s);

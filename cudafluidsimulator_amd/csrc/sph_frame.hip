@@ -16,7 +16,7 @@ int render_resize(sph_handle *h, int width, int height) {
     // the old buffers may still be read by a queued compose / frame copy
     HIPCHK(h, hipStreamSynchronize(h->compute));
     HIPCHK(h, hipStreamSynchronize(h->copy));
-    h->framePending = false;
+    h->frameOut.pending = false;
     h->frameValid = false;
     for (uint32_t **b : {&h->rDepth, &h->rCount, &h->rEdge, &h->rRgb}) {
         if (*b) (void)hipFree(*b);
@@ -36,8 +36,6 @@ int render_resize(sph_handle *h, int width, int height) {
     HIPCHK(h, hipMalloc(&h->rRgb, rgbBytes));
     HIPCHK(h, hipHostMalloc(&h->frameHost, rgbBytes, hipHostMallocDefault));
     memset(h->frameHost, 0, rgbBytes);
-    if (!h->frameDrawn) HIPCHK(h, hipEventCreateWithFlags(&h->frameDrawn, hipEventDisableTiming));
-    if (!h->frameCopied) HIPCHK(h, hipEventCreateWithFlags(&h->frameCopied, hipEventDisableTiming));
     RenderParams R = h->rp;
     R.width = width;
     R.height = height;
@@ -46,16 +44,6 @@ int render_resize(sph_handle *h, int width, int height) {
     sph_launch_render_edges(R, h->rEdge, h->compute);
     HIPCHK(h, hipGetLastError());
     h->rp = R;
-    return SPH_OK;
-}
-
-// a caller's option struct into `o` (zero: defaults): as many bytes as its struct_size says, at most all of `o`
-template <class Opt>
-int copy_options(sph_handle *h, const Opt *opt, Opt &o, const char *unset) {
-    if (!opt) return SPH_OK;
-    if (opt->struct_size <= 0) return fail(h, SPH_EINVAL, unset);
-    const size_t sz = (size_t)opt->struct_size;
-    memcpy(&o, opt, sz < sizeof o ? sz : sizeof o);
     return SPH_OK;
 }
 
@@ -78,15 +66,11 @@ int frame_begin(sph_handle *h, const Opt *opt, const char *unset, Rest rest, boo
         if (!h->rPacked) HIPCHK(h, hipMalloc(&h->rPacked, (size_t)width * height * sizeof(unsigned long long)));
         if (!h->rRange) HIPCHK(h, hipMalloc(&h->rRange, 2 * sizeof(uint32_t)));
         if (!h->rangeHost) HIPCHK(h, hipHostMalloc(&h->rangeHost, 2 * sizeof(uint32_t), hipHostMallocDefault));
-        HIPCHK(h, (hipError_t)sph_prepare_render_field());
     }
     h->rp.radius = (pointSize - 1) / 2;
     plain = false;
     if (const char *e = getenv("SPH_RENDER_PLAIN")) plain = atoi(e) != 0;
-    if (h->framePending) { // the previous frame's copy still reads the device frame the compose is about to rewrite
-        HIPCHK(h, hipStreamWaitEvent(h->compute, h->frameCopied, 0));
-        h->framePending = false;
-    }
+    if ((rc = outbound_fence(h, h->frameOut))) return rc; // the previous frame's copy still reads the device frame the compose is about to rewrite
     return pair_begin(h, &h->renderSeconds, &pe);
 }
 
@@ -98,14 +82,9 @@ int frame_finish(sph_handle *h, PairEvent *pe, bool field) {
     h->renderFrames += 1;
     h->frameValid = true;
     h->fieldFrame = field;
-    // the frame leaves on the copy stream, behind an event, like the positions do
-    HIPCHK(h, hipEventRecord(h->frameDrawn, h->compute));
-    HIPCHK(h, hipStreamWaitEvent(h->copy, h->frameDrawn, 0));
-    HIPCHK(h, hipMemcpyAsync(h->frameHost, h->rRgb, (size_t)h->rp.width * h->rp.height * 3, hipMemcpyDeviceToHost, h->copy));
-    if (field) HIPCHK(h, hipMemcpyAsync(h->rangeHost, h->rRange, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, h->copy));
-    HIPCHK(h, hipEventRecord(h->frameCopied, h->copy));
-    h->framePending = true;
-    return SPH_OK;
+    const OutboundCopy frame{h->frameHost, h->rRgb, (size_t)h->rp.width * h->rp.height * 3};
+    if (!field) return outbound_send(h, h->frameOut, {frame});
+    return outbound_send(h, h->frameOut, {frame, {h->rangeHost, h->rRange, 2 * sizeof(uint32_t)}});
 }
 
 } // namespace
@@ -136,7 +115,7 @@ const uint8_t *sph_frame_host(sph_handle *h, int *width, int *height) {
         h->err = "sph_render_frame must come first";
         return nullptr;
     }
-    if (h->framePending && hipEventSynchronize(h->frameCopied) != hipSuccess) {
+    if (outbound_wait(h->frameOut) != hipSuccess) {
         h->err = "frame copy failed";
         return nullptr;
     }
@@ -159,19 +138,7 @@ int sph_download_frame_buffers(sph_handle *h, uint32_t *depth_bits, uint32_t *co
 
 int sph_get_render_time(sph_handle *h, double *seconds, int64_t *frames, int reset) {
     if (!h) return SPH_EINVAL;
-    SPH_ON_DEVICE(h);
-    for (auto &pe : h->pairs)
-        if (pe.used && pe.target == &h->renderSeconds) {
-            int rc = resolve_pair(h, pe);
-            if (rc) return rc;
-        }
-    if (seconds) *seconds = h->renderSeconds;
-    if (frames) *frames = h->renderFrames;
-    if (reset) {
-        h->renderSeconds = 0;
-        h->renderFrames = 0;
-    }
-    return SPH_OK;
+    return timed_total(h, &h->renderSeconds, &h->renderFrames, seconds, frames, reset);
 }
 
 int sph_render_field(sph_handle *h, const SphFieldFrameOptions *opt) {
@@ -180,7 +147,7 @@ int sph_render_field(sph_handle *h, const SphFieldFrameOptions *opt) {
     bool plain = false;
     PairEvent *pe = nullptr;
     auto rest = [](const SphFieldFrameOptions &o) -> const char * {
-        if (o.field != SPH_FIELD_SPEED && o.field != SPH_FIELD_DENSITY && o.field != SPH_FIELD_PRESSURE) return "unknown field";
+        if (bad_field(o.field)) return "unknown field";
         if (!std::isfinite(o.value_lo) || !std::isfinite(o.value_hi)) return "value_lo / value_hi must be finite";
         return o.value_hi < o.value_lo ? "value_hi < value_lo" : nullptr;
     };
@@ -209,7 +176,7 @@ int sph_field_range(sph_handle *h, float *lo, float *hi) {
     if (!h) return SPH_EINVAL;
     SPH_ON_DEVICE(h);
     if (!h->frameValid || !h->fieldFrame) return fail(h, SPH_ESTATE, "the last render was not a field frame (sph_render_field)");
-    if (h->framePending) HIPCHK(h, hipEventSynchronize(h->frameCopied));
+    HIPCHK(h, outbound_wait(h->frameOut));
     if (lo) memcpy(lo, &h->rangeHost[0], sizeof(float));
     if (hi) memcpy(hi, &h->rangeHost[1], sizeof(float));
     return SPH_OK;

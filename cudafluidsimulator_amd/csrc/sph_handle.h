@@ -6,6 +6,8 @@
 #include "sph_device.h"
 
 #include <chrono>
+#include <cstring>
+#include <initializer_list>
 #include <string>
 
 namespace sph_host {
@@ -21,6 +23,18 @@ struct PairEvent { // one timed section of the slab path
     bool used = false;
 };
 constexpr int kPairRing = 48;
+
+// A result on its way to pinned memory over the copy stream, behind what `compute` had queued when it left
+// (outbound_* below): the frame, the field sample.
+struct Outbound {
+    hipEvent_t done = nullptr, copied = nullptr; // on compute: the result is complete; on copy: it has arrived
+    bool pending = false;                        // a copy is queued: `copied` tells when the device buffer is free again
+};
+struct OutboundCopy {
+    void *dst;
+    const void *src;
+    size_t bytes;
+};
 
 struct StepEvents {
     hipEvent_t e[6] = {}; // start, hash, sort, gather, density, force
@@ -141,8 +155,7 @@ struct sph_handle {
     RenderParams rp{};               // size / point radius / shade of the last render (width 0: none yet)
     uint32_t *rDepth = nullptr, *rCount = nullptr, *rEdge = nullptr, *rRgb = nullptr;
     uint8_t *frameHost = nullptr;
-    hipEvent_t frameDrawn = nullptr, frameCopied = nullptr;
-    bool framePending = false;       // a frame copy is queued on the copy stream
+    sph_host::Outbound frameOut;     // the frame (a field frame: and its range) on its way to frameHost / rangeHost
     bool frameValid = false;         // the buffers hold a rendered frame of the size in rp
     double renderSeconds = 0;        // clear + splat + compose, from HIP events (PairEvent ring)
     long long renderFrames = 0;
@@ -158,8 +171,7 @@ struct sph_handle {
     float *sampleDev = nullptr, *sampleHost = nullptr;
     size_t sampleCap = 0;            // floats either buffer holds
     int sampleDim[3] = {0, 0, 0};    // nx, ny, nz of the last sample
-    hipEvent_t sampleDone = nullptr, sampleCopied = nullptr;
-    bool samplePending = false;      // a copy of the values is queued on the copy stream
+    sph_host::Outbound sampleOut;    // the values on their way to sampleHost
     bool sampleValid = false;
     double sampleSeconds = 0;        // the sampling kernel, from HIP events (PairEvent ring)
     long long sampleCount = 0;
@@ -201,6 +213,13 @@ int tile_chunk(const sph_handle *h, int count, int layers);
 int launch_density(sph_handle *h, SweepArgs &A, hipStream_t stream);
 int pair_begin(sph_handle *h, double *target, PairEvent **out, hipStream_t stream = nullptr);
 int resolve_pair(sph_handle *h, PairEvent &pe);
+// seconds and count of the sections timed into *seconds (render, sample), the open ones resolved first; reset: both to zero after
+int timed_total(sph_handle *h, double *seconds, long long *count, double *secondsOut, int64_t *countOut, int reset);
+// a result leaving on the copy stream: `compute` waits until the last copy has read the device buffer (before it is
+// rewritten); the copies are queued behind everything `compute` holds now; the host waits for the last copy
+int outbound_fence(sph_handle *h, Outbound &o);
+int outbound_send(sph_handle *h, Outbound &o, std::initializer_list<OutboundCopy> copies);
+hipError_t outbound_wait(const Outbound &o);
 int begin_step_events(sph_handle *h);
 int build_grid_ahead(sph_handle *h);
 int resolve_events(sph_handle *h, StepEvents &se);
@@ -231,5 +250,17 @@ int staged_upload(sph_handle *h, float4 *dev, size_t n, Fill fill) {
     HIPCHK(h, hipStreamSynchronize(h->compute));
     return SPH_OK;
 }
+
+// a caller's option struct into `o` (zero: defaults): as many bytes as its struct_size says, at most all of `o`
+template <class Opt>
+int copy_options(sph_handle *h, const Opt *opt, Opt &o, const char *unset) {
+    if (!opt) return SPH_OK;
+    if (opt->struct_size <= 0) return fail(h, SPH_EINVAL, unset);
+    const size_t sz = (size_t)opt->struct_size;
+    memcpy(&o, opt, sz < sizeof o ? sz : sizeof o);
+    return SPH_OK;
+}
+
+inline bool bad_field(int f) { return f != SPH_FIELD_SPEED && f != SPH_FIELD_DENSITY && f != SPH_FIELD_PRESSURE; }
 
 } // namespace sph_host

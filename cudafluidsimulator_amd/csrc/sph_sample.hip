@@ -3,7 +3,6 @@
 
 #include <cmath>
 #include <cstdlib>
-#include <cstring>
 
 using namespace sph_host;
 
@@ -11,13 +10,11 @@ namespace {
 
 // (re)allocate the value buffers for `points` floats
 int sample_reserve(sph_handle *h, size_t points) {
-    if (!h->sampleDone) HIPCHK(h, hipEventCreateWithFlags(&h->sampleDone, hipEventDisableTiming));
-    if (!h->sampleCopied) HIPCHK(h, hipEventCreateWithFlags(&h->sampleCopied, hipEventDisableTiming));
     if (points <= h->sampleCap) return SPH_OK;
     // the old buffers may still be read by a queued copy
     HIPCHK(h, hipStreamSynchronize(h->compute));
     HIPCHK(h, hipStreamSynchronize(h->copy));
-    h->samplePending = false;
+    h->sampleOut.pending = false;
     h->sampleValid = false;
     if (h->sampleDev) (void)hipFree(h->sampleDev);
     if (h->sampleHost) (void)hipHostFree(h->sampleHost);
@@ -37,7 +34,7 @@ const char *bad_lattice(const SphSampleLattice &L) {
         if (!std::isfinite(o)) return "origin must be finite";
     for (float s : L.spacing)
         if (!std::isfinite(s) || !(s > 0.f)) return "spacing must be finite and > 0";
-    if (L.field != SPH_FIELD_SPEED && L.field != SPH_FIELD_DENSITY && L.field != SPH_FIELD_PRESSURE) return "unknown field";
+    if (bad_field(L.field)) return "unknown field";
     return nullptr;
 }
 
@@ -53,24 +50,21 @@ int sph_sample_field(sph_handle *h, const SphSampleLattice *lat) {
     if (h->opt.sweep == SPH_SWEEP_LINKED) return fail(h, SPH_ESTATE, "the field sample needs a cell table: not available with SPH_SWEEP_LINKED");
     if (h->P.morton) return fail(h, SPH_ESTATE, "the field sample walks rows of cells as runs of the stream: not available with SPH_KEY_MORTON");
     if (h->phase != 0 && h->phase != 1) return fail(h, SPH_ESTATE, "a step split into phases is still open");
-    if (!lat || lat->struct_size <= 0) return fail(h, SPH_EINVAL, "SphSampleLattice.struct_size is not set");
+    const char *unset = "SphSampleLattice.struct_size is not set";
+    if (!lat) return fail(h, SPH_EINVAL, unset); // (no defaults: a lattice has to be given)
     SphSampleLattice L{};
-    const size_t sz = (size_t)lat->struct_size;
-    memcpy(&L, lat, sz < sizeof L ? sz : sizeof L);
+    int rc = copy_options(h, lat, L, unset);
+    if (rc) return rc;
     if (const char *bad = bad_lattice(L)) return fail(h, SPH_EINVAL, bad);
     const size_t points = (size_t)L.nx * L.ny * L.nz;
-    int rc = sample_reserve(h, points);
-    if (rc) return rc;
+    if ((rc = sample_reserve(h, points))) return rc;
     // A grid of the state the handle holds NOW.  Phase 1: it exists (sph_phase_grid, or built ahead by a timed
     // step).  Phase 0: the table of the last step is the pre-integration one; the next step's grid is built
     // here, ahead, and that step consumes it.
     if (h->phase == 0 && h->n > 0 && (rc = build_grid_ahead(h))) return rc;
     bool plain = false;
     if (const char *e = getenv("SPH_SAMPLE_PLAIN")) plain = atoi(e) != 0;
-    if (h->samplePending) { // the previous sample's copy still reads the device buffer
-        HIPCHK(h, hipStreamWaitEvent(h->compute, h->sampleCopied, 0));
-        h->samplePending = false;
-    }
+    if ((rc = outbound_fence(h, h->sampleOut))) return rc; // the previous sample's copy still reads the device buffer
     SampleArgs A{};
     A.nx = L.nx, A.ny = L.ny, A.nz = L.nz;
     A.ox = L.origin[0], A.oy = L.origin[1], A.oz = L.origin[2];
@@ -97,12 +91,7 @@ int sph_sample_field(sph_handle *h, const SphSampleLattice *lat) {
     h->sampleCount += 1;
     (plain ? h->samplePlainCalls : h->sampleTileCalls) += 1;
     h->sampleValid = false; // (until the copy is queued: the pinned buffer still holds the previous sample)
-    // the values leave on the copy stream, behind an event, like the frame does
-    HIPCHK(h, hipEventRecord(h->sampleDone, h->compute));
-    HIPCHK(h, hipStreamWaitEvent(h->copy, h->sampleDone, 0));
-    HIPCHK(h, hipMemcpyAsync(h->sampleHost, h->sampleDev, points * sizeof(float), hipMemcpyDeviceToHost, h->copy));
-    HIPCHK(h, hipEventRecord(h->sampleCopied, h->copy));
-    h->samplePending = true;
+    if ((rc = outbound_send(h, h->sampleOut, {{h->sampleHost, h->sampleDev, points * sizeof(float)}}))) return rc;
     h->sampleDim[0] = L.nx, h->sampleDim[1] = L.ny, h->sampleDim[2] = L.nz;
     h->sampleValid = true;
     return SPH_OK;
@@ -114,7 +103,7 @@ const float *sph_sample_host(sph_handle *h, int *nx, int *ny, int *nz) {
         h->err = "sph_sample_field must come first";
         return nullptr;
     }
-    if (h->samplePending && hipEventSynchronize(h->sampleCopied) != hipSuccess) {
+    if (outbound_wait(h->sampleOut) != hipSuccess) {
         h->err = "sample copy failed";
         return nullptr;
     }
@@ -126,19 +115,7 @@ const float *sph_sample_host(sph_handle *h, int *nx, int *ny, int *nz) {
 
 int sph_get_sample_time(sph_handle *h, double *seconds, int64_t *samples, int reset) {
     if (!h) return SPH_EINVAL;
-    SPH_ON_DEVICE(h);
-    for (auto &pe : h->pairs)
-        if (pe.used && pe.target == &h->sampleSeconds) {
-            int rc = resolve_pair(h, pe);
-            if (rc) return rc;
-        }
-    if (seconds) *seconds = h->sampleSeconds;
-    if (samples) *samples = h->sampleCount;
-    if (reset) {
-        h->sampleSeconds = 0;
-        h->sampleCount = 0;
-    }
-    return SPH_OK;
+    return timed_total(h, &h->sampleSeconds, &h->sampleCount, seconds, samples, reset);
 }
 
 } // extern "C"

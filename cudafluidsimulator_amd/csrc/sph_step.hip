@@ -195,6 +195,41 @@ int pair_begin(sph_handle *h, double *target, PairEvent **out, hipStream_t strea
     return SPH_OK;
 }
 
+int timed_total(sph_handle *h, double *seconds, long long *count, double *secondsOut, int64_t *countOut, int reset) {
+    SPH_ON_DEVICE(h);
+    for (auto &pe : h->pairs)
+        if (pe.used && pe.target == seconds) {
+            int rc = resolve_pair(h, pe);
+            if (rc) return rc;
+        }
+    if (secondsOut) *secondsOut = *seconds;
+    if (countOut) *countOut = *count;
+    if (reset) {
+        *seconds = 0;
+        *count = 0;
+    }
+    return SPH_OK;
+}
+
+int outbound_fence(sph_handle *h, Outbound &o) {
+    if (o.pending) HIPCHK(h, hipStreamWaitEvent(h->compute, o.copied, 0));
+    o.pending = false;
+    return SPH_OK;
+}
+
+int outbound_send(sph_handle *h, Outbound &o, std::initializer_list<OutboundCopy> copies) {
+    if (!o.done) HIPCHK(h, hipEventCreateWithFlags(&o.done, hipEventDisableTiming));
+    if (!o.copied) HIPCHK(h, hipEventCreateWithFlags(&o.copied, hipEventDisableTiming));
+    HIPCHK(h, hipEventRecord(o.done, h->compute));
+    HIPCHK(h, hipStreamWaitEvent(h->copy, o.done, 0));
+    for (const OutboundCopy &c : copies) HIPCHK(h, hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, h->copy));
+    HIPCHK(h, hipEventRecord(o.copied, h->copy));
+    o.pending = true;
+    return SPH_OK;
+}
+
+hipError_t outbound_wait(const Outbound &o) { return o.pending ? hipEventSynchronize(o.copied) : hipSuccess; }
+
 // the density sweep of the single domain and of a slab: counters on request, clean hit-stream cursors
 int launch_density(sph_handle *h, SweepArgs &A, hipStream_t stream) {
     if (h->opt.flags & SPH_FLAG_COUNT_PAIRS) A.pairCounter = h->pairCounter;

@@ -319,9 +319,3 @@ __device__ __forceinline__ int xcd_tile(int b, int nb, int C, int rot = 0) {
     return base + xcd * q + min(xcd, rem) + idx;
 }
 
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-

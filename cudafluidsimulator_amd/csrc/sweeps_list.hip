@@ -95,12 +95,6 @@ __device__ __forceinline__ uint32_t sl_quiet_window(const uint32_t *__restrict__
     return __builtin_amdgcn_alignbit(hi, lo, j & 31u);
 }
 
-__device__ __forceinline__ int wave_max_i32(int v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off));
-    return v;
-}
-
 // SAMECUT: the force cut-off P.cut2 (largest dist2 with sqrtf(dist2) <= h) equals h*h --
 // true for the reference's h = 0.1f.  The hit bit is then the sign of h2 - dist2, which the
 // density term needs anyway, and one v_alignbit_b32 shifts it in (miss = 1; the word is

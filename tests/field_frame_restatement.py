@@ -36,19 +36,8 @@ def scalar(vel, rho, field):
 
 def packed_buffers(pos, s, width=800, height=600, point_size=3):
     """(packed, count): per pixel the minimum of (bits(w) << 32) | bits(s) as uint64, and the hit count"""
-    packed = np.full(width * height, EMPTY64, np.uint64)
-    count = np.zeros(width * height, np.uint32)
-    px, py, wb = R.project(pos, width, height)
-    word = (wb.astype(np.uint64) << np.uint64(32)) | np.ascontiguousarray(s, dtype=F).view(np.uint32).astype(np.uint64)
-    r = (point_size - 1) // 2
-    for dy in range(-r, r + 1):
-        for dx in range(-r, r + 1):
-            x, y = px + dx, py + dy
-            ok = (x >= 0) & (x < width) & (y >= 0) & (y < height)
-            idx = y[ok] * width + x[ok]
-            np.minimum.at(packed, idx, word[ok])
-            np.add.at(count, idx, np.uint32(1))
-    return packed.reshape(height, width), count.reshape(height, width)
+    sb = np.ascontiguousarray(s, dtype=F).view(np.uint32).astype(np.uint64)
+    return R.splat(pos, lambda wb: (wb.astype(np.uint64) << np.uint64(32)) | sb, EMPTY64, np.uint64, width, height, point_size)
 
 
 def split(packed):

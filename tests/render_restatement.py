@@ -27,20 +27,27 @@ def project(pos, width, height):
     return px, py, np.ascontiguousarray(w).view(np.uint32)
 
 
-def particle_buffers(pos, width=800, height=600, point_size=3):
-    """(depth bits, count): two (height, width) uint32 arrays"""
-    depth = np.full(width * height, EMPTY, np.uint32)
+def splat(pos, word, empty, dtype, width, height, point_size):
+    """(minimum, count): per pixel the minimum of word(depth bits) over the particles whose square covers it
+    (`empty` where none does) as a (height, width) `dtype` array, and how many do as a uint32 one"""
+    least = np.full(width * height, empty, dtype)
     count = np.zeros(width * height, np.uint32)
     px, py, wb = project(pos, width, height)
+    w = word(wb)
     r = (point_size - 1) // 2
     for dy in range(-r, r + 1):
         for dx in range(-r, r + 1):
             x, y = px + dx, py + dy
             ok = (x >= 0) & (x < width) & (y >= 0) & (y < height)
             idx = y[ok] * width + x[ok]
-            np.minimum.at(depth, idx, wb[ok])
+            np.minimum.at(least, idx, w[ok])
             np.add.at(count, idx, np.uint32(1))
-    return depth.reshape(height, width), count.reshape(height, width)
+    return least.reshape(height, width), count.reshape(height, width)
+
+
+def particle_buffers(pos, width=800, height=600, point_size=3):
+    """(depth bits, count): two (height, width) uint32 arrays"""
+    return splat(pos, lambda wb: wb, EMPTY, np.uint32, width, height, point_size)
 
 
 def edge_points():

@@ -133,6 +133,36 @@ def test_aggregated_splat_equals_plain_splat(monkeypatch):
     sim.close()
 
 
+# the shapes test_gpu_field_frame.py holds the field splat to.  64 x 48: the whole image fits the LDS tile, every
+# workgroup aggregates; 800 x 600: a 1024-row workgroup of these 4096 particles spans far more than a tile, every
+# workgroup issues the per-hit atomics; one odd size
+PATH_CASES = [dict(width=64, height=48, point_size=1), dict(width=64, height=48, point_size=9),
+              dict(width=800, height=600, point_size=3), dict(width=333, height=77, point_size=3)]
+
+
+@pytest.mark.parametrize("steps", [0, 3])
+def test_paths_tile_fallback_and_plain(steps, monkeypatch):
+    data = np.load(os.path.join(GOLD, "random4096.npz"))
+
+    def handle():
+        sim = make(len(data["pos_1"]))
+        sim.upload_state(data["pos_1"], data["vel_1"])
+        for _ in range(steps):
+            sim.simulate()
+        return sim
+
+    monkeypatch.setenv("SPH_RENDER_PLAIN", "0")
+    sim = handle()
+    pos = sim.download_state()["pos"]
+    tiled = [check_against_restatement(sim, f"random4096 + {steps} steps", pos, shade="count", **case) for case in PATH_CASES]
+    sim.close()
+    monkeypatch.setenv("SPH_RENDER_PLAIN", "1")
+    twin = handle()  # a fresh handle: nothing of the tiled frames is left in its buffers
+    for case, a in zip(PATH_CASES, tiled):
+        assert_frame_equal(gpu_frame(twin, shade="count", **case), a, f"plain vs tiled, {steps} steps {case}")
+    twin.close()
+
+
 def test_same_image_from_every_sweep_and_key_order():
     n, steps = 32768, 5
     frames, poses = {}, {}
