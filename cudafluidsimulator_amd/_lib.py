@@ -26,6 +26,8 @@ EXPORTED_SYMBOLS = [
     "sph_render_frame", "sph_frame_host", "sph_download_frame_buffers", "sph_get_render_time", "sph_api_version",
     "sph_render_field", "sph_download_field_buffer", "sph_field_range",
     "sph_sample_field", "sph_sample_host", "sph_get_sample_time",
+    "sph_diagnose", "sph_diagnostics_host", "sph_diagnostics_values", "sph_diagnostics_add",
+    "sph_get_diagnostics_time", "sph_slab_diagnose",
 ]
 SPH_API_VERSION = 3
 SPH_SHADE_FLAT, SPH_SHADE_COUNT = 0, 1
@@ -34,6 +36,10 @@ SPH_HAS_FIELD_FRAME = 1
 SPH_FIELD_SPEED, SPH_FIELD_DENSITY, SPH_FIELD_PRESSURE = 0, 1, 2
 FIELDS = {"speed": SPH_FIELD_SPEED, "density": SPH_FIELD_DENSITY, "pressure": SPH_FIELD_PRESSURE}
 SPH_HAS_FIELD_SAMPLE = 1
+SPH_HAS_DIAGNOSTICS = 1
+DIAG_SUMS = ("x", "y", "z", "vx", "vy", "vz", "rho", "prs", "v2")   # SPH_DIAG_SUM_*
+DIAG_EXTREMA = ("x", "y", "z", "speed", "rho", "prs")               # SPH_DIAG_EXT_*
+DIAG_BINS = 256
 
 
 class SphError(RuntimeError):
@@ -73,6 +79,68 @@ class SphFieldFrameOptions(C.Structure):
 class SphSampleLattice(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32),
                 ("origin", C.c_float * 3), ("spacing", C.c_float * 3), ("field", C.c_int32)]
+
+
+class SphSum128(C.Structure):
+    _fields_ = [("lo", C.c_uint64), ("hi", C.c_int64)]
+
+
+class SphDiagnosticsOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("hist_field", C.c_int32),
+                ("value_lo", C.c_float), ("value_hi", C.c_float)]
+
+
+class SphDiagnosticsRaw(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("pad_", C.c_int32), ("n", C.c_int64),
+                ("sum", SphSum128 * 9), ("min_bits", C.c_uint32 * 6), ("max_bits", C.c_uint32 * 6),
+                ("saturated", C.c_uint64), ("hist_field", C.c_int32),
+                ("hist_lo_bits", C.c_uint32), ("hist_hi_bits", C.c_uint32), ("pad2_", C.c_int32),
+                ("hist", C.c_uint64 * DIAG_BINS)]
+
+
+class SphDiagnostics(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("pad_", C.c_int32), ("n", C.c_int64),
+                ("mass", C.c_double), ("com", C.c_double * 3), ("momentum", C.c_double * 3),
+                ("kinetic", C.c_double), ("potential", C.c_double),
+                ("mean_rho", C.c_double), ("mean_prs", C.c_double),
+                ("min_rho", C.c_double), ("max_rho", C.c_double),
+                ("max_speed", C.c_double), ("cfl", C.c_double),
+                ("box_min", C.c_double * 3), ("box_max", C.c_double * 3), ("saturated", C.c_uint64)]
+
+
+def diagnostics_options(hist=None, value_range=None):
+    """SphDiagnosticsOptions for a histogram of `hist` (a FIELDS name or SPH_FIELD_*; None: no histogram) over
+    value_range = (lo, hi) (None: the minimum and maximum of the field, reduced on the device)"""
+    o = SphDiagnosticsOptions()
+    o.struct_size = C.sizeof(SphDiagnosticsOptions)
+    o.hist_field = -1 if hist is None else FIELDS[hist] if isinstance(hist, str) else int(hist)
+    if value_range is not None:
+        o.value_lo, o.value_hi = float(value_range[0]), float(value_range[1])
+    return o
+
+
+def diagnostics_dict(raw, settings):
+    """The dict Simulator.diagnostics() returns, from the words `raw` (SphDiagnosticsRaw): the derived floats of
+    sph_diagnostics_values and, under "raw", the sums as Python ints (Q32.32: value = int / 2**32), the extrema as
+    float32, the histogram as an np.uint64 array and `saturated`."""
+    import numpy as np
+    v = SphDiagnostics()
+    rc = load_library().sph_diagnostics_values(C.byref(raw), C.byref(settings), C.byref(v))
+    if rc:
+        raise SphError(f"sph_diagnostics_values failed ({rc})")
+    out = dict(n=v.n, mass=v.mass, com=tuple(v.com), momentum=tuple(v.momentum), kinetic=v.kinetic,
+               potential=v.potential, mean_rho=v.mean_rho, mean_prs=v.mean_prs, min_rho=v.min_rho, max_rho=v.max_rho,
+               max_speed=v.max_speed, cfl=v.cfl, box_min=tuple(v.box_min), box_max=tuple(v.box_max),
+               saturated=v.saturated)
+    bits = lambda a: np.array(list(a), np.uint32).view(np.float32)
+    out["raw"] = dict(
+        n=raw.n,
+        sums={name: (raw.sum[k].hi << 64) | raw.sum[k].lo for k, name in enumerate(DIAG_SUMS)},
+        min=dict(zip(DIAG_EXTREMA, bits(raw.min_bits))), max=dict(zip(DIAG_EXTREMA, bits(raw.max_bits))),
+        saturated=raw.saturated, hist_field=raw.hist_field,
+        hist_range=tuple(bits([raw.hist_lo_bits, raw.hist_hi_bits])),
+        hist=np.array(list(raw.hist), np.uint64), struct=raw)
+    return out
 
 
 class SphKernelTimes(C.Structure):
@@ -153,5 +221,11 @@ def load_library():
     L.sph_sample_host.argtypes = [hp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.sph_sample_host.restype = fp
     L.sph_get_sample_time.argtypes = [hp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]
+    L.sph_diagnose.argtypes = [hp, C.POINTER(SphDiagnosticsOptions)]
+    L.sph_diagnostics_host.argtypes = [hp, C.POINTER(SphDiagnosticsRaw)]
+    L.sph_diagnostics_values.argtypes = [C.POINTER(SphDiagnosticsRaw), C.POINTER(SphSettings), C.POINTER(SphDiagnostics)]
+    L.sph_diagnostics_add.argtypes = [C.POINTER(SphDiagnosticsRaw), C.POINTER(SphDiagnosticsRaw)]
+    L.sph_get_diagnostics_time.argtypes = [hp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]
+    L.sph_slab_diagnose.argtypes = [hp, C.c_int, C.c_int, C.c_int, C.POINTER(SphDiagnosticsOptions)]
     _lib = L
     return L

@@ -10,6 +10,7 @@
 
 #include "sha256.h"
 #include "simulator.h"
+#include "sph_c_api.h"
 
 bool mouseClicked = false;
 int2 clickCoords;
@@ -91,6 +92,20 @@ static bool write_slice(Simulator *simulator, const char *dir, int f, int field)
     return (fclose(out) == 0) && ok;
 }
 
+// SPH_FREE_STATS=1: for each written frame one JSON line of run diagnostics (Simulator::diagnostics) in
+// <dir>/stats.jsonl; doubles as %.17g, which reads back to the same double
+static bool write_stats(Simulator *simulator, FILE *out, int f) {
+    SphDiagnostics d;
+    if (!simulator->diagnostics(&d)) return false;
+    fprintf(out,
+            "{\"frame\": %d, \"kinetic\": %.17g, \"potential\": %.17g, \"momentum\": [%.17g, %.17g, %.17g], "
+            "\"com\": [%.17g, %.17g, %.17g], \"max_speed\": %.17g, \"cfl\": %.17g, \"min_rho\": %.17g, "
+            "\"mean_rho\": %.17g, \"max_rho\": %.17g, \"saturated\": %llu}\n",
+            f, d.kinetic, d.potential, d.momentum[0], d.momentum[1], d.momentum[2], d.com[0], d.com[1], d.com[2], d.max_speed,
+            d.cfl, d.min_rho, d.mean_rho, d.max_rho, (unsigned long long)d.saturated);
+    return fflush(out) == 0;
+}
+
 void startVisualization(Simulator *simulator) {
     int frames = 100;
     if (const char *e = getenv("SPH_FREE_FRAMES")) frames = atoi(e);
@@ -100,6 +115,11 @@ void startVisualization(Simulator *simulator) {
     if (const char *e = getenv("SPH_FREE_FRAME_EVERY")) every = atoi(e) > 0 ? atoi(e) : 1;
     const int field = framesDir ? shade_field() : -1;
     int slice = framesDir ? env_field("SPH_FREE_SLICE", "writing no slices") : -1;
+    FILE *stats = NULL;
+    if (framesDir && getenv("SPH_FREE_STATS") && atoi(getenv("SPH_FREE_STATS")) != 0) {
+        const std::string path = std::string(framesDir) + "/stats.jsonl";
+        if (!(stats = fopen(path.c_str(), "w"))) fprintf(stderr, "sph: cannot write %s\n", path.c_str());
+    }
     fprintf(stderr, "sph: built without GLUT -- running %d frames headless\n", frames);
     for (int f = 0; f < frames; ++f) {
         if (f == frames / 2 && getenv("SPH_FREE_CLICK")) {
@@ -109,7 +129,12 @@ void startVisualization(Simulator *simulator) {
         simulator->simulate();
         if (framesDir && f % every == 0 && !write_frame(simulator, framesDir, f, field)) framesDir = NULL;
         if (framesDir && slice >= 0 && f % every == 0 && !write_slice(simulator, framesDir, f, slice)) slice = -1;
+        if (framesDir && stats && f % every == 0 && !write_stats(simulator, stats, f)) {
+            fclose(stats);
+            stats = NULL;
+        }
     }
+    if (stats) fclose(stats);
     const float3 *p = simulator->getPosition();
     if (p && simulator->settings->numParticles > 0)
         printf("particle 0 after %d frames: (%f, %f, %f)\n", frames, p[0].x, p[0].y, p[0].z);

@@ -455,6 +455,29 @@ int sph_mgpu_download_state(sph_mgpu *m, float *pos, float *vel, float *rho, int
     return SPH_OK;
 }
 
+int sph_mgpu_diagnostics(sph_mgpu *m, const SphDiagnosticsOptions *opt, SphDiagnosticsRaw *out) {
+    if (!m || !out) return SPH_EINVAL;
+    if (!m->ready) return fail(m, SPH_ESTATE, "setup()/upload_state() must come first");
+    if (m->poisoned) return m->poisonCode; // (err holds the message)
+    if (m->phase != 0) return fail(m, SPH_ESTATE, "diagnose between steps");
+    // every slab queues its reduction behind its last step (the owned rows: what gather_local copies) ...
+    for (auto &sl : m->slabs) {
+        HIPM(m, hipSetDevice(sl.device));
+        SPHM(m, sl, sph_slab_diagnose(sl.h, sl.cur, sl.off, sl.off + sl.n_own, opt));
+    }
+    // ... then the host waits for each and merges
+    bool first = true;
+    for (auto &sl : m->slabs) {
+        HIPM(m, hipSetDevice(sl.device));
+        SphDiagnosticsRaw part;
+        SPHM(m, sl, sph_diagnostics_host(sl.h, &part));
+        if (first) *out = part;
+        else if (sph_diagnostics_add(out, &part)) return fail(m, SPH_EHIP, "the slabs' diagnostics do not merge");
+        first = false;
+    }
+    return SPH_OK;
+}
+
 int sph_mgpu_get_stats(sph_mgpu *m, SphMgpuStats *out, int reset) {
     if (!m || !out) return SPH_EINVAL;
     PASS(sph_mgpu_sync(m));

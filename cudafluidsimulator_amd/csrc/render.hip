@@ -46,14 +46,7 @@ __device__ __forceinline__ Pixel project(float x, float y, float z, const Render
 // particle (the smallest among several at that depth).  A payload gives the per-pixel word, its "empty", the word of
 // particle i and the global buffer the minima go to.
 
-__device__ __forceinline__ uint32_t field_bits(const float4 v, int field) {
-    float s;
-    if (field == SPH_FIELD_SPEED) s = sqrtf((v.x * v.x + v.y * v.y) + v.z * v.z);
-    else if (field == SPH_FIELD_DENSITY) s = v.w;
-    else s = fmaxf(0.f, SPH_GAS_CONSTANT * (v.w - SPH_REST_DENSITY)); // as sph_download_state
-    return __float_as_uint(s);
-}
-
+// (field_bits, the scalar of a row: sph_device.h)
 __device__ __forceinline__ unsigned long long field_word(uint32_t wbits, uint32_t sbits) {
     return ((unsigned long long)wbits << 32) | sbits;
 }

@@ -171,6 +171,25 @@ const float *Simulator::sampleField(int field, const float origin[3], const floa
     return v;
 }
 
+bool Simulator::diagnostics(SphDiagnostics *out, SphDiagnosticsRaw *raw) {
+    if (!out || (!impl && !multi)) {
+        fprintf(stderr, "sph: diagnostics: setup() must come first\n");
+        return false;
+    }
+    SphDiagnosticsRaw r;
+    if (multi) {
+        mcheck(multi, sph_mgpu_diagnostics(multi, NULL, &r), "sph_mgpu_diagnostics");
+    } else {
+        check(impl, sph_diagnose(impl, NULL), "sph_diagnose");
+        check(impl, sph_diagnostics_host(impl, &r), "sph_diagnostics_host");
+    }
+    SphSettings s;
+    memcpy(&s, settings, sizeof s);
+    check(impl, sph_diagnostics_values(&r, &s, out), "sph_diagnostics_values");
+    if (raw) *raw = r;
+    return true;
+}
+
 void Simulator::moveParticles(int2 mouse_pos) {
     if (multi) { // multi-GPU: the impulse needs the slabs' grids of a step: it rides on the next simulate()
         mcheck(multi, sph_mgpu_queue_click(multi, mouse_pos.x, mouse_pos.y), "sph_mgpu_queue_click");

@@ -436,13 +436,16 @@ void sph_destroy(sph_handle *h) {
                     (void *)h->force4, (void *)h->pairCounter, (void *)h->pv8, (void *)h->maskPool, (void *)h->maskOff,
                     (void *)h->noneList, (void *)h->hitCount, (void *)h->maskCursor, (void *)h->quiet, (void *)h->quietVref,
                     (void *)h->calm, (void *)h->initPos4, (void *)h->rDepth, (void *)h->rCount, (void *)h->rEdge, (void *)h->rRgb,
-                    (void *)h->rPacked, (void *)h->rRange, (void *)h->boundsDev, (void *)h->partTiles, (void *)h->sampleDev})
+                    (void *)h->rPacked, (void *)h->rRange, (void *)h->boundsDev, (void *)h->partTiles, (void *)h->sampleDev,
+                    (void *)h->diagDev})
         if (p) (void)hipFree(p);
     for (void *p : {(void *)h->hostPos, (void *)h->stage[0], (void *)h->stage[1], (void *)h->pairHost, (void *)h->oobHost,
-                    (void *)h->frameHost, (void *)h->rangeHost, (void *)h->boundsHost, (void *)h->sampleHost})
+                    (void *)h->frameHost, (void *)h->rangeHost, (void *)h->boundsHost, (void *)h->sampleHost,
+                    (void *)h->diagHost})
         if (p) (void)hipHostFree(p);
     for (hipEvent_t e : {h->computeDone[0], h->computeDone[1], h->copyDone[0], h->copyDone[1], h->stageFree[0], h->stageFree[1],
-                         h->frameOut.done, h->frameOut.copied, h->sampleOut.done, h->sampleOut.copied})
+                         h->frameOut.done, h->frameOut.copied, h->sampleOut.done, h->sampleOut.copied, h->diagOut.done,
+                         h->diagOut.copied})
         if (e) (void)hipEventDestroy(e);
     for (auto &se : h->ring) {
         for (auto &e : se.e) if (e) (void)hipEventDestroy(e);

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sph_c_api.h"
+
 #define SPH_WAVE 64
 
 // Physics constants of the reference (simulator.h:6-12, simulator.cu:13-14).
@@ -236,6 +238,16 @@ void sph_launch_render_field(const RenderParams &R, const float4 *pos4, const fl
                             bool autoRange, float lo, float hi, unsigned long long *packed, uint32_t *depth, uint32_t *count,
                             const uint32_t *edge, uint32_t *range, uint32_t *rgb, hipStream_t s);
 
+// The bits of the field frame's scalar of a row, from the (vx, vy, vz, rho) sph_download_state
+// reads: what the field frame colours by and the diagnostics reduce.  fp32, every operation rounded on its own.
+__device__ __forceinline__ uint32_t field_bits(const float4 v, int field) {
+    float s;
+    if (field == SPH_FIELD_SPEED) s = sqrtf((v.x * v.x + v.y * v.y) + v.z * v.z);
+    else if (field == SPH_FIELD_DENSITY) s = v.w;
+    else s = fmaxf(0.f, SPH_GAS_CONSTANT * (v.w - SPH_REST_DENSITY)); // as sph_download_state
+    return __float_as_uint(s);
+}
+
 // ---- the field sample (sample.hip; defined in DESIGN.md section 10b) ----
 struct SampleArgs {
     int nx, ny, nz;          // lattice points per axis; point (ix, iy, iz) -> out[(iz ny + iy) nx + ix]
@@ -250,3 +262,27 @@ struct SampleArgs {
 };
 // one value per lattice point into out[0, nx ny nz); plain = the one-thread-per-point check path
 void sph_launch_sample(const DevParams &P, const SampleArgs &A, bool plain, float *out, hipStream_t s);
+
+// ---- diagnostics (diag.hip; defined in DESIGN.md section 10c) ----
+// The result block on the device: every word an integer, written by integer atomics only.
+struct DiagBlock {
+    unsigned long long lo[SPH_DIAG_SUMS]; // sum of q & 0xFFFFFFFF per sum
+    long long hi[SPH_DIAG_SUMS];          // sum of q >> 32 (arithmetic)
+    unsigned long long saturated;
+    uint32_t minKey[SPH_DIAG_EXTREMA];    // ordering keys, not bit patterns (identities: 0xFFFFFFFF / 0)
+    uint32_t maxKey[SPH_DIAG_EXTREMA];
+    uint32_t range[2];                    // bits of the histogram's lo / hi (given, or filled in from the keys)
+    uint32_t pad[2];
+    unsigned long long hist[SPH_DIAG_BINS];
+};
+struct DiagArgs {
+    const float4 *pos;  // row j: pos[j stride] = (x, y, z, id) and vel[j stride] = (vx, vy, vz, rho)
+    const float4 *vel;
+    int stride;
+    int n;              // rows
+    int histField;      // SPH_FIELD_*, -1 = no histogram
+    int autoRange;      // the histogram's range is the reduced minimum / maximum of its scalar
+    float lo, hi;       // ... else this one
+};
+// clear + reduce (+ histogram) into *blk; plain = the one-thread-per-row, one-atomic-per-term check path
+void sph_launch_diagnose(const DiagArgs &A, bool plain, DiagBlock *blk, hipStream_t s);

@@ -1,5 +1,5 @@
 // The handle behind include/sph_c_api.h and the few helpers its host translation units share (sph_api.hip,
-// sph_step.hip, sph_readback.hip, sph_slab.hip, sph_snapshot.hip, sph_frame.hip, sph_sample.hip).  Host code only.
+// sph_step.hip, sph_readback.hip, sph_slab.hip, sph_snapshot.hip, sph_frame.hip, sph_sample.hip, sph_diag.hip).  Host code only.
 #pragma once
 
 #include "sph_c_api.h"
@@ -176,6 +176,18 @@ struct sph_handle {
     double sampleSeconds = 0;        // the sampling kernel, from HIP events (PairEvent ring)
     long long sampleCount = 0;
     long long sampleTileCalls = 0, samplePlainCalls = 0; // which kernel ran (SPH_STEP_TRACE=1: printed by sph_destroy)
+
+    // ---- sph_diag.hip ----
+    // Run diagnostics (diag.hip): the small result block on the device and in pinned memory, allocated by the
+    // first sph_diagnose / sph_slab_diagnose.
+    DiagBlock *diagDev = nullptr, *diagHost = nullptr;
+    sph_host::Outbound diagOut;      // the block on its way to diagHost
+    bool diagValid = false;
+    int diagN = 0;                   // rows of the last call
+    SphDiagnosticsOptions diagOpt{}; // ... its options
+    bool diagAuto = false;           // ... and whether its histogram took the reduced range
+    double diagSeconds = 0;          // clear + reduce + histogram, from HIP events (PairEvent ring)
+    long long diagCount = 0;
 };
 
 #define HIPCHK(h, call)                                                               \

@@ -27,6 +27,7 @@ EXPORTED_SYMBOLS = [
     "sph_mgpu_upload_state", "sph_mgpu_step", "sph_mgpu_step_phase", "sph_mgpu_positions_host",
     "sph_mgpu_download_state",
     "sph_mgpu_sync", "sph_mgpu_get_stats", "sph_mgpu_last_error", "sph_mgpu_queue_click",
+    "sph_mgpu_diagnostics",
 ]
 
 
@@ -78,6 +79,7 @@ def load_mgpu_library():
     L.sph_mgpu_sync.argtypes = [hp]
     L.sph_mgpu_queue_click.argtypes = [hp, C.c_int, C.c_int]
     L.sph_mgpu_get_stats.argtypes = [hp, C.POINTER(SphMgpuStats), C.c_int]
+    L.sph_mgpu_diagnostics.argtypes = [hp, C.POINTER(_lib.SphDiagnosticsOptions), C.POINTER(_lib.SphDiagnosticsRaw)]
     L.sph_mgpu_last_error.argtypes = [hp]
     L.sph_mgpu_last_error.restype = C.c_char_p
     _lib_mgpu = L
@@ -188,6 +190,19 @@ class MultiGpuSimulator:
         self._check(self._L.sph_mgpu_download_state(self._h, _fp(pos), _fp(vel), _fp(rho), C.byref(w)),
                     "sph_mgpu_download_state")
         return dict(pos=pos, vel=vel, rho=rho, written=w.value)
+
+    def diagnostics_raw(self, hist=None, value_range=None):
+        """The words of the LOCAL slabs' rows as an SphDiagnosticsRaw (sph_mgpu_diagnostics); between steps, blocks.
+        One process per GPU: merge the ranks' structs with sph_diagnostics_add."""
+        o = _lib.diagnostics_options(hist, value_range)
+        raw = _lib.SphDiagnosticsRaw()
+        self._check(self._L.sph_mgpu_diagnostics(self._h, C.byref(o), C.byref(raw)), "sph_mgpu_diagnostics")
+        return raw
+
+    def diagnostics(self, hist=None, value_range=None):
+        """Simulator.diagnostics() of the run: the same dict, the same words whatever the number of slabs.  A
+        histogram needs an explicit value_range."""
+        return _lib.diagnostics_dict(self.diagnostics_raw(hist, value_range), self.settings)
 
     def sync(self):
         self._check(self._L.sph_mgpu_sync(self._h), "sph_mgpu_sync")

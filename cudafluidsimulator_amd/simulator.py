@@ -254,6 +254,34 @@ class Simulator:
                     "sph_get_sample_time")
         return sec.value, cnt.value
 
+    # -- run diagnostics: exact sums, extrema and a histogram, reduced on the device (sph_diagnose) --
+    def diagnose(self, hist=None, value_range=None):
+        """Queue the reduction of the current state (sph_diagnose); does not block."""
+        o = _lib.diagnostics_options(hist, value_range)
+        self._check(self._L.sph_diagnose(self._h, C.byref(o)), "sph_diagnose")
+
+    def diagnostics_raw(self):
+        """The words of the last diagnose() as an SphDiagnosticsRaw; blocks until they have landed."""
+        raw = _lib.SphDiagnosticsRaw()
+        self._check(self._L.sph_diagnostics_host(self._h, C.byref(raw)), "sph_diagnostics_host")
+        return raw
+
+    def diagnostics(self, hist=None, value_range=None):
+        """Mass, centre of mass, momentum, kinetic and potential energy, mean / min / max density, mean pressure,
+        the fastest particle, the CFL number and the box of the particles of the current state as Python floats,
+        and under "raw" the exact words behind them (sums as Python ints in Q32.32, extrema as float32,
+        `saturated`).  hist = "speed" | "density" | "pressure" adds raw["hist"], 256 np.uint64 counts over
+        value_range = (lo, hi), or over the field's own minimum and maximum (raw["hist_range"])."""
+        self.diagnose(hist, value_range)
+        return _lib.diagnostics_dict(self.diagnostics_raw(), self.settings)
+
+    def diagnostics_time(self, reset=False):
+        """(seconds, calls): GPU time of the diagnostics launches summed over `calls` calls."""
+        sec, cnt = C.c_double(0), C.c_int64(0)
+        self._check(self._L.sph_get_diagnostics_time(self._h, C.byref(sec), C.byref(cnt), 1 if reset else 0),
+                    "sph_get_diagnostics_time")
+        return sec.value, cnt.value
+
     def phase(self, name):
         self._check(getattr(self._L, "sph_phase_" + name)(self._h), "sph_phase_" + name)
 

@@ -64,6 +64,8 @@ struct Particle {
 
 struct sph_handle;
 struct sph_mgpu;
+struct SphDiagnostics;    // include/sph_c_api.h
+struct SphDiagnosticsRaw;
 
 class Simulator {
   private:
@@ -97,6 +99,11 @@ class Simulator {
     // until the next call.  NULL (with a message on stderr) with SPH_GPUS > 1 and where the library answers
     // SPH_ESTATE (SPH_SWEEP=linked has no cell table to walk).
     const float *sampleField(int field, const float origin[3], const float spacing[3], int nx, int ny, int nz);
+    // Run diagnostics of the current state, reduced on the GPU (sph_diagnose in sph_c_api.h): total kinetic and
+    // potential energy, momentum, centre of mass, the fastest particle, the CFL number, the spread of density.
+    // *raw, if given, receives the exact words behind them.  With SPH_GPUS > 1 through the multi-GPU driver
+    // (sph_mgpu_diagnostics): the same words.  False (with a message on stderr) before setup().
+    bool diagnostics(SphDiagnostics *out, SphDiagnosticsRaw *raw = nullptr);
 };
 
 #endif

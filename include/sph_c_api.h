@@ -428,6 +428,95 @@ const float *sph_sample_host(sph_handle *h, int *nx, int *ny, int *nz);
  * the step that consumes it), summed over `samples` calls. */
 int sph_get_sample_time(sph_handle *h, double *seconds, int64_t *samples, int reset);
 
+/* ---- run diagnostics: exact sums, extrema and a histogram of the state, reduced on the device ----
+ * Additive to version 3: test for SPH_HAS_DIAGNOSTICS.  Defined to the bit in DESIGN.md section 10c ("Diagnostics").
+ * The rows are those sph_render_field reads, (x, y, z, vx, vy, vz, rho) per particle as sph_download_state returns
+ * them; speed and prs are the field frame's scalars.  Every sum is a sum of signed 64-bit Q32.32 terms
+ * q(t) = (int64)floor(t 2^32) of the double t (NaN: 0; t >= 2^31: INT64_MAX; t < -2^31: INT64_MIN; `saturated` counts
+ * the terms that took one of those three branches), accumulated in integers only and reported as a 128-bit two's
+ * complement value: the words depend on the SET of rows, not on their order, the launch shape or the number of slabs.
+ * The term of the first eight sums is the fp32 value widened to double, that of V2 is ((double)vx vx + (double)vy vy)
+ * + (double)vz vz.  Extrema are fp32 bit patterns ordered by the key b ^ ((b >> 31) ? 0xFFFFFFFF : 0x80000000):
+ * -0 < +0, a NaN sorts where its bits put it; no rows: min_bits = 0x7F800000, max_bits = 0xFF800000. */
+#define SPH_HAS_DIAGNOSTICS 1
+enum { /* indices of SphDiagnosticsRaw.sum */
+    SPH_DIAG_SUM_X = 0, SPH_DIAG_SUM_Y = 1, SPH_DIAG_SUM_Z = 2,
+    SPH_DIAG_SUM_VX = 3, SPH_DIAG_SUM_VY = 4, SPH_DIAG_SUM_VZ = 5,
+    SPH_DIAG_SUM_RHO = 6, SPH_DIAG_SUM_PRS = 7, SPH_DIAG_SUM_V2 = 8,
+    SPH_DIAG_SUMS = 9
+};
+enum { /* indices of SphDiagnosticsRaw.min_bits / max_bits */
+    SPH_DIAG_EXT_X = 0, SPH_DIAG_EXT_Y = 1, SPH_DIAG_EXT_Z = 2,
+    SPH_DIAG_EXT_SPEED = 3, SPH_DIAG_EXT_RHO = 4, SPH_DIAG_EXT_PRS = 5,
+    SPH_DIAG_EXTREMA = 6
+};
+#define SPH_DIAG_BINS 256
+typedef struct SphSum128 { /* lo + 2^64 hi: a two's complement sum of Q32.32 terms; its value is that times 2^-32 */
+    uint64_t lo;
+    int64_t hi;
+} SphSum128;
+typedef struct SphDiagnosticsOptions {
+    int32_t struct_size; /* = sizeof(SphDiagnosticsOptions) */
+    int32_t hist_field;  /* SPH_FIELD_* of the histogram, -1 = none */
+    float value_lo;      /* the 256 bins are the field frame's q over value_lo .. value_hi; both 0: the minimum and */
+    float value_hi;      /* maximum (by the key above) of the scalar over this call's rows, taken on the device */
+} SphDiagnosticsOptions;
+typedef struct SphDiagnosticsRaw {
+    int32_t struct_size; /* = sizeof(SphDiagnosticsRaw) */
+    int32_t pad_;        /* 0 */
+    int64_t n;           /* rows */
+    SphSum128 sum[SPH_DIAG_SUMS];
+    uint32_t min_bits[SPH_DIAG_EXTREMA];
+    uint32_t max_bits[SPH_DIAG_EXTREMA];
+    uint64_t saturated;
+    int32_t hist_field;    /* -1: no histogram (hist is all zero, the range words are 0) */
+    uint32_t hist_lo_bits; /* the range the bins were cut over (the options' or the reduced one), fp32 bit patterns */
+    uint32_t hist_hi_bits;
+    int32_t pad2_;         /* 0 */
+    uint64_t hist[SPH_DIAG_BINS];
+} SphDiagnosticsRaw;
+/* The derived values (DESIGN.md section 10c gives every expression; Python floats reproduce them bit for bit). */
+typedef struct SphDiagnostics {
+    int32_t struct_size; /* = sizeof(SphDiagnostics) */
+    int32_t pad_;
+    int64_t n;
+    double mass;         /* n MASS */
+    double com[3];       /* centre of mass; 0 without rows, like every quotient by n */
+    double momentum[3];  /* MASS sum(v) */
+    double kinetic;      /* 0.5 MASS sum(v^2) */
+    double potential;    /* MASS 9.8 sum(y) (the constant is -GRAVITY) */
+    double mean_rho, mean_prs;
+    double min_rho, max_rho;
+    double max_speed;
+    double cfl;          /* max_speed timestep / h */
+    double box_min[3], box_max[3]; /* the box of the particles */
+    uint64_t saturated;
+} SphDiagnostics;
+/* Queues the reduction of the state the handle holds NOW (the rows sph_render_field reads), the optional histogram
+ * behind it and the copy of the small result block to pinned memory, on the handle's streams; does not block.
+ * opt == NULL: no histogram.  State rules of sph_render_field: SPH_ESTATE before any state and for
+ * SPH_FLAG_EXTERNAL_STATE handles; works with SPH_FLAG_NO_READBACK, with every sweep (SPH_SWEEP_LINKED included)
+ * and both key orders, between the phases of a split step too: it needs no grid and builds none, and no result of
+ * any step changes.  SPH_EINVAL: an unknown hist_field, and with a histogram a non-finite value_lo / value_hi or
+ * value_hi < value_lo.  SPH_DIAG_PLAIN=1 in the environment selects the check path (one thread per row, every term a
+ * global integer atomic; identical words). */
+int sph_diagnose(sph_handle *h, const SphDiagnosticsOptions *opt);
+/* The words of the last sph_diagnose / sph_slab_diagnose.  Blocks until the copy has landed.  SPH_ESTATE before the
+ * first one. */
+int sph_diagnostics_host(sph_handle *h, SphDiagnosticsRaw *out);
+/* Pure host code, no GPU and no handle: the derived values of `raw` for a run with `settings` (h, timestep). */
+int sph_diagnostics_values(const SphDiagnosticsRaw *raw, const SphSettings *settings, SphDiagnostics *out);
+/* Pure host code: merges `part` into `into` -- 128-bit adds, key-ordered minima and maxima, histogram adds -- the way
+ * slabs, and the ranks of a one-process-per-GPU run, combine.  SPH_EINVAL when the two histogram fields or ranges
+ * differ. */
+int sph_diagnostics_add(SphDiagnosticsRaw *into, const SphDiagnosticsRaw *part);
+/* GPU time of the diagnostics launches (HIP events on the compute stream), summed over `calls` calls. */
+int sph_get_diagnostics_time(sph_handle *h, double *seconds, int64_t *calls, int reset);
+/* The same kernels over the rows [i_begin, i_end) of buffer pair `buf` of a slab handle, on the handle's stream; read
+ * the result with sph_diagnostics_host.  An automatic histogram range is SPH_EINVAL: a slab cannot know the global
+ * range. */
+int sph_slab_diagnose(sph_handle *h, int buf, int i_begin, int i_end, const SphDiagnosticsOptions *opt);
+
 const char *sph_build_info(void);
 
 #ifdef __cplusplus

@@ -117,6 +117,13 @@ const float *sph_mgpu_positions_host(sph_mgpu *m);
 /* particle-id order; only rows of locally owned particles are written.  Returns the
  * number of rows written through *written (may be NULL). */
 int sph_mgpu_download_state(sph_mgpu *m, float *pos_xyz, float *vel_xyz, float *rho, int *written);
+/* Run diagnostics of the whole run (sph_diagnose in sph_c_api.h): every local slab reduces the
+ * rows it owns (sph_slab_diagnose), the host waits and merges the parts with sph_diagnostics_add.  The words are those
+ * of the single domain, whatever the number of slabs: the sums are integer sums.  Call it between steps; it blocks.
+ * With one process per GPU the result covers the LOCAL slabs only: the caller merges the ranks' structs with
+ * sph_diagnostics_add.  A histogram needs an explicit range (value_lo, value_hi not both 0): SPH_EINVAL otherwise.
+ * Adds no message to the step and changes no phase of it.  opt == NULL: no histogram. */
+int sph_mgpu_diagnostics(sph_mgpu *m, const SphDiagnosticsOptions *opt, SphDiagnosticsRaw *out);
 int sph_mgpu_sync(sph_mgpu *m);
 int sph_mgpu_get_stats(sph_mgpu *m, SphMgpuStats *out, int reset);
 const char *sph_mgpu_last_error(const sph_mgpu *m); /* m may be NULL: create errors */
