@@ -25,6 +25,7 @@
 
 #include "mgpu_plan.h"
 #include "sph_mgpu.h"
+#include "sph_owned.h"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -41,6 +42,10 @@
 
 namespace mgpu_host {
 
+using sph_owned::DeviceBuf;
+using sph_owned::Event;
+using sph_owned::PinnedBuf;
+
 struct F4 { float x, y, z, w; };
 
 // The slab's pinned host words: what the step's one synchronisation reads, and the outgoing status word.
@@ -54,7 +59,8 @@ struct Pinned {
 static_assert(sizeof(Pinned) == 128 && offsetof(Pinned, rx) == 32 && offsetof(Pinned, sort) == 96 &&
                   offsetof(Pinned, status) == 124, "own Hdr (8 ints) | rx Hdr x2 (16) | sort bounds (4) | pad | status");
 
-// What alloc_slab makes and free_slab resets wholesale.
+// What alloc_slab makes and free_slab resets wholesale: assigning SlabResources{} releases every buffer and event
+// (the handle and the streams: free_slab itself).
 struct SlabResources {
     int zlo = 0, zhi = 0;
     bool has_dn = false, has_up = false;
@@ -63,19 +69,19 @@ struct SlabResources {
     hipStream_t comm = nullptr;   // exchange B overlaps the interior force sweep
     hipStream_t bnd = nullptr;    // the boundary layers' force sweep (joins the interior's launch)
     hipStream_t copy = nullptr;   // position read-back
-    hipEvent_t evDensity = nullptr, evB = nullptr, evBnd = nullptr, evForce = nullptr, evCopy = nullptr;
-    hipEvent_t evT[3] = {nullptr, nullptr, nullptr}; // step start, grid done, force done (the timed ones)
-    hipEvent_t evTx[2] = {nullptr, nullptr};         // STREAMS transport: [compute, exchange] stream reached its sends
-    hipEvent_t evRx[2] = {nullptr, nullptr};         //                    ... its receives have landed
-    F4 *pos[2] = {nullptr, nullptr}, *vel[2] = {nullptr, nullptr};
-    F4 *rx_pos[2] = {nullptr, nullptr}, *rx_vel[2] = {nullptr, nullptr}; // [0] from below, [1] from above
-    F4 *ex_pos[2] = {nullptr, nullptr}, *ex_vel[2] = {nullptr, nullptr}; // overflow messages (rare)
+    Event evDensity, evB, evBnd, evForce, evCopy; // (without timing)
+    Event evT[3];                 // step start, grid done, force done (the timed ones)
+    Event evTx[2];                // STREAMS transport: [compute, exchange] stream reached its sends (without timing)
+    Event evRx[2];                //                    ... its receives have landed
+    DeviceBuf<F4> pos[2], vel[2];
+    DeviceBuf<F4> rx_pos[2], rx_vel[2]; // [0] from below, [1] from above
+    DeviceBuf<F4> ex_pos[2], ex_vel[2]; // overflow messages (rare: ensure_extra)
     int ex_cap[2] = {0, 0};
-    Hdr *hdr_tx = nullptr;        // device
-    Hdr *hdr_rx = nullptr;        // device [2]
-    int *sortb = nullptr;         // device: bounds of the combined sort (5 ints)
-    Pinned *pinned = nullptr;     // host
-    F4 *hostRows = nullptr;       // pinned: owned pos4 rows of the last step
+    DeviceBuf<Hdr> hdr_tx;
+    DeviceBuf<Hdr> hdr_rx;        // [2]
+    DeviceBuf<int> sortb;         // bounds of the combined sort (5 ints)
+    PinnedBuf<Pinned> pinned;
+    PinnedBuf<F4> hostRows;       // owned pos4 rows of the last step
     int hostRowsCount = 0;
     bool rowsStale = true;        // hostRows does not hold the owned rows (fresh upload, re-cut): refill on demand
     bool copyPending = false;

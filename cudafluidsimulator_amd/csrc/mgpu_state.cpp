@@ -56,36 +56,14 @@ int layer_of(const sph_mgpu *m, float z) {
     return std::min(std::max(c, 0), m->D - 1);
 }
 
-// The lists alloc_slab and free_slab walk: the events without timing (evT[] are the timed ones) ...
-std::vector<hipEvent_t *> untimed_events(Slab &sl) {
-    return {&sl.evDensity, &sl.evB, &sl.evBnd, &sl.evForce, &sl.evCopy, &sl.evTx[0], &sl.evTx[1], &sl.evRx[0], &sl.evRx[1]};
-}
-// ... and the buffer pairs with the rows alloc_slab gives each of the two (none: the overflow round's, see ensure_extra)
-struct BufferPair { F4 **buf; size_t rows; };
-std::vector<BufferPair> buffers_of(Slab &sl, size_t cap, size_t F) {
-    return {{sl.pos, cap}, {sl.vel, cap}, {sl.rx_pos, F}, {sl.rx_vel, F}, {sl.ex_pos, 0}, {sl.ex_vel, 0}};
-}
-
 // Release the slab's resources; its identity (rank, device, communicator) stays.
 void free_slab(Slab &sl) {
     (void)hipSetDevice(sl.device);
     if (sl.h) sph_destroy(sl.h);
-    for (const BufferPair &p : buffers_of(sl, 0, 0))
-        for (int b = 0; b < 2; ++b)
-            if (p.buf[b]) (void)hipFree(p.buf[b]);
-    if (sl.hdr_tx) (void)hipFree(sl.hdr_tx);
-    if (sl.hdr_rx) (void)hipFree(sl.hdr_rx);
-    if (sl.sortb) (void)hipFree(sl.sortb);
-    if (sl.pinned) (void)hipHostFree(sl.pinned);
-    if (sl.hostRows) (void)hipHostFree(sl.hostRows);
-    for (hipEvent_t *e : untimed_events(sl))
-        if (*e) (void)hipEventDestroy(*e);
-    for (hipEvent_t e : sl.evT)
-        if (e) (void)hipEventDestroy(e);
     if (sl.comm) (void)hipStreamDestroy(sl.comm);
     if (sl.bnd) (void)hipStreamDestroy(sl.bnd);
     if (sl.copy) (void)hipStreamDestroy(sl.copy);
-    static_cast<SlabResources &>(sl) = SlabResources{};
+    static_cast<SlabResources &>(sl) = SlabResources{}; // (every buffer and event)
 }
 
 // (Re)build the slabs' buffers for capacity m->cap / face capacity m->F.
@@ -100,22 +78,26 @@ int alloc_slab(sph_mgpu *m, Slab &sl) {
     o.capacity = m->cap;
     int rc = sph_create(&m->settings, &o, &sl.h);
     if (rc) return fail(m, rc, std::string("sph_create: ") + sph_last_error(nullptr));
-    for (int b = 0; b < 2; ++b)
-        for (const BufferPair &p : buffers_of(sl, (size_t)m->cap, (size_t)m->F)) {
-            if (p.rows) HIPM(m, hipMalloc(&p.buf[b], p.rows * sizeof(F4)));
-            if (p.buf == sl.pos || p.buf == sl.vel) HIPM(m, hipMemset(p.buf[b], 0, p.rows * sizeof(F4))); // (the state)
+    for (int b = 0; b < 2; ++b) { // (the overflow round's ex_pos / ex_vel: ensure_extra, when one comes)
+        for (DeviceBuf<F4> *state : {&sl.pos[b], &sl.vel[b]}) {
+            if (m->cap) HIPM(m, state->alloc((size_t)m->cap));
+            HIPM(m, hipMemset(*state, 0, (size_t)m->cap * sizeof(F4)));
         }
+        if (m->F) HIPM(m, sl.rx_pos[b].alloc((size_t)m->F));
+        if (m->F) HIPM(m, sl.rx_vel[b].alloc((size_t)m->F));
+    }
     SPHM(m, sl, sph_bind_buffers(sl.h, sl.pos[0], sl.vel[0], sl.pos[1], sl.vel[1], m->cap));
-    HIPM(m, hipMalloc(&sl.hdr_tx, sizeof(Hdr)));
-    HIPM(m, hipMalloc(&sl.hdr_rx, 2 * sizeof(Hdr)));
-    HIPM(m, hipMalloc(&sl.sortb, 8 * sizeof(int)));
+    HIPM(m, sl.hdr_tx.alloc(1));
+    HIPM(m, sl.hdr_rx.alloc(2));
+    HIPM(m, sl.sortb.alloc(8));
     HIPM(m, hipMemset(sl.hdr_tx, 0, sizeof(Hdr)));
     HIPM(m, hipMemset(sl.hdr_rx, 0, 2 * sizeof(Hdr)));
-    HIPM(m, hipHostMalloc(&sl.pinned, sizeof(Pinned), hipHostMallocDefault));
+    HIPM(m, sl.pinned.alloc(1));
     *sl.pinned = Pinned{};
-    HIPM(m, hipHostMalloc(&sl.hostRows, (size_t)m->cap * sizeof(F4), hipHostMallocDefault));
-    for (hipEvent_t *e : untimed_events(sl)) HIPM(m, hipEventCreateWithFlags(e, hipEventDisableTiming));
-    for (auto &e : sl.evT) HIPM(m, hipEventCreate(&e));
+    HIPM(m, sl.hostRows.alloc((size_t)m->cap));
+    for (Event *e : {&sl.evDensity, &sl.evB, &sl.evBnd, &sl.evForce, &sl.evCopy, &sl.evTx[0], &sl.evTx[1], &sl.evRx[0], &sl.evRx[1]})
+        HIPM(m, e->create(hipEventDisableTiming));
+    for (auto &e : sl.evT) HIPM(m, e.create());
     HIPM(m, hipStreamCreateWithFlags(&sl.copy, hipStreamNonBlocking));
     if (m->shared_stream) {
         SPHM(m, sl, sph_set_stream(sl.h, m->shared));

@@ -38,12 +38,10 @@ void payload_rows(const sph_mgpu *m, const Slab &sl, int which, int a, int b, in
 
 int ensure_extra(sph_mgpu *m, Slab &sl, int which, int rows) {
     if (rows <= sl.ex_cap[which]) return SPH_OK;
-    if (sl.ex_pos[which]) (void)hipFree(sl.ex_pos[which]);
-    if (sl.ex_vel[which]) (void)hipFree(sl.ex_vel[which]);
-    sl.ex_pos[which] = sl.ex_vel[which] = nullptr;
     const int capr = rows + rows / 4 + 1024;
-    HIPM(m, hipMalloc(&sl.ex_pos[which], (size_t)capr * sizeof(F4)));
-    HIPM(m, hipMalloc(&sl.ex_vel[which], (size_t)capr * sizeof(F4)));
+    sl.ex_cap[which] = 0;
+    HIPM(m, sl.ex_pos[which].alloc((size_t)capr));
+    HIPM(m, sl.ex_vel[which].alloc((size_t)capr));
     sl.ex_cap[which] = capr;
     return SPH_OK;
 }

@@ -32,6 +32,21 @@ float force_cut2(float h) {
     return x;
 }
 
+// every SPH_* knob read at create (the list: sph_handle.h, above Knobs)
+Knobs read_knobs() {
+    Knobs k;
+    if (const char *e = getenv("SPH_SLIM_DIV")) k.slimDiv = atoi(e);
+    if (const char *e = getenv("SPH_PIPELINE")) k.pipeline = atoi(e) != 0;
+    if (const char *e = getenv("SPH_MASK_POOL_WORDS")) k.maskPoolSet = true, k.maskPoolQuads = strtoull(e, nullptr, 10) / 4;
+    if (const char *e = getenv("SPH_ZERO_PAIR_FILTER")) k.zeroPairFilter = atoi(e) != 0;
+    if (const char *e = getenv("SPH_PREWARM_COPIES")) k.prewarmCopies = atoi(e);
+    if (const char *e = getenv("SPH_TILE_CHUNK")) k.tileChunk = atoi(e); // tuning studies
+    if (const char *e = getenv("SPH_XCD_ROTATE")) k.xcdRotate = atoi(e);
+    if (const char *e = getenv("SPH_STEP_TRACE")) k.stepTrace = atoi(e) != 0;
+    if (const char *e = getenv("SPH_READBACK_SDMA")) k.readbackSdma = atoi(e) != 0;
+    return k;
+}
+
 void fill_params(sph_handle *h) {
     const SphSettings &s = h->settings;
     DevParams &P = h->P;
@@ -52,7 +67,7 @@ void fill_params(sph_handle *h) {
         SphSettings ref{};
         sph_default_settings(&ref, s.numParticles, s.randomInit);
         P.slimDiv = (s.h == ref.h && s.v_kernel_coeff == ref.v_kernel_coeff && s.d_kernel_coeff == ref.d_kernel_coeff) ? 1 : 0;
-        if (const char *e = getenv("SPH_SLIM_DIV")) if (atoi(e) == 0) P.slimDiv = 0;
+        if (h->knobs.slimDiv == 0) P.slimDiv = 0;
     }
     if (P.morton) {
         int b = 0;
@@ -117,46 +132,52 @@ int alloc_device(sph_handle *h) {
     const size_t posCap = h->external ? 1 : cap; // id-ordered read-back is single-domain only
     for (int b = 0; b < 2; ++b) {
         if (!h->external) {
-            HIPCHK(h, hipMalloc(&h->pos4[b], cap * sizeof(float4)));
-            HIPCHK(h, hipMalloc(&h->vel4[b], cap * sizeof(float4)));
+            HIPCHK(h, h->posBuf[b].alloc(cap));
+            HIPCHK(h, h->velBuf[b].alloc(cap));
+            h->pos4[b] = h->posBuf[b];
+            h->vel4[b] = h->velBuf[b];
             // never hand uninitialised indices to a gather, whatever happens upstream
             HIPCHK(h, hipMemset(h->pos4[b], 0, cap * sizeof(float4)));
             HIPCHK(h, hipMemset(h->vel4[b], 0, cap * sizeof(float4)));
         }
-        HIPCHK(h, hipMalloc(&h->ws.keys[b], cap * sizeof(uint32_t)));
-        HIPCHK(h, hipMalloc(&h->ws.vals[b], cap * sizeof(uint32_t)));
-        if (!(h->opt.flags & SPH_FLAG_MAPPED_POSITIONS))
-            HIPCHK(h, hipMalloc(&h->devPos[b], posCap * 3 * sizeof(float)));
+        HIPCHK(h, h->sortKeys[b].alloc(cap));
+        HIPCHK(h, h->sortVals[b].alloc(cap));
+        h->ws.keys[b] = h->sortKeys[b];
+        h->ws.vals[b] = h->sortVals[b];
+        if (!(h->opt.flags & SPH_FLAG_MAPPED_POSITIONS)) {
+            HIPCHK(h, h->devPosBuf[b].alloc(posCap * 3));
+            h->devPos[b] = h->devPosBuf[b];
+        }
         HIPCHK(h, hipMemset(h->ws.keys[b], 0, cap * sizeof(uint32_t)));
         HIPCHK(h, hipMemset(h->ws.vals[b], 0, cap * sizeof(uint32_t)));
-        HIPCHK(h, hipEventCreateWithFlags(&h->computeDone[b], hipEventDisableTiming));
-        HIPCHK(h, hipEventCreateWithFlags(&h->copyDone[b], hipEventDisableTiming));
+        HIPCHK(h, h->computeDone[b].create(hipEventDisableTiming));
+        HIPCHK(h, h->copyDone[b].create(hipEventDisableTiming));
     }
     h->ws.capacity = (int)cap;
     h->ws.maxBlocks = (int)sph_sort_workspace_blocks((int)cap);
-    HIPCHK(h, hipMalloc(&h->ws.blockHist,
-                        (size_t)1024 * (size_t)(h->ws.maxBlocks > 0 ? h->ws.maxBlocks : 1) *
-                            sizeof(uint32_t)));
-    HIPCHK(h, hipMalloc(&h->ws.digitTotal, 1024 * sizeof(uint32_t)));
+    HIPCHK(h, h->sortBlockHist.alloc((size_t)1024 * (size_t)(h->ws.maxBlocks > 0 ? h->ws.maxBlocks : 1)));
+    HIPCHK(h, h->sortDigitTotal.alloc(1024));
+    h->ws.blockHist = h->sortBlockHist;
+    h->ws.digitTotal = h->sortDigitTotal;
     for (int b = 0; b < 2; ++b) {
-        HIPCHK(h, hipMalloc(&h->cellTable[b], (size_t)h->P.numCells * sizeof(int2)));
+        HIPCHK(h, h->cellTable[b].alloc((size_t)h->P.numCells));
         HIPCHK(h, hipMemset(h->cellTable[b], 0, (size_t)h->P.numCells * sizeof(int2)));
     }
     h->cellRange = h->cellTable[0];
     // measured (profiles/r03_experiments.md): n = 262,144: 0.170 -> 0.149 ms per step; n = 4,194,304: nothing
     // (the early steps are bound by the read-back, and beside more GPU work its blit kernel slows down)
     h->aheadEnabled = h->n < (3 << 19);
-    if (const char *e = getenv("SPH_PIPELINE")) h->aheadEnabled = atoi(e) != 0;
+    if (h->knobs.pipeline >= 0) h->aheadEnabled = h->knobs.pipeline != 0;
     if (h->opt.flags & SPH_FLAG_MAPPED_POSITIONS) {
         // zero-copy: the force sweep's id-ordered scatter goes over PCIe into this buffer
-        HIPCHK(h, hipHostMalloc(&h->hostPos, posCap * 3 * sizeof(float), hipHostMallocMapped));
+        HIPCHK(h, h->hostPos.alloc(posCap * 3, hipHostMallocMapped));
         void *dp = nullptr;
         HIPCHK(h, hipHostGetDevicePointer(&dp, h->hostPos, 0));
         h->devPos[0] = h->devPos[1] = static_cast<float *>(dp);
         h->mappedPos = true;
     } else {
         // (measured, round 3: a non-coherent buffer changes nothing for the runtime's copy)
-        HIPCHK(h, hipHostMalloc(&h->hostPos, posCap * 3 * sizeof(float), hipHostMallocDefault));
+        HIPCHK(h, h->hostPos.alloc(posCap * 3));
     }
     memset(h->hostPos, 0, posCap * 3 * sizeof(float));
     if (h->opt.sweep == SPH_SWEEP_LIST) {
@@ -179,60 +200,58 @@ int alloc_device(sph_handle *h) {
             const unsigned long long lim = (unsigned long long)(0.4 * (double)freeB) / sizeof(uint4);
             if (quads > lim) quads = lim;
         }
-        if (const char *e = getenv("SPH_MASK_POOL_WORDS")) quads = strtoull(e, nullptr, 10) / 4;
+        if (h->knobs.maskPoolSet) quads = h->knobs.maskPoolQuads;
         if (quads > 0xFFFFFFF0ull) quads = 0xFFFFFFF0ull; // wave bases are 32-bit quad indices
         h->maskCapacity = quads;
-        HIPCHK(h, hipMalloc(&h->maskPool, (size_t)(quads ? quads : 1) * sizeof(uint4)));
-        HIPCHK(h, hipMalloc(&h->pv8, cap * 2 * sizeof(float4)));
+        HIPCHK(h, h->maskPool.alloc((size_t)(quads ? quads : 1) * 4)); // (a quad: four words)
+        HIPCHK(h, h->pv8.alloc(cap * 2));
         // per 64-particle wave: {base of its quads or ~0u, quads per lane}
         const size_t hdrWords = 2 * ((cap + 63) / 64 + 1);
-        HIPCHK(h, hipMalloc(&h->maskOff, hdrWords * sizeof(uint32_t)));
+        HIPCHK(h, h->maskOff.alloc(hdrWords));
         HIPCHK(h, hipMemset(h->maskOff, 0xFF, hdrWords * sizeof(uint32_t)));
-        HIPCHK(h, hipMalloc(&h->noneList, hdrWords * sizeof(uint32_t))); // (>= one entry per wave)
-        HIPCHK(h, hipMalloc(&h->maskCursor, kCursorBytes));
+        HIPCHK(h, h->noneList.alloc(hdrWords)); // (>= one entry per wave)
+        HIPCHK(h, h->maskCursor.alloc(kCursorBytes / sizeof(unsigned long long)));
         HIPCHK(h, hipMemset(h->maskCursor, 0, kCursorBytes));
-        HIPCHK(h, hipMalloc(&h->hitCount, (cap + 64) * sizeof(uint32_t)));
+        HIPCHK(h, h->hitCount.alloc(cap + 64));
         HIPCHK(h, hipMemset(h->hitCount, 0, (cap + 64) * sizeof(uint32_t)));
         // one bit per sorted row + the word a 32-row window may reach into
         const size_t quietWords = 2 * ((cap + 63) / 64) + 2;
-        HIPCHK(h, hipMalloc(&h->quiet, quietWords * sizeof(uint32_t)));
+        HIPCHK(h, h->quiet.alloc(quietWords));
         HIPCHK(h, hipMemset(h->quiet, 0, quietWords * sizeof(uint32_t)));
-        HIPCHK(h, hipMalloc(&h->quietVref, 2 * sizeof(float4))); // [0] the reference velocity, [1].x the all-quiet word, [1].y the halo rows'
+        HIPCHK(h, h->quietVref.alloc(2)); // [0] the reference velocity, [1].x the all-quiet word, [1].y the halo rows'
         HIPCHK(h, hipMemset(h->quietVref, 0, 2 * sizeof(float4)));
-        HIPCHK(h, hipMalloc(&h->calm, ((cap + 63) / 64 + 1) * sizeof(unsigned long long)));
+        HIPCHK(h, h->calm.alloc((cap + 63) / 64 + 1));
         HIPCHK(h, hipMemset(h->calm, 0, ((cap + 63) / 64 + 1) * sizeof(unsigned long long)));
-        if (const char *e = getenv("SPH_ZERO_PAIR_FILTER")) h->useQuiet = atoi(e) != 0;
     }
-    HIPCHK(h, hipHostMalloc(&h->oobHost, sizeof(SphOobLog), hipHostMallocMapped));
+    HIPCHK(h, h->oobHost.alloc(1, hipHostMallocMapped));
     memset(h->oobHost, 0, sizeof(SphOobLog));
     {
         void *dp = nullptr;
         HIPCHK(h, hipHostGetDevicePointer(&dp, h->oobHost, 0));
         h->ws.oob = static_cast<SphOobLog *>(dp);
     }
-    HIPCHK(h, hipMalloc(&h->boundsDev, 16 * sizeof(int)));
-    HIPCHK(h, hipMalloc(&h->partTiles, sph_partition_tiles((int)cap) * 9 * sizeof(int)));
-    HIPCHK(h, hipHostMalloc(&h->boundsHost, 8 * sizeof(int), hipHostMallocDefault));
+    HIPCHK(h, h->boundsDev.alloc(16));
+    HIPCHK(h, h->partTiles.alloc(sph_partition_tiles((int)cap) * 9));
+    HIPCHK(h, h->boundsHost.alloc(8));
     for (auto &pe : h->pairs) {
-        HIPCHK(h, hipEventCreate(&pe.a));
-        HIPCHK(h, hipEventCreate(&pe.b));
+        HIPCHK(h, pe.a.create());
+        HIPCHK(h, pe.b.create());
     }
     if (h->opt.flags & SPH_FLAG_STORE_FORCE)
-        HIPCHK(h, hipMalloc(&h->force4, cap * sizeof(float4)));
-    HIPCHK(h, hipMalloc(&h->pairCounter, kCounterWords * sizeof(unsigned long long)));
+        HIPCHK(h, h->force4.alloc(cap));
+    HIPCHK(h, h->pairCounter.alloc(kCounterWords));
     HIPCHK(h, hipMemset(h->pairCounter, 0, kCounterWords * sizeof(unsigned long long)));
-    HIPCHK(h, hipHostMalloc(&h->pairHost, kCounterWords * sizeof(unsigned long long), hipHostMallocDefault));
+    HIPCHK(h, h->pairHost.alloc(kCounterWords));
     *h->pairHost = 0;
     for (auto &se : h->ring) {
-        for (auto &e : se.e) HIPCHK(h, hipEventCreate(&e));
-        for (auto &e : se.c) HIPCHK(h, hipEventCreate(&e));
+        for (auto &e : se.e) HIPCHK(h, e.create());
+        for (auto &e : se.c) HIPCHK(h, e.create());
     }
     // Read-back pre-warm.  The runtime sets up its device-to-host copy path on the first copies
     // of a process: a one-off ~7 ms stall, which otherwise lands in the first steps of a run
     // (scripts/studies/early_stall.py).  A few small copies through the same stream and buffers here.
     if (h->hostPos && h->devPos[0] && !h->mappedPos) {
-        int warm = 16;
-        if (const char *e = getenv("SPH_PREWARM_COPIES")) warm = atoi(e);
+        const int warm = h->knobs.prewarmCopies;
         const size_t bytes = std::min<size_t>(posCap * 3 * sizeof(float), (size_t)1 << 20);
         for (int k = 0; k < warm; ++k) {
             HIPCHK(h, hipMemcpyAsync(h->hostPos, h->devPos[k & 1], bytes, hipMemcpyDeviceToHost, h->copy));
@@ -361,6 +380,7 @@ int sph_create(const SphSettings *settings, const SphOptions *options, sph_handl
                     "no HIP device: libsph_hip has no CPU fallback by design");
     sph_handle *h = new (std::nothrow) sph_handle();
     if (!h) return fail(nullptr, SPH_ENOMEM, "out of host memory");
+    h->knobs = read_knobs();
     h->settings = *settings;
     if (options) {
         size_t sz = options->struct_size > 0 ? (size_t)options->struct_size : sizeof(SphOptions);
@@ -388,9 +408,6 @@ int sph_create(const SphSettings *settings, const SphOptions *options, sph_handl
     // holds ~1/N of the numParticles its settings name
     if ((h->opt.flags & SPH_FLAG_EXTERNAL_STATE) && h->opt.capacity > 0) h->cap = h->opt.capacity;
     else h->cap = h->opt.capacity > h->n ? h->opt.capacity : h->n;
-    if (const char *e = getenv("SPH_TILE_CHUNK")) h->tileChunkEnv = atoi(e); // tuning studies
-    if (const char *e = getenv("SPH_XCD_ROTATE")) h->tileRotate = atoi(e);
-    if (const char *e = getenv("SPH_STEP_TRACE")) h->trace = atoi(e) != 0;
     fill_params(h);
     int rc = SPH_OK;
     do {
@@ -417,48 +434,22 @@ int sph_create(const SphSettings *settings, const SphOptions *options, sph_handl
 
 void sph_destroy(sph_handle *h) {
     if (!h) return;
-    if (h->trace && h->trSteps > 0)
+    if (h->knobs.stepTrace && h->trSteps > 0)
         fprintf(stderr, "sph step trace (host, us per timed step over %lld steps): enqueue %.1f | wait for the compute stream %.1f | "
                         "after the wait %.1f | caller between two steps %.1f\n", h->trSteps, h->trEnqueue / h->trSteps * 1e6,
                 h->trSync / h->trSteps * 1e6, h->trPost / h->trSteps * 1e6, h->trBetween / (h->trSteps > 1 ? h->trSteps - 1 : 1) * 1e6),
         fprintf(stderr, "  enqueue split: events %.1f | grid %.1f | density %.1f | force %.1f | read-back %.1f\n", h->trPh[0] / h->trSteps * 1e6,
                 h->trPh[1] / h->trSteps * 1e6, h->trPh[2] / h->trSteps * 1e6, h->trPh[3] / h->trSteps * 1e6, h->trPh[4] / h->trSteps * 1e6);
-    if (h->trace && h->sampleTileCalls + h->samplePlainCalls > 0)
+    if (h->knobs.stepTrace && h->sampleTileCalls + h->samplePlainCalls > 0)
         fprintf(stderr, "sph sample trace: %lld samples by k_sample_tile, %lld by k_sample_plain\n", h->sampleTileCalls, h->samplePlainCalls);
     if (h->compute) (void)hipStreamSynchronize(h->compute);
     if (h->copy) (void)hipStreamSynchronize(h->copy);
     sdma_destroy(h);
-    if (h->external) h->pos4[0] = h->pos4[1] = h->vel4[0] = h->vel4[1] = nullptr; // the caller's
-    if (h->mappedPos) h->devPos[0] = h->devPos[1] = nullptr;                      // (aliases of hostPos)
-    for (void *p : {(void *)h->pos4[0], (void *)h->pos4[1], (void *)h->vel4[0], (void *)h->vel4[1], (void *)h->ws.keys[0],
-                    (void *)h->ws.keys[1], (void *)h->ws.vals[0], (void *)h->ws.vals[1], (void *)h->devPos[0], (void *)h->devPos[1],
-                    (void *)h->ws.blockHist, (void *)h->ws.digitTotal, (void *)h->cellTable[0], (void *)h->cellTable[1],
-                    (void *)h->force4, (void *)h->pairCounter, (void *)h->pv8, (void *)h->maskPool, (void *)h->maskOff,
-                    (void *)h->noneList, (void *)h->hitCount, (void *)h->maskCursor, (void *)h->quiet, (void *)h->quietVref,
-                    (void *)h->calm, (void *)h->initPos4, (void *)h->rDepth, (void *)h->rCount, (void *)h->rEdge, (void *)h->rRgb,
-                    (void *)h->rPacked, (void *)h->rRange, (void *)h->boundsDev, (void *)h->partTiles, (void *)h->sampleDev,
-                    (void *)h->diagDev})
-        if (p) (void)hipFree(p);
-    for (void *p : {(void *)h->hostPos, (void *)h->stage[0], (void *)h->stage[1], (void *)h->pairHost, (void *)h->oobHost,
-                    (void *)h->frameHost, (void *)h->rangeHost, (void *)h->boundsHost, (void *)h->sampleHost,
-                    (void *)h->diagHost})
-        if (p) (void)hipHostFree(p);
-    for (hipEvent_t e : {h->computeDone[0], h->computeDone[1], h->copyDone[0], h->copyDone[1], h->stageFree[0], h->stageFree[1],
-                         h->frameOut.done, h->frameOut.copied, h->sampleOut.done, h->sampleOut.copied, h->diagOut.done,
-                         h->diagOut.copied})
-        if (e) (void)hipEventDestroy(e);
-    for (auto &se : h->ring) {
-        for (auto &e : se.e) if (e) (void)hipEventDestroy(e);
-        for (auto &e : se.c) if (e) (void)hipEventDestroy(e);
-    }
-    for (auto &pe : h->pairs) {
-        if (pe.a) (void)hipEventDestroy(pe.a);
-        if (pe.b) (void)hipEventDestroy(pe.b);
-    }
     if (h->ownCompute) h->compute = h->ownCompute;
-    if (h->compute) (void)hipStreamDestroy(h->compute);
-    if (h->copy) (void)hipStreamDestroy(h->copy);
-    delete h;
+    const hipStream_t compute = h->compute, copy = h->copy;
+    delete h; // every buffer and event, before the streams they were used on
+    if (compute) (void)hipStreamDestroy(compute);
+    if (copy) (void)hipStreamDestroy(copy);
 }
 
 int sph_setup(sph_handle *h) {
@@ -488,15 +479,9 @@ int sph_setup(sph_handle *h) {
     rc = upload_common(h, pos.data(), nullptr, n);
     if (rc || n <= 0 || h->external) return rc;
     // keep the initial streams (best effort: without the copy the next setup() recomputes them)
-    if (hipMalloc(&h->initPos4, (size_t)n * sizeof(float4)) == hipSuccess) {
-        if (hipMemcpy(h->initPos4, h->pos4[0], (size_t)n * sizeof(float4), hipMemcpyDeviceToDevice) == hipSuccess) {
-            h->initZLayers = h->zLayers;
-        } else {
-            (void)hipFree(h->initPos4);
-            h->initPos4 = nullptr;
-        }
-    } else {
-        h->initPos4 = nullptr;
+    if (h->initPos4.alloc((size_t)n) == hipSuccess) {
+        if (hipMemcpy(h->initPos4, h->pos4[0], (size_t)n * sizeof(float4), hipMemcpyDeviceToDevice) == hipSuccess) h->initZLayers = h->zLayers;
+        else h->initPos4.reset();
     }
     (void)hipGetLastError();
     return SPH_OK;
@@ -650,42 +635,36 @@ int sph_sort_check(int device, const uint32_t *keys, int n, int key_bits_, uint3
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return SPH_ENODEV;
     if (device >= 0 && hipSetDevice(device) != hipSuccess) return SPH_EHIP;
     if (n == 0) return SPH_OK;
-    SortWorkspace ws{};
-    int rc = SPH_OK;
     std::vector<uint32_t> iota((size_t)n);
     for (int i = 0; i < n; ++i) iota[i] = (uint32_t)i;
-    size_t nb = sph_sort_workspace_blocks(n);
-    bool ok = true;
-    for (int b = 0; b < 2 && ok; ++b) {
-        ok = ok && hipMalloc(&ws.keys[b], (size_t)n * 4) == hipSuccess;
-        ok = ok && hipMalloc(&ws.vals[b], (size_t)n * 4) == hipSuccess;
-    }
-    ok = ok && hipMalloc(&ws.blockHist, 1024 * nb * 4) == hipSuccess;
-    ok = ok && hipMalloc(&ws.digitTotal, 1024 * 4) == hipSuccess;
-    for (int b = 0; b < 2 && ok; ++b) {
-        ok = ok && hipMemset(ws.keys[b], 0, (size_t)n * 4) == hipSuccess;
-        ok = ok && hipMemset(ws.vals[b], 0, (size_t)n * 4) == hipSuccess;
-    }
-    if (ok) {
-        ws.capacity = n;
-        ws.maxBlocks = (int)nb;
-        ok = ok && hipMemcpy(ws.keys[0], keys, (size_t)n * 4, hipMemcpyHostToDevice) == hipSuccess;
-        ok = ok && hipMemcpy(ws.vals[0], iota.data(), (size_t)n * 4, hipMemcpyHostToDevice) == hipSuccess;
-        int res = sph_sort_pairs(ws, n, key_bits_, nullptr);
-        ok = ok && hipDeviceSynchronize() == hipSuccess;
-        if (ok && perm_out)
-            ok = hipMemcpy(perm_out, ws.vals[res], (size_t)n * 4, hipMemcpyDeviceToHost) == hipSuccess;
-        if (ok && sorted_keys_out)
-            ok = hipMemcpy(sorted_keys_out, ws.keys[res], (size_t)n * 4, hipMemcpyDeviceToHost) == hipSuccess;
-    }
-    if (!ok) rc = SPH_EHIP;
+    const size_t nb = sph_sort_workspace_blocks(n);
+    DeviceBuf<uint32_t> dk[2], dv[2], blockHist, digitTotal; // (released on every way out)
+#define SORT_TRY(call) do { if ((call) != hipSuccess) return SPH_EHIP; } while (0)
     for (int b = 0; b < 2; ++b) {
-        if (ws.keys[b]) (void)hipFree(ws.keys[b]);
-        if (ws.vals[b]) (void)hipFree(ws.vals[b]);
+        SORT_TRY(dk[b].alloc((size_t)n));
+        SORT_TRY(dv[b].alloc((size_t)n));
     }
-    if (ws.blockHist) (void)hipFree(ws.blockHist);
-    if (ws.digitTotal) (void)hipFree(ws.digitTotal);
-    return rc;
+    SORT_TRY(blockHist.alloc(1024 * nb));
+    SORT_TRY(digitTotal.alloc(1024));
+    SortWorkspace ws{};
+    for (int b = 0; b < 2; ++b) {
+        ws.keys[b] = dk[b];
+        ws.vals[b] = dv[b];
+        SORT_TRY(hipMemset(ws.keys[b], 0, (size_t)n * 4));
+        SORT_TRY(hipMemset(ws.vals[b], 0, (size_t)n * 4));
+    }
+    ws.blockHist = blockHist;
+    ws.digitTotal = digitTotal;
+    ws.capacity = n;
+    ws.maxBlocks = (int)nb;
+    SORT_TRY(hipMemcpy(ws.keys[0], keys, (size_t)n * 4, hipMemcpyHostToDevice));
+    SORT_TRY(hipMemcpy(ws.vals[0], iota.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    const int res = sph_sort_pairs(ws, n, key_bits_, nullptr);
+    SORT_TRY(hipDeviceSynchronize());
+    if (perm_out) SORT_TRY(hipMemcpy(perm_out, ws.vals[res], (size_t)n * 4, hipMemcpyDeviceToHost));
+    if (sorted_keys_out) SORT_TRY(hipMemcpy(sorted_keys_out, ws.keys[res], (size_t)n * 4, hipMemcpyDeviceToHost));
+#undef SORT_TRY
+    return SPH_OK;
 }
 
 } // extern "C"

@@ -3,7 +3,6 @@
 #include "sph_handle.h"
 
 #include <cmath>
-#include <cstdlib>
 
 using namespace sph_host;
 
@@ -26,10 +25,9 @@ int diag_options(sph_handle *h, const SphDiagnosticsOptions *opt, SphDiagnostics
 
 // clear + reduce (+ histogram) of `n` rows on the compute stream, timed, and the result block on its way to pinned memory
 int diag_run(sph_handle *h, const float4 *pos, const float4 *vel, int n, const SphDiagnosticsOptions &o) {
-    if (!h->diagDev) HIPCHK(h, hipMalloc(&h->diagDev, sizeof(DiagBlock)));
-    if (!h->diagHost) HIPCHK(h, hipHostMalloc(&h->diagHost, sizeof(DiagBlock), hipHostMallocDefault));
-    bool plain = false;
-    if (const char *e = getenv("SPH_DIAG_PLAIN")) plain = atoi(e) != 0;
+    if (!h->diagDev) HIPCHK(h, h->diagDev.alloc(1));
+    if (!h->diagHost) HIPCHK(h, h->diagHost.alloc(1));
+    const bool plain = plain_path("SPH_DIAG_PLAIN");
     int rc = outbound_fence(h, h->diagOut); // the previous call's copy still reads the block the clear is about to rewrite
     if (rc) return rc;
     DiagArgs A{};
@@ -45,7 +43,7 @@ int diag_run(sph_handle *h, const float4 *pos, const float4 *vel, int n, const S
     HIPCHK(h, hipGetLastError());
     h->diagCount += 1;
     h->diagValid = false; // (until the copy is queued: the pinned block still holds the previous result)
-    if ((rc = outbound_send(h, h->diagOut, {{h->diagHost, h->diagDev, sizeof(DiagBlock)}}))) return rc;
+    if ((rc = outbound_send(h, h->diagOut, {{h->diagHost.get(), h->diagDev.get(), sizeof(DiagBlock)}}))) return rc;
     h->diagN = n;
     h->diagOpt = o;
     h->diagAuto = A.autoRange != 0;

@@ -2,7 +2,6 @@
 #include "sph_handle.h"
 
 #include <cmath>
-#include <cstdlib>
 #include <cstring>
 #include <vector>
 
@@ -18,23 +17,16 @@ int render_resize(sph_handle *h, int width, int height) {
     HIPCHK(h, hipStreamSynchronize(h->copy));
     h->frameOut.pending = false;
     h->frameValid = false;
-    for (uint32_t **b : {&h->rDepth, &h->rCount, &h->rEdge, &h->rRgb}) {
-        if (*b) (void)hipFree(*b);
-        *b = nullptr;
-    }
-    if (h->frameHost) (void)hipHostFree(h->frameHost);
-    h->frameHost = nullptr;
-    if (h->rPacked) (void)hipFree(h->rPacked); // (sized by the image: the next field frame allocates it again)
-    h->rPacked = nullptr;
+    h->rPacked.reset(); // (sized by the image: the next field frame allocates it again)
     h->fieldFrame = false;
     h->rp.width = h->rp.height = 0;
     const size_t npix = (size_t)width * (size_t)height;
     const size_t rgbBytes = (npix + 3) / 4 * 12; // whole groups of four pixels (k_render_compose)
-    HIPCHK(h, hipMalloc(&h->rDepth, npix * sizeof(uint32_t)));
-    HIPCHK(h, hipMalloc(&h->rCount, npix * sizeof(uint32_t)));
-    HIPCHK(h, hipMalloc(&h->rEdge, npix * sizeof(uint32_t)));
-    HIPCHK(h, hipMalloc(&h->rRgb, rgbBytes));
-    HIPCHK(h, hipHostMalloc(&h->frameHost, rgbBytes, hipHostMallocDefault));
+    HIPCHK(h, h->rDepth.alloc(npix));
+    HIPCHK(h, h->rCount.alloc(npix));
+    HIPCHK(h, h->rEdge.alloc(npix));
+    HIPCHK(h, h->rRgb.alloc(rgbBytes / sizeof(uint32_t)));
+    HIPCHK(h, h->frameHost.alloc(rgbBytes));
     memset(h->frameHost, 0, rgbBytes);
     RenderParams R = h->rp;
     R.width = width;
@@ -63,13 +55,12 @@ int frame_begin(sph_handle *h, const Opt *opt, const char *unset, Rest rest, boo
     if (const char *bad = rest(o)) return fail(h, SPH_EINVAL, bad);
     if ((rc = render_resize(h, width, height))) return rc;
     if (field) {
-        if (!h->rPacked) HIPCHK(h, hipMalloc(&h->rPacked, (size_t)width * height * sizeof(unsigned long long)));
-        if (!h->rRange) HIPCHK(h, hipMalloc(&h->rRange, 2 * sizeof(uint32_t)));
-        if (!h->rangeHost) HIPCHK(h, hipHostMalloc(&h->rangeHost, 2 * sizeof(uint32_t), hipHostMallocDefault));
+        if (!h->rPacked) HIPCHK(h, h->rPacked.alloc((size_t)width * height));
+        if (!h->rRange) HIPCHK(h, h->rRange.alloc(2));
+        if (!h->rangeHost) HIPCHK(h, h->rangeHost.alloc(2));
     }
     h->rp.radius = (pointSize - 1) / 2;
-    plain = false;
-    if (const char *e = getenv("SPH_RENDER_PLAIN")) plain = atoi(e) != 0;
+    plain = plain_path("SPH_RENDER_PLAIN");
     if ((rc = outbound_fence(h, h->frameOut))) return rc; // the previous frame's copy still reads the device frame the compose is about to rewrite
     return pair_begin(h, &h->renderSeconds, &pe);
 }
@@ -82,9 +73,9 @@ int frame_finish(sph_handle *h, PairEvent *pe, bool field) {
     h->renderFrames += 1;
     h->frameValid = true;
     h->fieldFrame = field;
-    const OutboundCopy frame{h->frameHost, h->rRgb, (size_t)h->rp.width * h->rp.height * 3};
+    const OutboundCopy frame{h->frameHost.get(), h->rRgb.get(), (size_t)h->rp.width * h->rp.height * 3};
     if (!field) return outbound_send(h, h->frameOut, {frame});
-    return outbound_send(h, h->frameOut, {frame, {h->rangeHost, h->rRange, 2 * sizeof(uint32_t)}});
+    return outbound_send(h, h->frameOut, {frame, {h->rangeHost.get(), h->rRange.get(), 2 * sizeof(uint32_t)}});
 }
 
 } // namespace

@@ -1,16 +1,66 @@
 // The handle behind include/sph_c_api.h and the few helpers its host translation units share (sph_api.hip,
 // sph_step.hip, sph_readback.hip, sph_slab.hip, sph_snapshot.hip, sph_frame.hip, sph_sample.hip, sph_diag.hip).  Host code only.
+// Ownership: every device buffer, pinned block and event below is a DeviceBuf / PinnedBuf / Event (sph_owned.h) and goes
+// with the handle; a raw pointer member is a view of one of them (or of the caller's memory) and says so.
 #pragma once
 
 #include "sph_c_api.h"
 #include "sph_device.h"
+#include "sph_owned.h"
 
 #include <chrono>
+#include <cstdlib>
 #include <cstring>
 #include <initializer_list>
 #include <string>
 
 namespace sph_host {
+
+using sph_owned::DeviceBuf;
+using sph_owned::Event;
+using sph_owned::PinnedBuf;
+
+// The library's SPH_* environment knobs: this comment is the list.  None changes a result; all are for A/B runs,
+// studies and diagnosis.  "create": read once, by read_knobs() at the top of sph_create, into sph_handle::knobs.
+// "call": read by every call, through plain_path().  Numbers are parsed with atoi (an empty value is 0).
+//   name                  default  read    what it does
+//   SPH_SLIM_DIV          (auto)   create  0: the pair body uses the full IEEE divide / square-root expansions even
+//                                          with the reference's constants (same bits); any other value: no effect
+//   SPH_PIPELINE          (auto)   create  0 / non-zero: a timed step does not / does queue the next step's grid build
+//                                          before it waits; default: on below 1.5 M particles
+//   SPH_MASK_POOL_WORDS   (auto)   create  size of the list sweep's hit-stream pool in 32-bit words (strtoull, / 4 =
+//                                          quads; then the 32-bit clamp); default: sized from n and the free memory
+//   SPH_ZERO_PAIR_FILTER  1        create  0: the list sweep's zero-pair filter is off
+//   SPH_PREWARM_COPIES    16       create  small device-to-host copies sph_create issues to warm the runtime's copy path
+//   SPH_TILE_CHUNK        -1       create  xcd_tile()'s chunk: -1 auto, 0 contiguous eighths, > 0 tiles per chunk
+//   SPH_XCD_ROTATE        -1       create  xcd_tile()'s rotation period in groups (z-layers), 0 = off; -1: off for the
+//                                          single domain, every layer for a slab (slab_rotate)
+//   SPH_STEP_TRACE        0        create  non-zero: sph_destroy prints where the host spent its timed steps, every timed
+//                                          step its GPU timeline, sph_create the SDMA engine it picked
+//   SPH_READBACK_SDMA     1        create  0: timed steps read back through the HIP runtime's copy, not an SDMA engine
+//   SPH_RENDER_PLAIN      0        call    non-zero: sph_render_frame / sph_render_field take the check path
+//   SPH_SAMPLE_PLAIN      0        call    non-zero: sph_sample_field takes the one-thread-per-point check path
+//   SPH_DIAG_PLAIN        0        call    non-zero: sph_diagnose / sph_slab_diagnose take the check path
+//   SPH_MGPU_THREADS      0        (libsph_mgpu.so, its own object: sph_mgpu_create in mgpu_state.cpp) non-zero: one
+//                                          host thread per local slab
+// (The SPH_* variables the command-line front end reads -- SPH_SWEEP, SPH_GPUS, SPH_TRANSPORT, SPH_RECUT_EVERY,
+// SPH_FREE_*, SPH_PRINT_SHA256 -- are its arguments by another road, not library knobs.)
+struct Knobs {
+    int slimDiv = 1;        // only 0 acts
+    int pipeline = -1;      // -1: by n
+    bool maskPoolSet = false;
+    unsigned long long maskPoolQuads = 0;
+    bool zeroPairFilter = true;
+    int prewarmCopies = 16;
+    int tileChunk = -1;
+    int xcdRotate = -1;
+    bool stepTrace = false;
+    bool readbackSdma = true;
+};
+inline bool plain_path(const char *name) {
+    const char *e = getenv(name);
+    return e && atoi(e) != 0;
+}
 
 constexpr int kEventRing = 64;
 constexpr int kCounterWords = 16 + 256 * 16; // 16 spare words, then 256 shards x 16: [0] pair tests,
@@ -18,8 +68,8 @@ constexpr int kCounterWords = 16 + 256 * 16; // 16 spare words, then 256 shards 
 constexpr size_t kCursorBytes = (size_t)SL_POOL_SHARDS * SL_CURSOR_STRIDE * sizeof(unsigned long long);
 
 struct PairEvent { // one timed section of the slab path
-    hipEvent_t a = nullptr, b = nullptr;
-    double *target = nullptr;
+    Event a, b;
+    double *target = nullptr; // view: the handle's accumulator the section is added to
     bool used = false;
 };
 constexpr int kPairRing = 48;
@@ -27,8 +77,8 @@ constexpr int kPairRing = 48;
 // A result on its way to pinned memory over the copy stream, behind what `compute` had queued when it left
 // (outbound_* below): the frame, the field sample.
 struct Outbound {
-    hipEvent_t done = nullptr, copied = nullptr; // on compute: the result is complete; on copy: it has arrived
-    bool pending = false;                        // a copy is queued: `copied` tells when the device buffer is free again
+    Event done, copied; // on compute: the result is complete; on copy: it has arrived
+    bool pending = false;  // a copy is queued: `copied` tells when the device buffer is free again
 };
 struct OutboundCopy {
     void *dst;
@@ -37,8 +87,8 @@ struct OutboundCopy {
 };
 
 struct StepEvents {
-    hipEvent_t e[6] = {}; // start, hash, sort, gather, density, force
-    hipEvent_t c[2] = {}; // copy start / end
+    Event e[6]; // start, hash, sort, gather, density, force
+    Event c[2]; // copy start / end
     bool used = false, hasCopy = false, counted = false;
 };
 
@@ -48,51 +98,51 @@ struct sph_handle {
     // ---- sph_api.hip: settings, the particle streams and the grid's buffers, state flags ----
     SphSettings settings{};
     SphOptions opt{};
+    sph_host::Knobs knobs{}; // the SPH_* environment, as sph_create found it
     DevParams P{};
     int n = 0, cap = 0, device = 0;
-    hipStream_t compute = nullptr, copy = nullptr;
-    float4 *pos4[2] = {nullptr, nullptr};
+    hipStream_t compute = nullptr, copy = nullptr; // created by sph_create; sph_destroy destroys them last, after every buffer and event
+    sph_host::DeviceBuf<float4> posBuf[2], velBuf[2]; // the particle streams of a handle that owns its state
+    float4 *pos4[2] = {nullptr, nullptr}; // views: posBuf / velBuf, or the caller's buffers (sph_bind_buffers)
     float4 *vel4[2] = {nullptr, nullptr};
     int cur = 0;     // buffers holding the current state
     int sorted = -1; // buffers holding the sorted streams of the last grid build
-    SortWorkspace ws{};
+    sph_host::DeviceBuf<uint32_t> sortKeys[2], sortVals[2], sortBlockHist, sortDigitTotal;
+    SortWorkspace ws{}; // views of the six above and of oobHost (the struct is sort.hip's argument)
     int sortedKeyBuf = 0;
-    int2 *cellRange = nullptr;       // the cell table of the LAST grid build (= cellTable[cellCur])
-    int2 *cellTable[2] = {nullptr, nullptr}; // two tables: a grid built ahead (below) must not clobber the last step's
+    int2 *cellRange = nullptr;       // view: the cell table of the LAST grid build (= cellTable[cellCur])
+    sph_host::DeviceBuf<int2> cellTable[2]; // two tables: a grid built ahead (below) must not clobber the last step's
     int cellCur = 0;
-    float *devPos[2] = {nullptr, nullptr};
-    float *hostPos = nullptr; // pinned, n*3
+    sph_host::DeviceBuf<float> devPosBuf[2];
+    float *devPos[2] = {nullptr, nullptr}; // views: devPosBuf, or (SPH_FLAG_MAPPED_POSITIONS) the device address of hostPos
+    sph_host::PinnedBuf<float> hostPos; // n*3
     bool hostPosIsInit = false; // setup() restored the initial state on the device: getPosition() fetches it on demand
     // Pinned staging for state uploads (two halves, ping-pong).  A hipMemcpy from pageable
     // memory makes the runtime pin and later unpin the caller's pages; the unpin is deferred
     // and stalls the GPU's queues for 6-28 ms some time AFTER the call returned -- inside the
     // first steps of the run that follows (measured).
-    float4 *stage[2] = {nullptr, nullptr};
-    hipEvent_t stageFree[2] = {nullptr, nullptr};
-    bool mappedPos = false;   // SPH_FLAG_MAPPED_POSITIONS: devPos[] alias hostPos (host-mapped)
-    float4 *force4 = nullptr;
-    unsigned long long *pairCounter = nullptr; // device
-    unsigned long long *pairHost = nullptr;    // pinned
+    sph_host::PinnedBuf<float4> stage[2];
+    sph_host::Event stageFree[2];
+    bool mappedPos = false;   // SPH_FLAG_MAPPED_POSITIONS: devPos[] view hostPos (host-mapped)
+    sph_host::DeviceBuf<float4> force4;
+    sph_host::DeviceBuf<unsigned long long> pairCounter;
+    sph_host::PinnedBuf<unsigned long long> pairHost;
     SphKernelTimes kt{};
-    float4 *pv8 = nullptr;
-    uint32_t *maskPool = nullptr, *maskOff = nullptr; // SPH_SWEEP_LIST
-    uint32_t *noneList = nullptr;    // SPH_SWEEP_LIST: waves without a stream this step (pool exhausted)
-    uint32_t *hitCount = nullptr;    // SPH_SWEEP_LIST: recorded hits per sorted row
-    uint32_t *quiet = nullptr;       // SPH_SWEEP_LIST: one bit per sorted row, the force sweep's zero-pair filter
-    float4 *quietVref = nullptr;     // ... its reference velocity (device; picked by the first sort pass) ...
-    unsigned long long *calm = nullptr; // ... and one bit per sorted row "moves with it" (written by the gather launch)
-    float4 *initPos4 = nullptr;      // setup()'s initial positions (+ids), kept on the device for the next setup()
-    SphOobLog *oobHost = nullptr;    // host-mapped: positions outside the grid met by the cell hash
+    sph_host::DeviceBuf<float4> pv8;
+    sph_host::DeviceBuf<uint32_t> maskPool, maskOff; // SPH_SWEEP_LIST
+    sph_host::DeviceBuf<uint32_t> noneList; // SPH_SWEEP_LIST: waves without a stream this step (pool exhausted)
+    sph_host::DeviceBuf<uint32_t> hitCount; // SPH_SWEEP_LIST: recorded hits per sorted row
+    sph_host::DeviceBuf<uint32_t> quiet;    // SPH_SWEEP_LIST: one bit per sorted row, the force sweep's zero-pair filter
+    sph_host::DeviceBuf<float4> quietVref; // ... its reference velocity (picked by the first sort pass) ...
+    sph_host::DeviceBuf<unsigned long long> calm; // ... and one bit per sorted row "moves with it" (written by the gather launch)
+    sph_host::DeviceBuf<float4> initPos4; // setup()'s initial positions (+ids), kept on the device for the next setup()
+    sph_host::PinnedBuf<SphOobLog> oobHost; // host-mapped: positions outside the grid met by the cell hash
     uint32_t oobSeen = 0;            // how many of them were already reported
     int initZLayers = 0;
-    bool useQuiet = true;            // SPH_ZERO_PAIR_FILTER=0 switches the filter off (A/B; same results)
     uint64_t hitsRecorded = 0;       // SPH_FLAG_COUNT_PAIRS: hits in the stream, before the filter
-    unsigned long long *maskCursor = nullptr;
+    sph_host::DeviceBuf<unsigned long long> maskCursor;
     unsigned long long maskCapacity = 0; // quads (16 B)
     int zLayers = 0;        // occupied z-layers of the (owned) particles: sizes xcd_tile()'s chunks
-    int tileChunkEnv = -1;  // SPH_TILE_CHUNK: -1 auto, 0 contiguous eighths, >0 tiles per chunk
-    int tileRotate = -1;    // SPH_XCD_ROTATE: xcd_tile()'s rotation period in groups (z-layers), 0 = off;
-                            // -1 (default): off for the single domain, every layer for a slab (see slab_rotate)
     bool ready = false;     // state uploaded
     bool gridValid = false; // sorted streams + cell table match `sorted`
     int phase = 0;          // 0 idle, 1 grid done, 2 density done, 3 force done
@@ -106,11 +156,11 @@ struct sph_handle {
     // own force event instead of the whole stream; the next step finds its grid built.  Anything that changes
     // or replaces the state in between (click, upload, load) simply drops the grid built ahead.
     bool gridAhead = false;
-    int2 *clickTable = nullptr;      // cell table of the last COMPLETED step (what sph_apply_click walks)
+    int2 *clickTable = nullptr;      // view: cell table of the last COMPLETED step (what sph_apply_click walks)
     bool clickValid = false;
     bool aheadEnabled = true;        // default: below 1.5 M particles; SPH_PIPELINE=0/1 forces it (same results)
-    sph_host::StepEvents *aheadEv = nullptr;
-    hipEvent_t computeDone[2] = {nullptr, nullptr}, copyDone[2] = {nullptr, nullptr};
+    sph_host::StepEvents *aheadEv = nullptr; // view into ring[]
+    sph_host::Event computeDone[2], copyDone[2];
     bool copyPending[2] = {false, false};
     bool stepTimed = false;          // sph_step(times != NULL) is running (the read-back phase picks the copy path by it)
     int rbDeferredSlot = -1;         // the read-back phase left this slot's copy to sph_step
@@ -118,15 +168,14 @@ struct sph_handle {
     long long stepIndex = 0;
     sph_host::StepEvents ring[sph_host::kEventRing];
     int ringHead = 0;
-    sph_host::StepEvents *curEv = nullptr;
+    sph_host::StepEvents *curEv = nullptr; // view into ring[]
     sph_host::PairEvent pairs[sph_host::kPairRing];
     int pairHead = 0;
-    // SPH_STEP_TRACE=1 (diagnostic): where the HOST spends a timed step, printed by sph_destroy
-    bool trace = false;
+    // SPH_STEP_TRACE=1 (knobs.stepTrace, diagnostic): where the HOST spends a timed step, printed by sph_destroy
     double trEnqueue = 0, trSync = 0, trPost = 0, trBetween = 0, trPh[5] = {0, 0, 0, 0, 0};
     long long trSteps = 0;
     std::chrono::steady_clock::time_point trLastReturn{};
-    hipEvent_t trBase = nullptr;     // first traced step's start: GPU-side timeline of every later step
+    sph_host::Event trBase;           // first traced step's start: GPU-side timeline of every later step
 
     // ---- sph_readback.hip ----
     // Read-back of a TIMED step through an SDMA engine (hsa_amd_memory_async_copy) instead of the HIP runtime's
@@ -145,30 +194,33 @@ struct sph_handle {
     // ---- sph_slab.hip ----
     int slabOwnedBegin = 0, slabOwnedEnd = 0; // rows of the last sph_slab_density (the rest of [0, n_all) is halo)
     bool external = false;  // pos4/vel4 are caller-owned (sph_bind_buffers)
-    hipStream_t ownCompute = nullptr;
-    int *boundsDev = nullptr, *boundsHost = nullptr;
-    int *partTiles = nullptr; // slab partition: class counts per 1024-particle tile
+    hipStream_t ownCompute = nullptr; // the created `compute` while a caller's stream stands in (sph_set_stream)
+    sph_host::DeviceBuf<int> boundsDev;
+    sph_host::PinnedBuf<int> boundsHost;
+    sph_host::DeviceBuf<int> partTiles; // slab partition: class counts per 1024-particle tile
 
     // ---- sph_frame.hip ----
     // The visualiser's frame (render.hip), allocated by the first sph_render_frame: per-pixel depth bits,
     // hit count and the static box-edge layer on the device, the RGB8 frame on the device and in pinned memory.
     RenderParams rp{};               // size / point radius / shade of the last render (width 0: none yet)
-    uint32_t *rDepth = nullptr, *rCount = nullptr, *rEdge = nullptr, *rRgb = nullptr;
-    uint8_t *frameHost = nullptr;
+    sph_host::DeviceBuf<uint32_t> rDepth, rCount, rEdge, rRgb;
+    sph_host::PinnedBuf<uint8_t> frameHost;
     sph_host::Outbound frameOut;     // the frame (a field frame: and its range) on its way to frameHost / rangeHost
     bool frameValid = false;         // the buffers hold a rendered frame of the size in rp
     double renderSeconds = 0;        // clear + splat + compose, from HIP events (PairEvent ring)
     long long renderFrames = 0;
     // The field frame (sph_render_field) adds the packed (depth bits << 32 | value bits) minimum per pixel and
     // the range of the colour scale: two words on the device, copied to pinned memory with the frame.
-    unsigned long long *rPacked = nullptr;
-    uint32_t *rRange = nullptr, *rangeHost = nullptr;
+    sph_host::DeviceBuf<unsigned long long> rPacked;
+    sph_host::DeviceBuf<uint32_t> rRange;
+    sph_host::PinnedBuf<uint32_t> rangeHost;
     bool fieldFrame = false;         // the last render was a field frame
 
     // ---- sph_sample.hip ----
     // The field sample (sample.hip): one float per lattice point on the device and in pinned memory, both grown
     // on demand by sph_sample_field.
-    float *sampleDev = nullptr, *sampleHost = nullptr;
+    sph_host::DeviceBuf<float> sampleDev;
+    sph_host::PinnedBuf<float> sampleHost;
     size_t sampleCap = 0;            // floats either buffer holds
     int sampleDim[3] = {0, 0, 0};    // nx, ny, nz of the last sample
     sph_host::Outbound sampleOut;    // the values on their way to sampleHost
@@ -180,7 +232,8 @@ struct sph_handle {
     // ---- sph_diag.hip ----
     // Run diagnostics (diag.hip): the small result block on the device and in pinned memory, allocated by the
     // first sph_diagnose / sph_slab_diagnose.
-    DiagBlock *diagDev = nullptr, *diagHost = nullptr;
+    sph_host::DeviceBuf<DiagBlock> diagDev;
+    sph_host::PinnedBuf<DiagBlock> diagHost;
     sph_host::Outbound diagOut;      // the block on its way to diagHost
     bool diagValid = false;
     int diagN = 0;                   // rows of the last call
@@ -248,8 +301,8 @@ constexpr size_t kStageRows = (size_t)1 << 19; // 8 MB per half
 template <class Fill>
 int staged_upload(sph_handle *h, float4 *dev, size_t n, Fill fill) {
     for (int b = 0; b < 2; ++b) {
-        if (!h->stage[b]) HIPCHK(h, hipHostMalloc(&h->stage[b], kStageRows * sizeof(float4), hipHostMallocDefault));
-        if (!h->stageFree[b]) HIPCHK(h, hipEventCreateWithFlags(&h->stageFree[b], hipEventDisableTiming));
+        if (!h->stage[b]) HIPCHK(h, h->stage[b].alloc(kStageRows));
+        HIPCHK(h, h->stageFree[b].create(hipEventDisableTiming));
     }
     int b = 0;
     for (size_t k = 0; k < n; k += kStageRows, b ^= 1) {

@@ -34,7 +34,7 @@ hsa_status_t find_agents(hsa_agent_t a, void *data) {
 namespace sph_host {
 
 void sdma_init(sph_handle *h) {
-    if (const char *e = getenv("SPH_READBACK_SDMA")) if (atoi(e) == 0) return;
+    if (!h->knobs.readbackSdma) return;
     if (h->external || h->mappedPos || !h->hostPos || !h->devPos[0]) return;
     if (hsa_init() != HSA_STATUS_SUCCESS) return;
     AgentSearch S{};
@@ -107,7 +107,7 @@ void sdma_init(sph_handle *h) {
         memset(h->hostPos, 0, probe);
     }
     h->sdmaOk = true;
-    if (getenv("SPH_STEP_TRACE")) fprintf(stderr, "sph: read-back through SDMA engine id 0x%x (0 = the HSA runtime's choice)\n", h->sdmaEngine);
+    if (h->knobs.stepTrace) fprintf(stderr, "sph: read-back through SDMA engine id 0x%x (0 = the HSA runtime's choice)\n", h->sdmaEngine);
 }
 
 // wait for the SDMA copy out of devPos[slot] (if one is in flight); its duration goes to kt.readback

@@ -2,7 +2,6 @@
 #include "sph_handle.h"
 
 #include <cmath>
-#include <cstdlib>
 
 using namespace sph_host;
 
@@ -16,12 +15,9 @@ int sample_reserve(sph_handle *h, size_t points) {
     HIPCHK(h, hipStreamSynchronize(h->copy));
     h->sampleOut.pending = false;
     h->sampleValid = false;
-    if (h->sampleDev) (void)hipFree(h->sampleDev);
-    if (h->sampleHost) (void)hipHostFree(h->sampleHost);
-    h->sampleDev = h->sampleHost = nullptr;
     h->sampleCap = 0;
-    HIPCHK(h, hipMalloc(&h->sampleDev, points * sizeof(float)));
-    HIPCHK(h, hipHostMalloc(&h->sampleHost, points * sizeof(float), hipHostMallocDefault));
+    HIPCHK(h, h->sampleDev.alloc(points));
+    HIPCHK(h, h->sampleHost.alloc(points));
     h->sampleCap = points;
     return SPH_OK;
 }
@@ -62,8 +58,7 @@ int sph_sample_field(sph_handle *h, const SphSampleLattice *lat) {
     // step).  Phase 0: the table of the last step is the pre-integration one; the next step's grid is built
     // here, ahead, and that step consumes it.
     if (h->phase == 0 && h->n > 0 && (rc = build_grid_ahead(h))) return rc;
-    bool plain = false;
-    if (const char *e = getenv("SPH_SAMPLE_PLAIN")) plain = atoi(e) != 0;
+    const bool plain = plain_path("SPH_SAMPLE_PLAIN");
     if ((rc = outbound_fence(h, h->sampleOut))) return rc; // the previous sample's copy still reads the device buffer
     SampleArgs A{};
     A.nx = L.nx, A.ny = L.ny, A.nz = L.nz;
@@ -91,7 +86,7 @@ int sph_sample_field(sph_handle *h, const SphSampleLattice *lat) {
     h->sampleCount += 1;
     (plain ? h->samplePlainCalls : h->sampleTileCalls) += 1;
     h->sampleValid = false; // (until the copy is queued: the pinned buffer still holds the previous sample)
-    if ((rc = outbound_send(h, h->sampleOut, {{h->sampleHost, h->sampleDev, points * sizeof(float)}}))) return rc;
+    if ((rc = outbound_send(h, h->sampleOut, {{h->sampleHost.get(), h->sampleDev.get(), points * sizeof(float)}}))) return rc;
     h->sampleDim[0] = L.nx, h->sampleDim[1] = L.ny, h->sampleDim[2] = L.nz;
     h->sampleValid = true;
     return SPH_OK;

@@ -9,7 +9,7 @@ namespace {
 // = the first eighth of a layer's rows) lands on the same XCD and the launch waits for it -- N = 8 slabs of the
 // headline run over 100 steps, slowest slab: density 0.196 -> 0.149, force 0.285 -> 0.187 ms per step with the map
 // moved on by one XCD per layer.  (The single domain's 80 layers: within noise either way, default off.)
-int slab_rotate(const sph_handle *h) { return h->tileRotate >= 0 ? h->tileRotate : 1; }
+int slab_rotate(const sph_handle *h) { return h->knobs.xcdRotate >= 0 ? h->knobs.xcdRotate : 1; }
 
 // the sweeps' precondition: the last grid build sorted into `buf`
 int slab_sorted_ok(sph_handle *h, int buf) {
@@ -74,7 +74,7 @@ int sph_bind_buffers(sph_handle *h, void *pos4_a, void *vel4_a, void *pos4_b, vo
 }
 
 void *sph_get_stream(sph_handle *h) { return h ? (void *)h->compute : nullptr; }
-void *sph_slab_records(sph_handle *h) { return (h && h->opt.sweep == SPH_SWEEP_LIST) ? (void *)h->pv8 : nullptr; }
+void *sph_slab_records(sph_handle *h) { return (h && h->opt.sweep == SPH_SWEEP_LIST) ? (void *)h->pv8.get() : nullptr; }
 
 int sph_slab_sort_async(sph_handle *h, int src_buf, int src_offset, int count,
                         const uint32_t *thresholds, int nthr, void *bounds_dev_out) {
@@ -88,7 +88,7 @@ int sph_slab_sort_async(sph_handle *h, int src_buf, int src_offset, int count,
     hipStream_t s = h->compute;
     PairEvent *pe = nullptr;
     if ((rc = pair_begin(h, &h->kt.sort, &pe))) return rc;
-    h->ws.velSample = (h->quiet && h->useQuiet) ? h->vel4[src_buf] + src_offset : nullptr; // the filter's reference velocity
+    h->ws.velSample = (h->quiet && h->knobs.zeroPairFilter) ? h->vel4[src_buf] + src_offset : nullptr; // the filter's reference velocity
     h->ws.vrefOut = h->quietVref;
     int res = sph_sort_cells(h->ws, h->P, h->pos4[src_buf] + src_offset, count, key_bits(h), s, h->cellRange,
                              h->P.numCells); // (clears the cell table too)
@@ -98,7 +98,7 @@ int sph_slab_sort_async(sph_handle *h, int src_buf, int src_offset, int count,
     if (nthr > 0) {
         for (int k = 0; k < nthr; ++k) X.thr.v[k] = thresholds[k];
         X.nthr = nthr;
-        X.bounds = bounds_dev_out ? static_cast<int *>(bounds_dev_out) : h->boundsDev;
+        X.bounds = bounds_dev_out ? static_cast<int *>(bounds_dev_out) : h->boundsDev.get();
     }
     sph_launch_gather(h->pos4[src_buf] + src_offset, h->vel4[src_buf] + src_offset,
                       h->ws.vals[res], h->ws.keys[res], h->pos4[src_buf ^ 1],

@@ -48,7 +48,7 @@ int key_bits(const sph_handle *h) {
 
 // xcd_tile() chunk: an eighth of one z-layer's worth of 256-particle tiles.
 int tile_chunk(const sph_handle *h, int count, int layers) {
-    if (h->tileChunkEnv >= 0) return h->tileChunkEnv;
+    if (h->knobs.tileChunk >= 0) return h->knobs.tileChunk;
     if (layers <= 0) return 0;
     const long long tiles = ((long long)count + 255) / 256;
     return (int)(tiles / (8ll * layers)); // 0 (contiguous eighths) when a layer is under 8 tiles
@@ -74,7 +74,7 @@ SweepArgs make_sweep_args(sph_handle *h) {
     A.patchHalo = 0;
     A.n_all = h->n;
     A.tileChunk = tile_chunk(h, h->n, h->zLayers);
-    A.tileRotate = h->tileRotate > 0 ? h->tileRotate : 0;
+    A.tileRotate = h->knobs.xcdRotate > 0 ? h->knobs.xcdRotate : 0;
     A.maskPool = h->maskPool;
     A.maskOff = h->maskOff;
     A.noneList = h->noneList;
@@ -84,7 +84,7 @@ SweepArgs make_sweep_args(sph_handle *h) {
     A.pv8 = h->pv8;
     // (slabs: the wave origin is rounded down to a multiple of 64, the gather launch clears the array,
     // so halo rows -- whose densities arrive after the density sweep -- stay "not quiet")
-    A.quiet = (h->useQuiet && h->quiet) ? h->quiet : nullptr;
+    A.quiet = h->knobs.zeroPairFilter ? h->quiet.get() : nullptr;
     A.calm = h->calm;
     A.quietAll = A.quiet ? reinterpret_cast<uint32_t *>(h->quietVref + 1) : nullptr;
     A.quietHalo = nullptr; // (slab launches next to a halo layer set it: slab_halo_quiet)
@@ -102,7 +102,7 @@ GatherExtras gather_extras(sph_handle *h) {
         X.cursorWords = (int)(kCursorBytes / sizeof(unsigned long long));
         h->cursorClean = true;
     }
-    if (h->quiet && h->useQuiet) {
+    if (h->quiet && h->knobs.zeroPairFilter) {
         X.vref = h->quietVref;
         X.calm = h->calm;
         X.quietAll = reinterpret_cast<uint32_t *>(h->quietVref + 1);
@@ -134,7 +134,7 @@ int resolve_events(sph_handle *h, StepEvents &se) {
     h->kt.steps += 1;
     se.counted = true;
     se.used = false;
-    if (h->trace && h->trBase && se.hasCopy) { // GPU-side timeline (ms since the first traced step began)
+    if (h->knobs.stepTrace && h->trBase && se.hasCopy) { // GPU-side timeline (ms since the first traced step began)
         float t0 = 0, t3 = 0, t5 = 0, c0 = 0, c1 = 0;
         if (hipEventElapsedTime(&t0, h->trBase, se.e[0]) == hipSuccess && hipEventElapsedTime(&t3, h->trBase, se.e[3]) == hipSuccess &&
             hipEventElapsedTime(&t5, h->trBase, se.e[5]) == hipSuccess && hipEventElapsedTime(&c0, h->trBase, se.c[0]) == hipSuccess &&
@@ -218,8 +218,8 @@ int outbound_fence(sph_handle *h, Outbound &o) {
 }
 
 int outbound_send(sph_handle *h, Outbound &o, std::initializer_list<OutboundCopy> copies) {
-    if (!o.done) HIPCHK(h, hipEventCreateWithFlags(&o.done, hipEventDisableTiming));
-    if (!o.copied) HIPCHK(h, hipEventCreateWithFlags(&o.copied, hipEventDisableTiming));
+    HIPCHK(h, o.done.create(hipEventDisableTiming));
+    HIPCHK(h, o.copied.create(hipEventDisableTiming));
     HIPCHK(h, hipEventRecord(o.done, h->compute));
     HIPCHK(h, hipStreamWaitEvent(h->copy, o.done, 0));
     for (const OutboundCopy &c : copies) HIPCHK(h, hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, h->copy));
@@ -313,7 +313,7 @@ int sph_phase_grid(sph_handle *h) {
     h->cellCur ^= 1;
     if (h->clickValid && h->cellTable[h->cellCur] == h->clickTable) h->cellCur ^= 1;
     h->cellRange = h->cellTable[h->cellCur];
-    h->ws.velSample = (h->quiet && h->useQuiet) ? h->vel4[c] : nullptr; // the zero-pair filter's reference velocity
+    h->ws.velSample = (h->quiet && h->knobs.zeroPairFilter) ? h->vel4[c] : nullptr; // the zero-pair filter's reference velocity
     h->ws.vrefOut = h->quietVref;
     int res = sph_sort_cells(h->ws, h->P, h->pos4[c], n, key_bits(h), s, h->cellRange, h->P.numCells);
     if (ev) HIPCHK(h, hipEventRecord(ev->e[2], s));
@@ -417,7 +417,7 @@ int sph_phase_readback(sph_handle *h) {
 int sph_step(sph_handle *h, SphTimes *times) {
     if (!h) return SPH_EINVAL;
     const auto trIn = std::chrono::steady_clock::now();
-    if (h->trace && h->trSteps > 0) h->trBetween += std::chrono::duration<double>(trIn - h->trLastReturn).count();
+    if (h->knobs.stepTrace && h->trSteps > 0) h->trBetween += std::chrono::duration<double>(trIn - h->trLastReturn).count();
     if (h->external) return reject_slab_mode(h);
     if (!h->ready) return fail(h, SPH_ESTATE, "setup()/upload_state() must come first");
     if (h->phase != 0 && h->phase != 3 && !(h->gridAhead && h->phase == 1))
@@ -431,13 +431,13 @@ int sph_step(sph_handle *h, SphTimes *times) {
     h->rbDeferredSlot = -1;
     auto trT = std::chrono::steady_clock::now();
     auto trLap = [&](int k) {
-        if (!h->trace) return;
+        if (!h->knobs.stepTrace) return;
         const auto now = std::chrono::steady_clock::now();
         h->trPh[k] += std::chrono::duration<double>(now - trT).count();
         trT = now;
     };
-    if (h->trace && !h->trBase && !h->gridAhead) {
-        if (hipEventCreate(&h->trBase) == hipSuccess) (void)hipEventRecord(h->trBase, h->compute);
+    if (h->knobs.stepTrace && !h->trBase && !h->gridAhead) {
+        if (h->trBase.create() == hipSuccess) (void)hipEventRecord(h->trBase, h->compute);
     }
     if (h->gridAhead) { // the previous timed step queued this step's grid build (and recorded its events)
         ev = h->aheadEv;
@@ -467,7 +467,7 @@ int sph_step(sph_handle *h, SphTimes *times) {
             HIPCHK(h, hipStreamSynchronize(h->compute));
         }
         const auto trB = std::chrono::steady_clock::now();
-        if (h->trace) {
+        if (h->knobs.stepTrace) {
             h->trEnqueue += std::chrono::duration<double>(trA - trIn).count();
             h->trSync += std::chrono::duration<double>(trB - trA).count();
         }
@@ -493,7 +493,7 @@ int sph_step(sph_handle *h, SphTimes *times) {
                 std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         }
         times->iters += 1;
-        if (h->trace) {
+        if (h->knobs.stepTrace) {
             h->trLastReturn = std::chrono::steady_clock::now();
             h->trPost += std::chrono::duration<double>(h->trLastReturn - trB).count();
             h->trSteps++;
