@@ -35,7 +35,15 @@ extern "C" {
 #define SPH_ENODEV (-5)  /* no usable GPU                               */
 
 /* Layout-identical to the reference's `struct Settings` (simulator.h:19-31):
- * bool, int, 6 floats = 32 bytes.  numCellsPerDim is a float there too. */
+ * bool, int, 6 floats = 32 bytes.  numCellsPerDim is a float there too.
+ *
+ * Grids: sph_create accepts 1 <= numCellsPerDim <= 1024 and any h > 0.  The library flattens cell
+ * coordinates in integers, key = cx + cy D + cz D^2.  The reference (and the CPU oracle) flatten in
+ * fp32, which is exact only while every key formed stays below 2^24: D <= 256, or D = 257 with every
+ * particle below z-layer 253.  Up to there the library equals the reference's arithmetic bit for bit
+ * (tests/test_gpu_grids.py); above it the reference's own keys collide and the integer keys are the
+ * definition.  D = 1 is accepted, but its wall planes sit at h and boxDim - h = 0: the first step
+ * clamps every particle to h, outside the one-cell grid. */
 typedef struct SphSettings {
     uint8_t randomInit;
     uint8_t pad_[3];
@@ -125,7 +133,8 @@ int sph_default_settings(SphSettings *out, int numParticles, int randomInit);
  * (the slab driver splits this array across ranks). */
 int sph_initial_positions(const SphSettings *settings, float *pos_xyz);
 
-/* Simulator::Simulator (simulator.cu:370-375).  Copies *settings. */
+/* Simulator::Simulator (simulator.cu:370-375).  Copies *settings.  SPH_EINVAL unless h > 0 and
+ * 1 <= numCellsPerDim <= 1024 (see SphSettings for what D > 256 and D = 1 mean). */
 int sph_create(const SphSettings *settings, const SphOptions *options,
                sph_handle **out);
 /* Simulator::~Simulator (simulator.cu:377-405). */

@@ -299,9 +299,8 @@ def h025_settings(settings_factory):
     s.boxDim = 8.0
     s.numCellsPerDim = 32
     s.timestep = 0.004
-    h = F32(s.h)
-    s.v_kernel_coeff = float(F32(45.0) / (F32(3.14159265) * F32(float(h) ** 6)))
-    s.d_kernel_coeff = float(F32(315.0) / (F32(64.0) * F32(3.14159265) * F32(float(h) ** 9)))
+    from grid_states import kernel_coeffs
+    s.v_kernel_coeff, s.d_kernel_coeff = kernel_coeffs(s.h)
     return s
 
 

@@ -10,6 +10,7 @@ import pytest
 
 import cudafluidsimulator_amd as sph
 from cudafluidsimulator_amd import _lib
+from grid_states import kernel_coeffs
 from helpers import assert_bit_equal, clustered_state, dense_block, random_state
 from oracle import oracle as O
 
@@ -582,9 +583,7 @@ def _custom_pair(hh, cells, n, pos, vel, sweep, dt=0.002):
     s.boxDim = hh * cells
     s.numCellsPerDim = cells
     s.timestep = dt
-    h = np.float32(s.h)
-    s.v_kernel_coeff = float(np.float32(45.0) / (np.float32(3.14159265) * np.float32(float(h) ** 6)))
-    s.d_kernel_coeff = float(np.float32(315.0) / (np.float32(64.0) * np.float32(3.14159265) * np.float32(float(h) ** 9)))
+    s.v_kernel_coeff, s.d_kernel_coeff = kernel_coeffs(s.h)
     sim = sph.Simulator(s, sweep=sweep)
     sim.upload_state(pos, vel)
     ref = O.OracleSim(n, False)

@@ -67,3 +67,35 @@ def test_adversarial_digit_patterns():
     check(np.where(i % 2 == 0, 0, (1 << 20) - 1))
     check((n - i) % 1024 + ((i // 4096) % 1024 << 10))
     check(np.full(n, (1 << 20) - 1))
+
+
+# ---- every plan of sort.hip's digit_bits() / sort_impl(): key widths at both ends of each ----
+
+PLANS = {8: "1 x 8", 10: "1 x 10", 16: "8 + 8", 20: "10 + 10", 24: "8 + 8 + 8", 30: "10 + 10 + 10", 32: "4 x 8"}   # widest key of each
+PLAN_WIDTHS = [1, 3, 8, 9, 10, 11, 16, 17, 24, 25, 30, 31, 32]
+
+
+def random_keys(n, bits, seed):
+    keys = np.random.default_rng(seed).integers(0, 1 << bits, n, dtype=np.uint64).astype(np.uint32)
+    keys[n // 2] = (1 << bits) - 1          # the largest key of the width (32 bits: 0xFFFFFFFF)
+    return keys
+
+
+@pytest.mark.parametrize("bits", PLAN_WIDTHS)
+def test_every_sort_plan_at_its_narrowest_and_widest_key(bits):
+    """One pass (the result lands in the second buffer), two (back in the first), three and four, with 8- and 10-bit
+    digits; the top digit of the narrowest key of a plan uses a single bit of its pass."""
+    keys = random_keys(5003, bits, bits)
+    assert int(keys.max()) == (1 << bits) - 1
+    check(keys, bits=bits)
+
+
+@pytest.mark.parametrize("bits", list(PLANS))
+def test_all_equal_keys_on_every_sort_plan(bits):
+    check(np.full(5003, (1 << bits) - 1, dtype=np.uint32), bits=bits)
+
+
+@pytest.mark.parametrize("bits", [8, 25, 32])
+def test_big_tiles_with_odd_and_even_pass_counts(bits):
+    """n >= RS_SMALL_N: 4096-key tiles, one, three and four passes"""
+    check(random_keys(1572864 + 5, bits, 100 + bits), bits=bits)
