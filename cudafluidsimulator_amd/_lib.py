@@ -26,6 +26,7 @@ EXPORTED_SYMBOLS = [
     "sph_render_frame", "sph_frame_host", "sph_download_frame_buffers", "sph_get_render_time", "sph_api_version",
     "sph_render_field", "sph_download_field_buffer", "sph_field_range",
     "sph_sample_field", "sph_sample_host", "sph_get_sample_time",
+    "sph_extract_surface", "sph_surface_host", "sph_get_surface_time",
     "sph_diagnose", "sph_diagnostics_host", "sph_diagnostics_values", "sph_diagnostics_add",
     "sph_get_diagnostics_time", "sph_slab_diagnose",
 ]
@@ -36,6 +37,7 @@ SPH_HAS_FIELD_FRAME = 1
 SPH_FIELD_SPEED, SPH_FIELD_DENSITY, SPH_FIELD_PRESSURE = 0, 1, 2
 FIELDS = {"speed": SPH_FIELD_SPEED, "density": SPH_FIELD_DENSITY, "pressure": SPH_FIELD_PRESSURE}
 SPH_HAS_FIELD_SAMPLE = 1
+SPH_HAS_SURFACE = 1
 SPH_HAS_DIAGNOSTICS = 1
 DIAG_SUMS = ("x", "y", "z", "vx", "vy", "vz", "rho", "prs", "v2")   # SPH_DIAG_SUM_*
 DIAG_EXTREMA = ("x", "y", "z", "speed", "rho", "prs")               # SPH_DIAG_EXT_*
@@ -79,6 +81,11 @@ class SphFieldFrameOptions(C.Structure):
 class SphSampleLattice(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32),
                 ("origin", C.c_float * 3), ("spacing", C.c_float * 3), ("field", C.c_int32)]
+
+
+class SphSurfaceOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32),
+                ("origin", C.c_float * 3), ("spacing", C.c_float * 3), ("iso", C.c_float)]
 
 
 class SphSum128(C.Structure):
@@ -221,6 +228,9 @@ def load_library():
     L.sph_sample_host.argtypes = [hp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.sph_sample_host.restype = fp
     L.sph_get_sample_time.argtypes = [hp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]
+    L.sph_extract_surface.argtypes = [hp, C.POINTER(SphSurfaceOptions)]
+    L.sph_surface_host.argtypes = [hp, C.POINTER(fp), C.POINTER(C.c_int64), C.POINTER(u32p), C.POINTER(C.c_int64)]
+    L.sph_get_surface_time.argtypes = [hp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]
     L.sph_diagnose.argtypes = [hp, C.POINTER(SphDiagnosticsOptions)]
     L.sph_diagnostics_host.argtypes = [hp, C.POINTER(SphDiagnosticsRaw)]
     L.sph_diagnostics_values.argtypes = [C.POINTER(SphDiagnosticsRaw), C.POINTER(SphSettings), C.POINTER(SphDiagnostics)]

@@ -92,6 +92,37 @@ static bool write_slice(Simulator *simulator, const char *dir, int f, int field)
     return (fclose(out) == 0) && ok;
 }
 
+// SPH_FREE_SURFACE=<iso>: beside each frame the surface density == iso (sph_extract_surface) over 101^3 lattice
+// points on [0, boxDim]^3, as <dir>/surface_%04d.ply: binary little-endian PLY, `float x y z` vertices and
+// `list uchar int vertex_indices` faces -- binary keeps the vertices' bits.
+static bool write_surface(Simulator *simulator, const char *dir, int f, float iso) {
+    const int N = 101;
+    const float sp = simulator->settings->boxDim / (float)(N - 1);
+    const float origin[3] = {0.f, 0.f, 0.f}, spacing[3] = {sp, sp, sp};
+    const float *verts = NULL;
+    const unsigned *tris = NULL;
+    long long nv = 0, nt = 0;
+    if (!simulator->extractSurface(iso, origin, spacing, N, N, N, &verts, &nv, &tris, &nt)) return false;
+    char name[32];
+    snprintf(name, sizeof name, "/surface_%04d.ply", f);
+    const std::string path = std::string(dir) + name;
+    FILE *out = fopen(path.c_str(), "wb");
+    if (!out) {
+        fprintf(stderr, "sph: cannot write %s\n", path.c_str());
+        return false;
+    }
+    fprintf(out, "ply\nformat binary_little_endian 1.0\nelement vertex %lld\nproperty float x\nproperty float y\nproperty float z\n"
+                 "element face %lld\nproperty list uchar int vertex_indices\nend_header\n", nv, nt);
+    bool ok = nv == 0 || fwrite(verts, 12, (size_t)nv, out) == (size_t)nv;
+    std::string faces((size_t)nt * 13, '\0'); // per face: the count 3, then three 32-bit indices
+    for (long long t = 0; t < nt; ++t) {
+        faces[(size_t)t * 13] = 3;
+        memcpy(&faces[(size_t)t * 13 + 1], tris + 3 * t, 12);
+    }
+    ok = ok && fwrite(faces.data(), 1, faces.size(), out) == faces.size();
+    return (fclose(out) == 0) && ok;
+}
+
 // SPH_FREE_STATS=1: for each written frame one JSON line of run diagnostics (Simulator::diagnostics) in
 // <dir>/stats.jsonl; doubles as %.17g, which reads back to the same double
 static bool write_stats(Simulator *simulator, FILE *out, int f) {
@@ -115,6 +146,14 @@ void startVisualization(Simulator *simulator) {
     if (const char *e = getenv("SPH_FREE_FRAME_EVERY")) every = atoi(e) > 0 ? atoi(e) : 1;
     const int field = framesDir ? shade_field() : -1;
     int slice = framesDir ? env_field("SPH_FREE_SLICE", "writing no slices") : -1;
+    float surfaceIso = 0.f; // 0: no surfaces
+    if (framesDir && getenv("SPH_FREE_SURFACE")) {
+        surfaceIso = strtof(getenv("SPH_FREE_SURFACE"), NULL);
+        if (!(surfaceIso > 0.f) || !std::isfinite(surfaceIso)) {
+            fprintf(stderr, "sph: SPH_FREE_SURFACE=%s is not a finite level > 0 -- writing no surfaces\n", getenv("SPH_FREE_SURFACE"));
+            surfaceIso = 0.f;
+        }
+    }
     FILE *stats = NULL;
     if (framesDir && getenv("SPH_FREE_STATS") && atoi(getenv("SPH_FREE_STATS")) != 0) {
         const std::string path = std::string(framesDir) + "/stats.jsonl";
@@ -129,6 +168,7 @@ void startVisualization(Simulator *simulator) {
         simulator->simulate();
         if (framesDir && f % every == 0 && !write_frame(simulator, framesDir, f, field)) framesDir = NULL;
         if (framesDir && slice >= 0 && f % every == 0 && !write_slice(simulator, framesDir, f, slice)) slice = -1;
+        if (framesDir && surfaceIso > 0.f && f % every == 0 && !write_surface(simulator, framesDir, f, surfaceIso)) surfaceIso = 0.f;
         if (framesDir && stats && f % every == 0 && !write_stats(simulator, stats, f)) {
             fclose(stats);
             stats = NULL;

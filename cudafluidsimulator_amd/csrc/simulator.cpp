@@ -171,6 +171,35 @@ const float *Simulator::sampleField(int field, const float origin[3], const floa
     return v;
 }
 
+bool Simulator::extractSurface(float iso, const float origin[3], const float spacing[3], int nx, int ny, int nz,
+                               const float **vertices, long long *numVertices, const unsigned **triangles, long long *numTriangles) {
+    if (multi) {
+        fprintf(stderr, "sph: extractSurface: a multi-GPU run (SPH_GPUS > 1) is not meshed\n");
+        return false;
+    }
+    if (!impl) return false;
+    SphSurfaceOptions o{};
+    o.struct_size = (int32_t)sizeof o;
+    o.nx = nx, o.ny = ny, o.nz = nz;
+    for (int k = 0; k < 3; ++k) o.origin[k] = origin[k], o.spacing[k] = spacing[k];
+    o.iso = iso;
+    const int rc = sph_extract_surface(impl, &o);
+    if (rc == SPH_ESTATE) { // (SPH_SWEEP=linked, a step split into phases, ...): nothing to mesh, nothing broken
+        fprintf(stderr, "sph: extractSurface: %s\n", sph_last_error(impl));
+        return false;
+    }
+    check(impl, rc, "sph_extract_surface");
+    const float *v = NULL;
+    const uint32_t *t = NULL;
+    int64_t nv = 0, nt = 0;
+    check(impl, sph_surface_host(impl, &v, &nv, &t, &nt), "sph_surface_host");
+    if (vertices) *vertices = v;
+    if (numVertices) *numVertices = nv;
+    if (triangles) *triangles = t;
+    if (numTriangles) *numTriangles = nt;
+    return true;
+}
+
 bool Simulator::diagnostics(SphDiagnostics *out, SphDiagnosticsRaw *raw) {
     if (!out || (!impl && !multi)) {
         fprintf(stderr, "sph: diagnostics: setup() must come first\n");

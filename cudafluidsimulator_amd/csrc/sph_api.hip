@@ -1,7 +1,7 @@
 // C-ABI implementation (include/sph_c_api.h) of the MI355X SPH step path.
 // Host logic only; the kernels live in sort.hip / grid.hip / sweeps.hip.
 // This unit: settings and initialisers, the handle's life cycle, uploads, downloads and counters; the step is
-// in sph_step.hip, the rest in sph_readback / sph_slab / sph_snapshot / sph_frame / sph_sample.hip (shared: sph_handle.h).
+// in sph_step.hip, the rest in sph_readback / sph_slab / sph_snapshot / sph_frame / sph_sample / sph_surface.hip (shared: sph_handle.h).
 // Compile with -ffp-contract=off (host initialisers must round like the
 // reference's g++ -O3 x86-64 build, Makefile:22-23).
 #include "sph_handle.h"
@@ -442,6 +442,8 @@ void sph_destroy(sph_handle *h) {
                 h->trPh[1] / h->trSteps * 1e6, h->trPh[2] / h->trSteps * 1e6, h->trPh[3] / h->trSteps * 1e6, h->trPh[4] / h->trSteps * 1e6);
     if (h->knobs.stepTrace && h->sampleTileCalls + h->samplePlainCalls > 0)
         fprintf(stderr, "sph sample trace: %lld samples by k_sample_tile, %lld by k_sample_plain\n", h->sampleTileCalls, h->samplePlainCalls);
+    if (h->knobs.stepTrace && h->surfWaveCalls + h->surfPlainCalls > 0)
+        fprintf(stderr, "sph surface trace: %lld extractions by the lane-exchange path, %lld by the plain path\n", h->surfWaveCalls, h->surfPlainCalls);
     if (h->compute) (void)hipStreamSynchronize(h->compute);
     if (h->copy) (void)hipStreamSynchronize(h->copy);
     sdma_destroy(h);

@@ -263,6 +263,28 @@ struct SampleArgs {
 // one value per lattice point into out[0, nx ny nz); plain = the one-thread-per-point check path
 void sph_launch_sample(const DevParams &P, const SampleArgs &A, bool plain, float *out, hipStream_t s);
 
+// ---- the surface mesh (surface.hip; defined in DESIGN.md section 10d) ----
+struct SurfaceArgs {
+    int nx, ny, nz;          // lattice points per axis, each >= 2; point (ix, iy, iz) has L = (iz ny + iy) nx + ix
+    float ox, oy, oz;        // origin
+    float sx, sy, sz;        // spacing
+    float iso;
+};
+struct SurfaceBuffers {
+    const float *field;          // [points] the density sample of the lattice
+    uint8_t *bits;               // [points] bit k: corner k of the point's cell is inside (a corner off the lattice: 0)
+    uint32_t *local;             // [points] vertices (low half) and triangles (high half) before the point in its block,
+                                 // written where the point owns a vertex
+    uint2 *blockSum, *blockOff;  // [sph_surface_blocks] (vertices, triangles) of a block, and before it
+    unsigned long long *totals;  // [2] vertices, triangles of the mesh
+};
+// blocks of the counting launch
+int sph_surface_blocks(const SurfaceArgs &A);
+// classify + count + scan: fills bits, local, blockSum, blockOff and totals from field
+void sph_launch_surface_count(const SurfaceArgs &A, bool plain, const SurfaceBuffers &B, hipStream_t s);
+// 3 floats per vertex into verts, 3 indices per triangle into tris, as many as *totals says
+void sph_launch_surface_emit(const SurfaceArgs &A, bool plain, const SurfaceBuffers &B, float *verts, uint32_t *tris, hipStream_t s);
+
 // ---- diagnostics (diag.hip; defined in DESIGN.md section 10c) ----
 // The result block on the device: every word an integer, written by integer atomics only.
 struct DiagBlock {

@@ -1,5 +1,6 @@
 // The handle behind include/sph_c_api.h and the few helpers its host translation units share (sph_api.hip,
-// sph_step.hip, sph_readback.hip, sph_slab.hip, sph_snapshot.hip, sph_frame.hip, sph_sample.hip, sph_diag.hip).  Host code only.
+// sph_step.hip, sph_readback.hip, sph_slab.hip, sph_snapshot.hip, sph_frame.hip, sph_sample.hip, sph_surface.hip, sph_diag.hip).
+// Host code only.
 // Ownership: every device buffer, pinned block and event below is a DeviceBuf / PinnedBuf / Event (sph_owned.h) and goes
 // with the handle; a raw pointer member is a view of one of them (or of the caller's memory) and says so.
 #pragma once
@@ -41,6 +42,7 @@ using sph_owned::PinnedBuf;
 //   SPH_RENDER_PLAIN      0        call    non-zero: sph_render_frame / sph_render_field take the check path
 //   SPH_SAMPLE_PLAIN      0        call    non-zero: sph_sample_field takes the one-thread-per-point check path
 //   SPH_DIAG_PLAIN        0        call    non-zero: sph_diagnose / sph_slab_diagnose take the check path
+//   SPH_SURFACE_PLAIN     0        call    non-zero: sph_extract_surface takes the check path, for its sample and its extraction
 //   SPH_MGPU_THREADS      0        (libsph_mgpu.so, its own object: sph_mgpu_create in mgpu_state.cpp) non-zero: one
 //                                          host thread per local slab
 // (The SPH_* variables the command-line front end reads -- SPH_SWEEP, SPH_GPUS, SPH_TRANSPORT, SPH_RECUT_EVERY,
@@ -75,7 +77,7 @@ struct PairEvent { // one timed section of the slab path
 constexpr int kPairRing = 48;
 
 // A result on its way to pinned memory over the copy stream, behind what `compute` had queued when it left
-// (outbound_* below): the frame, the field sample.
+// (outbound_* below): the frame, the field sample, the surface mesh.
 struct Outbound {
     Event done, copied; // on compute: the result is complete; on copy: it has arrived
     bool pending = false;  // a copy is queued: `copied` tells when the device buffer is free again
@@ -228,6 +230,30 @@ struct sph_handle {
     double sampleSeconds = 0;        // the sampling kernel, from HIP events (PairEvent ring)
     long long sampleCount = 0;
     long long sampleTileCalls = 0, samplePlainCalls = 0; // which kernel ran (SPH_STEP_TRACE=1: printed by sph_destroy)
+
+    // ---- sph_surface.hip ----
+    // The surface mesh (surface.hip): per lattice point the density sample, the corner byte and the block-relative
+    // offsets; per counting block its sums and offsets; the two totals; the mesh on the device and in pinned memory.
+    // All grown on demand by sph_extract_surface.
+    sph_host::DeviceBuf<float> surfField;
+    sph_host::DeviceBuf<uint8_t> surfBits;
+    sph_host::DeviceBuf<uint32_t> surfLocal;
+    sph_host::DeviceBuf<uint2> surfBlockSum, surfBlockOff;
+    sph_host::DeviceBuf<unsigned long long> surfTotalsDev;
+    sph_host::PinnedBuf<unsigned long long> surfTotalsHost;
+    sph_host::Event surfCounted;     // the totals have landed
+    size_t surfPointCap = 0, surfBlockCap = 0; // points / blocks the buffers above hold
+    sph_host::DeviceBuf<float> surfVertsDev;
+    sph_host::DeviceBuf<uint32_t> surfTrisDev;
+    sph_host::PinnedBuf<float> surfVertsHost;
+    sph_host::PinnedBuf<uint32_t> surfTrisHost;
+    size_t surfVertCap = 0, surfTriCap = 0; // vertices / triangles either buffer holds
+    long long surfVerts = 0, surfTris = 0;  // of the last extraction
+    sph_host::Outbound surfOut;      // the mesh on its way to surfVertsHost / surfTrisHost
+    bool surfValid = false;
+    double surfSampleSeconds = 0, surfExtractSeconds = 0; // the sampling kernel; count + scan + emit (PairEvent ring)
+    long long surfCount = 0;
+    long long surfWaveCalls = 0, surfPlainCalls = 0; // which path ran (SPH_STEP_TRACE=1: printed by sph_destroy)
 
     // ---- sph_diag.hip ----
     // Run diagnostics (diag.hip): the small result block on the device and in pinned memory, allocated by the

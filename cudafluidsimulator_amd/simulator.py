@@ -254,6 +254,36 @@ class Simulator:
                     "sph_get_sample_time")
         return sec.value, cnt.value
 
+    # -- the surface mesh: the density iso-surface as indexed triangles (sph_extract_surface) --
+    def extract_surface(self, iso, origin=(0.0, 0.0, 0.0), spacing=0.1, shape=(2, 2, 2)):
+        """The surface density == `iso` of the current state over the lattice origin + (ix, iy, iz) * spacing,
+        `shape` = (nz, ny, nx) as for sample_field, by marching tetrahedra on the device: {"vertices": float32
+        (V, 3), "triangles": uint32 (T, 3)}, arrays of their own.  Normals (a, b, c -> (b - a) x (c - a)) point out
+        of the fluid; the mesh is closed when the lattice's outer shell lies outside it."""
+        nz, ny, nx = (int(d) for d in shape)
+        o = _lib.SphSurfaceOptions()
+        o.struct_size = C.sizeof(_lib.SphSurfaceOptions)
+        o.nx, o.ny, o.nz = nx, ny, nz
+        o.origin[:] = [float(v) for v in origin]
+        o.spacing[:] = [float(s) for s in (spacing if np.ndim(spacing) else (spacing,) * 3)]
+        o.iso = float(iso)
+        self._check(self._L.sph_extract_surface(self._h, C.byref(o)), "sph_extract_surface")
+        vp, tp = C.POINTER(C.c_float)(), C.POINTER(C.c_uint32)()
+        nv, nt = C.c_int64(0), C.c_int64(0)
+        self._check(self._L.sph_surface_host(self._h, C.byref(vp), C.byref(nv), C.byref(tp), C.byref(nt)),
+                    "sph_surface_host")
+        verts = np.array(np.ctypeslib.as_array(vp, shape=(nv.value, 3)), copy=True) if nv.value else np.zeros((0, 3), np.float32)
+        tris = np.array(np.ctypeslib.as_array(tp, shape=(nt.value, 3)), copy=True) if nt.value else np.zeros((0, 3), np.uint32)
+        return {"vertices": verts, "triangles": tris}
+
+    def surface_time(self, reset=False):
+        """(sample_seconds, extract_seconds, calls): GPU time of the surface's sampling kernel and of its
+        count + scan + emit launches, summed over `calls` extractions."""
+        a, b, cnt = C.c_double(0), C.c_double(0), C.c_int64(0)
+        self._check(self._L.sph_get_surface_time(self._h, C.byref(a), C.byref(b), C.byref(cnt), 1 if reset else 0),
+                    "sph_get_surface_time")
+        return a.value, b.value, cnt.value
+
     # -- run diagnostics: exact sums, extrema and a histogram, reduced on the device (sph_diagnose) --
     def diagnose(self, hist=None, value_range=None):
         """Queue the reduction of the current state (sph_diagnose); does not block."""

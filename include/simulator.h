@@ -99,6 +99,12 @@ class Simulator {
     // until the next call.  NULL (with a message on stderr) with SPH_GPUS > 1 and where the library answers
     // SPH_ESTATE (SPH_SWEEP=linked has no cell table to walk).
     const float *sampleField(int field, const float origin[3], const float spacing[3], int nx, int ny, int nz);
+    // The surface density == iso over the same kind of lattice as an indexed triangle mesh (sph_extract_surface in
+    // sph_c_api.h): 3 floats per vertex, 3 indices per triangle, owned by the simulator, valid until the next call;
+    // the pointers may be NULL for an empty mesh.  false (with a message on stderr) with SPH_GPUS > 1 and where
+    // the library answers SPH_ESTATE.
+    bool extractSurface(float iso, const float origin[3], const float spacing[3], int nx, int ny, int nz,
+                        const float **vertices, long long *numVertices, const unsigned **triangles, long long *numTriangles);
     // Run diagnostics of the current state, reduced on the GPU (sph_diagnose in sph_c_api.h): total kinetic and
     // potential energy, momentum, centre of mass, the fastest particle, the CFL number, the spread of density.
     // *raw, if given, receives the exact words behind them.  With SPH_GPUS > 1 through the multi-GPU driver

@@ -437,6 +437,45 @@ const float *sph_sample_host(sph_handle *h, int *nx, int *ny, int *nz);
  * the step that consumes it), summed over `samples` calls. */
 int sph_get_sample_time(sph_handle *h, double *seconds, int64_t *samples, int reset);
 
+/* ---- the surface mesh: the density iso-surface as an indexed triangle mesh, extracted on the device ----
+ * Additive to version 3: test for SPH_HAS_SURFACE.  Defined to the bit in DESIGN.md section 10d ("The surface
+ * mesh"): marching tetrahedra over the values sph_sample_field returns for SPH_FIELD_DENSITY on the same lattice.
+ * A point is inside when f >= iso.  Every point owns up to seven edges, towards (1,0,0) (0,1,0) (0,0,1) (1,1,0)
+ * (1,0,1) (0,1,1) (1,1,1); an edge whose ends differ carries one vertex at p_a + t (p_b - p_a), t = (iso - f_a) /
+ * (f_b - f_a), a the owner, all fp32 and rounded on their own.  Vertices are numbered by owner L = (iz ny + iy) nx + ix,
+ * then direction; triangles by cell L, then by the six tetrahedra of the cell, wound so that normals point out of
+ * the fluid.  Degenerate triangles (f == iso at a point) stay.  The mesh is closed when the lattice's outer shell
+ * is outside the fluid, open where the surface leaves the lattice. */
+#define SPH_HAS_SURFACE 1
+typedef struct SphSurfaceOptions {
+    int32_t struct_size;     /* = sizeof(SphSurfaceOptions) */
+    int32_t nx, ny, nz;      /* each 2..4096, nx*ny*nz <= 1<<24 */
+    float origin[3];         /* finite */
+    float spacing[3];        /* finite, > 0 */
+    float iso;               /* finite, > 0 */
+} SphSurfaceOptions;
+/* Extracts the surface of the state the handle holds NOW and queues the copy of the mesh to pinned host memory.
+ * State rules, grid handling and error codes are sph_sample_field's: the grid is found or built ahead in the same
+ * way (sph_download_grid returns the one that was walked) and no result of any step depends on the call;
+ * SPH_ESTATE before any state, inside an open phase-split step, for a handle in slab mode and with
+ * SPH_SWEEP_LINKED / SPH_KEY_MORTON; SPH_EINVAL for a NULL opt, struct_size not set, dimensions out of range, a
+ * non-finite origin, a spacing that is not finite and > 0, an iso that is not finite and > 0.  The values of the
+ * last sph_sample_field are left alone: the surface samples into a buffer of its own.
+ * Unlike sph_sample_field the call waits on the host once, for the two totals (16 bytes), to size the mesh; the
+ * device and pinned buffers grow on demand; then it queues the emit and the copy and returns.  No particles, or no
+ * edge that crosses iso: 0 vertices, 0 triangles, SPH_OK.  SPH_SURFACE_PLAIN=1 in the environment selects the check
+ * path for the sample and the extraction (one thread per point, every corner loaded from global memory; the same
+ * mesh). */
+int sph_extract_surface(sph_handle *h, const SphSurfaceOptions *opt);
+/* The mesh of the last sph_extract_surface: 3 floats per vertex, 3 vertex indices per triangle, owned by the handle,
+ * valid until the next extraction.  Blocks until the copy has landed.  Any out-pointer may be NULL; with 0 vertices
+ * (triangles) the pointer returned may be NULL.  SPH_ESTATE before the first extraction. */
+int sph_surface_host(sph_handle *h, const float **vertices_xyz, int64_t *num_vertices,
+                     const uint32_t **triangles, int64_t *num_triangles);
+/* GPU time of the surface's sampling kernel and of its count + scan + emit launches (HIP events on the compute
+ * stream), summed over `calls` extractions. */
+int sph_get_surface_time(sph_handle *h, double *sample_seconds, double *extract_seconds, int64_t *calls, int reset);
+
 /* ---- run diagnostics: exact sums, extrema and a histogram of the state, reduced on the device ----
  * Additive to version 3: test for SPH_HAS_DIAGNOSTICS.  Defined to the bit in DESIGN.md section 10c ("Diagnostics").
  * The rows are those sph_render_field reads, (x, y, z, vx, vy, vz, rho) per particle as sph_download_state returns
