@@ -2,8 +2,9 @@
 
 TEST INFRASTRUCTURE ONLY: importable from tests/, __graft_entry__.smoke() and
 bench.py's cpu_baseline leg.  The product package (cudafluidsimulator_amd) never
-imports this module.  Parity is unpinned by reference tests (the reference has
-none); see sph_oracle.h.
+imports this module.  Pinned bit for bit to the reference's kernels executed on the
+host, under the schedule that yields the canonical order, on the cases of
+tests/test_reference_pin_cpu.py (oracle/reference.py); see sph_oracle.h.
 """
 import ctypes as C
 import os

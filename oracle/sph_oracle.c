@@ -1,7 +1,7 @@
 /*
  * sph_oracle.c -- CPU oracle for the SPH step path.  TEST INFRASTRUCTURE ONLY.
- * See sph_oracle.h for scope, the canonical-order decision and the statement
- * that parity is UNPINNED by any reference test or fixture (there are none).
+ * See sph_oracle.h for scope, the canonical-order decision and what pins it:
+ * the reference's own kernels executed on the host, bit for bit.
  *
  * Build: gcc -O2 -ffp-contract=off -fopenmp -fPIC -shared (oracle/Makefile).
  * -ffp-contract=off is REQUIRED: every operation below must round on its own.

@@ -8,10 +8,15 @@
  * src/simulator.h:6-12.  Only tests/, __graft_entry__.smoke() and bench.py's
  * cpu_baseline leg may load it; the product (libsph_hip.so, ./sph) never does.
  *
- * PARITY UNPINNED BY REFERENCE TESTS: the reference ships no tests, fixtures or
- * golden vectors for this path and its CUDA source cannot be compiled or run
- * here (no nvcc, no NVIDIA device).  The oracle is pinned only by hand-derived
- * known-answer values (tests/test_oracle_known_answers.py).
+ * PINNED TO THE REFERENCE'S OWN KERNELS: the reference ships no tests, fixtures
+ * or golden vectors, but its simulator.cu compiles for the host against a small
+ * stand-in for the CUDA runtime (oracle/ref_host/, oracle/Makefile target ref).
+ * Run serially, with kernelBuildGrid's threads in the schedule that yields the
+ * canonical order below, it equals this oracle bit for bit in pos, vel, rho, prs
+ * and force on the cases of tests/test_reference_pin_cpu.py (goldens, grids of 1
+ * to 257 cells, clicks, cut-offs, other h, both initialisers).  Hand-derived
+ * known answers pin it as well (SURVEY.md Appendix D;
+ * tests/test_oracle_known_answers.py).
  *
  * The reference's neighbour lists are built by an atomicCAS race
  * (simulator.cu:44-55), so its summation order -- and therefore its last-ulp

@@ -1,13 +1,17 @@
 """Generates tests/golden/*.npz from the CPU oracle (oracle/sph_oracle.c).
 
-The reference holds no golden vectors for this path and its CUDA
-source cannot run here, so these fixtures are ORACLE outputs: they pin the HIP
-path and the oracle to each other across rounds, not to the reference.  Data
-only: inputs are regenerated from seeds / the reference initialisers.
+The reference holds no golden vectors for this path, so these
+fixtures are ORACLE outputs.  The oracle is pinned bit for bit to the reference's kernels
+executed on the host, under the schedule that yields the canonical order: the three array
+fixtures are re-derived from the reference's code, every stored array, by
+tests/test_reference_pin_cpu.py, and --reference writes digests that the reference build
+itself produced.  Data only: inputs are regenerated from seeds / the reference initialisers.
 Run:  python tests/golden/make_golden.py          (the small array fixtures)
       python tests/golden/make_golden.py --full   (sha256 of the n = 4,194,304 run)
       python tests/golden/make_golden.py --config4 | --config5   (first steps of configs 4 / 5 at full size)
       python tests/golden/make_golden.py --morton  (Morton-keyed oracle, n = 4,194,304, moving state, steps 1 and 3)
+      python tests/golden/make_golden.py --reference   (reference_pin.json: digests of the REFERENCE's kernels run on
+                                                        the host, oracle/reference.py; needs the reference build)
 """
 import os
 import sys
@@ -153,7 +157,23 @@ def big_config_checksums(n, random_init, checkpoints):
         json.dump(out, f, indent=1)
 
 
+def reference_pin():
+    """tests/golden/reference_pin.json: per case of tests/reference_pin_cases.JSON_CASES the sha256 of the inputs and,
+    after every step, of pos, vel, rho and prs by particle id as the reference's own kernels produce them on the host
+    under the canonical build schedule.  Data only; byte-identical when regenerated."""
+    import reference_pin_cases as P
+    from oracle import reference as R
+    if not R.available():
+        sys.exit("no oracle/_ref/libsph_reference.so: build() makes it where the reference's sources are present")
+    with open(P.PIN_JSON, "w") as f:
+        f.write(P.dump(P.reference_digests()))
+    print(P.PIN_JSON, os.path.getsize(P.PIN_JSON), "bytes")
+
+
 if __name__ == "__main__":
+    if "--reference" in sys.argv:
+        reference_pin()
+        sys.exit(0)
     if "--morton" in sys.argv:
         morton_checksums()
         sys.exit(0)

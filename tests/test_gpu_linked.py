@@ -5,7 +5,10 @@ The order of a list is decided by a race, exactly as in the reference, so every
 fp32 sum may be taken in a different order from the oracle's canonical one:
 results are compared at the north star's tolerance (1e-5 relative), NOT bit for
 bit -- except where a sum has at most two terms (fp32 addition is commutative).
-The oracle itself is pinned only by analytic known answers (parity unpinned)."""
+The oracle itself is pinned bit for bit to the reference's kernels executed on the host
+under the schedule that yields the canonical order; under another schedule those same
+kernels differ from it by rounding of this size (tests/test_reference_pin_cpu.py,
+DESIGN.md section 2)."""
 import numpy as np
 import pytest
 

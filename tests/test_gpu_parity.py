@@ -1,8 +1,8 @@
 """HIP path vs the CPU oracle through the C-ABI (cudafluidsimulator_amd.Simulator
 is a thin ctypes mirror of it).  Strict mode is BIT-EXACT: every comparison
-below is on the raw fp32 words.  The oracle itself is pinned only by analytic
-known answers -- the reference has no fixtures (parity unpinned, see
-test_oracle_known_answers.py)."""
+below is on the raw fp32 words.  The oracle itself is pinned by analytic
+known answers (test_oracle_known_answers.py) and, bit for bit, to the reference's own kernels
+executed on the host (test_reference_pin_cpu.py; the reference has no fixtures)."""
 import os
 
 import numpy as np

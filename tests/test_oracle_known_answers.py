@@ -1,7 +1,8 @@
 """Pins the CPU oracle.  The reference ships NO tests, fixtures or golden data
-(SURVEY.md section 4), so parity is unpinned by reference artefacts; what pins the
-oracle are these known-answer values, hand-derived from the cited reference
-formulas in strict fp32."""
+(SURVEY.md section 4).  These known-answer values, hand-derived from the cited reference
+formulas in strict fp32, pin the oracle on any machine; where the
+reference's sources are present tests/test_reference_pin_cpu.py pins it bit for bit to the
+reference's own kernels executed on the host."""
 import numpy as np
 import pytest
 
