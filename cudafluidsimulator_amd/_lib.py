@@ -29,6 +29,7 @@ EXPORTED_SYMBOLS = [
     "sph_extract_surface", "sph_surface_host", "sph_get_surface_time",
     "sph_diagnose", "sph_diagnostics_host", "sph_diagnostics_values", "sph_diagnostics_add",
     "sph_get_diagnostics_time", "sph_slab_diagnose",
+    "sph_tracers_set", "sph_tracers_advect", "sph_tracers_host", "sph_get_tracer_stats",
 ]
 SPH_API_VERSION = 3
 SPH_SHADE_FLAT, SPH_SHADE_COUNT = 0, 1
@@ -39,6 +40,8 @@ FIELDS = {"speed": SPH_FIELD_SPEED, "density": SPH_FIELD_DENSITY, "pressure": SP
 SPH_HAS_FIELD_SAMPLE = 1
 SPH_HAS_SURFACE = 1
 SPH_HAS_DIAGNOSTICS = 1
+SPH_HAS_TRACERS = 1
+MAX_TRACERS = 1 << 24
 DIAG_SUMS = ("x", "y", "z", "vx", "vy", "vz", "rho", "prs", "v2")   # SPH_DIAG_SUM_*
 DIAG_EXTREMA = ("x", "y", "z", "speed", "rho", "prs")               # SPH_DIAG_EXT_*
 DIAG_BINS = 256
@@ -150,6 +153,12 @@ def diagnostics_dict(raw, settings):
     return out
 
 
+class SphTracerStats(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("pad_", C.c_int32), ("calls", C.c_int64),
+                ("waves_shared", C.c_uint64), ("waves_direct", C.c_uint64), ("groups", C.c_uint64),
+                ("seconds", C.c_double)]
+
+
 class SphKernelTimes(C.Structure):
     _fields_ = [("hash", C.c_double), ("sort", C.c_double), ("gather", C.c_double),
                 ("density", C.c_double), ("force", C.c_double), ("readback", C.c_double),
@@ -237,5 +246,9 @@ def load_library():
     L.sph_diagnostics_add.argtypes = [C.POINTER(SphDiagnosticsRaw), C.POINTER(SphDiagnosticsRaw)]
     L.sph_get_diagnostics_time.argtypes = [hp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]
     L.sph_slab_diagnose.argtypes = [hp, C.c_int, C.c_int, C.c_int, C.POINTER(SphDiagnosticsOptions)]
+    L.sph_tracers_set.argtypes = [hp, fp, C.c_int]
+    L.sph_tracers_advect.argtypes = [hp, C.c_float]
+    L.sph_tracers_host.argtypes = [hp, C.POINTER(fp), C.POINTER(fp), C.POINTER(C.c_int)]
+    L.sph_get_tracer_stats.argtypes = [hp, C.POINTER(SphTracerStats), C.c_int]
     _lib = L
     return L

@@ -123,6 +123,41 @@ static bool write_surface(Simulator *simulator, const char *dir, int f, float is
     return (fclose(out) == 0) && ok;
 }
 
+// SPH_FREE_TRACERS=<count>: `count` passive tracers (sph_tracers_*), seeded at the setup positions of the particles
+// with ids k n / count, advected by `timestep` after every frame; beside each written frame their state as
+// <dir>/tracers_%04d.ply: binary little-endian PLY, vertex properties `float x y z vx vy vz density`.
+static bool seed_tracers(Simulator *simulator, int count) {
+    const int n = simulator->settings->numParticles;
+    const float3 *p = simulator->getPosition();
+    if (!p || n <= 0) return false;
+    std::string seeds((size_t)count * 12, '\0');
+    for (int k = 0; k < count; ++k) memcpy(&seeds[(size_t)k * 12], &p[(long long)k * n / count], 12);
+    return simulator->setTracers(reinterpret_cast<const float *>(seeds.data()), count);
+}
+static bool write_tracers(Simulator *simulator, const char *dir, int f) {
+    const float *pd = NULL, *u = NULL;
+    int m = 0;
+    if (!simulator->getTracers(&pd, &u, &m)) return false;
+    char name[32];
+    snprintf(name, sizeof name, "/tracers_%04d.ply", f);
+    const std::string path = std::string(dir) + name;
+    FILE *out = fopen(path.c_str(), "wb");
+    if (!out) {
+        fprintf(stderr, "sph: cannot write %s\n", path.c_str());
+        return false;
+    }
+    fprintf(out, "ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+                 "property float vx\nproperty float vy\nproperty float vz\nproperty float density\nend_header\n", m);
+    std::string rows((size_t)m * 28, '\0');
+    for (int i = 0; i < m; ++i) {
+        memcpy(&rows[(size_t)i * 28], pd + 4 * (size_t)i, 12);
+        memcpy(&rows[(size_t)i * 28 + 12], u + 4 * (size_t)i, 12);
+        memcpy(&rows[(size_t)i * 28 + 24], pd + 4 * (size_t)i + 3, 4);
+    }
+    const bool ok = fwrite(rows.data(), 1, rows.size(), out) == rows.size();
+    return (fclose(out) == 0) && ok;
+}
+
 // SPH_FREE_STATS=1: for each written frame one JSON line of run diagnostics (Simulator::diagnostics) in
 // <dir>/stats.jsonl; doubles as %.17g, which reads back to the same double
 static bool write_stats(Simulator *simulator, FILE *out, int f) {
@@ -154,6 +189,19 @@ void startVisualization(Simulator *simulator) {
             surfaceIso = 0.f;
         }
     }
+    int tracers = 0; // 0: no tracers
+    if (framesDir && getenv("SPH_FREE_TRACERS")) {
+        const char *e = getenv("SPH_FREE_TRACERS");
+        char *end = NULL;
+        const long v = strtol(e, &end, 10);
+        if (end == e || *end || v < 1 || v > (1l << 24)) {
+            fprintf(stderr, "sph: SPH_FREE_TRACERS=%s is not a count in 1..16777216 -- writing no tracers\n", e);
+        } else {
+            const int n = simulator->settings->numParticles;
+            tracers = v > n ? n : (int)v;
+            if (tracers > 0 && !seed_tracers(simulator, tracers)) tracers = 0;
+        }
+    }
     FILE *stats = NULL;
     if (framesDir && getenv("SPH_FREE_STATS") && atoi(getenv("SPH_FREE_STATS")) != 0) {
         const std::string path = std::string(framesDir) + "/stats.jsonl";
@@ -166,6 +214,8 @@ void startVisualization(Simulator *simulator) {
             clickCoords = make_int2(400, 300);
         }
         simulator->simulate();
+        if (tracers > 0 && !simulator->advectTracers(simulator->settings->timestep)) tracers = 0;
+        if (framesDir && tracers > 0 && f % every == 0 && !write_tracers(simulator, framesDir, f)) tracers = 0;
         if (framesDir && f % every == 0 && !write_frame(simulator, framesDir, f, field)) framesDir = NULL;
         if (framesDir && slice >= 0 && f % every == 0 && !write_slice(simulator, framesDir, f, slice)) slice = -1;
         if (framesDir && surfaceIso > 0.f && f % every == 0 && !write_surface(simulator, framesDir, f, surfaceIso)) surfaceIso = 0.f;

@@ -200,6 +200,33 @@ bool Simulator::extractSurface(float iso, const float origin[3], const float spa
     return true;
 }
 
+// the tracer calls share their way out: a multi-GPU run and SPH_ESTATE are reported, anything else is fatal
+static bool tracer_call(sph_handle *impl, sph_mgpu *multi, int rc, const char *what) {
+    if (multi) {
+        fprintf(stderr, "sph: %s: a multi-GPU run (SPH_GPUS > 1) carries no tracers\n", what);
+        return false;
+    }
+    if (!impl) return false;
+    if (rc == SPH_ESTATE) { // (SPH_SWEEP=linked, a step split into phases, ...): nothing moved, nothing broken
+        fprintf(stderr, "sph: %s: %s\n", what, sph_last_error(impl));
+        return false;
+    }
+    check(impl, rc, what);
+    return true;
+}
+
+bool Simulator::setTracers(const float *pos_xyz, int m) {
+    return tracer_call(impl, multi, (multi || !impl) ? SPH_OK : sph_tracers_set(impl, pos_xyz, m), "setTracers");
+}
+
+bool Simulator::advectTracers(float dt) {
+    return tracer_call(impl, multi, (multi || !impl) ? SPH_OK : sph_tracers_advect(impl, dt), "advectTracers");
+}
+
+bool Simulator::getTracers(const float **posDen, const float **vel, int *m) {
+    return tracer_call(impl, multi, (multi || !impl) ? SPH_OK : sph_tracers_host(impl, posDen, vel, m), "getTracers");
+}
+
 bool Simulator::diagnostics(SphDiagnostics *out, SphDiagnosticsRaw *raw) {
     if (!out || (!impl && !multi)) {
         fprintf(stderr, "sph: diagnostics: setup() must come first\n");

@@ -263,6 +263,25 @@ struct SampleArgs {
 // one value per lattice point into out[0, nx ny nz); plain = the one-thread-per-point check path
 void sph_launch_sample(const DevParams &P, const SampleArgs &A, bool plain, float *out, hipStream_t s);
 
+// ---- passive tracers (tracers.hip; defined in DESIGN.md section 10e) ----
+struct TracerArgs {
+    const float4 *pos;       // the candidates, as SampleArgs reads them: sorted row j at pos[j stride] / vel[j stride]
+    const float4 *vel;
+    int stride;
+    const int2 *cellRange;   // {start, end} per flattened cell (SPH_KEY_FLATTENED only)
+    int n;                   // rows of the stream (0: no particle, nothing is walked)
+    int m;                   // tracers
+    float dt;
+    float4 *posDen;          // [m] caller order: (x, y, z, den); read, then rewritten in place by the tracer's own lane
+    float4 *velOut;          // [m] caller order: (ux, uy, uz, +0)
+    uint32_t *keys, *vals;   // [m] default path: k_tracer_keys fills them (cell key, or numCells for a tracer outside; identity)
+    const uint32_t *order;   // [m] default path: the sort's values, read by the walk (set by sph_launch_tracers)
+    unsigned long long *counters; // [3] waves_shared, waves_direct, groups (default path)
+};
+constexpr int kTracerCounters = 3;
+// key + sort + walk (plain: the one-thread-per-tracer check path alone); `ws` is the tracers' own sort workspace
+void sph_launch_tracers(const DevParams &P, TracerArgs A, bool plain, const SortWorkspace &ws, int keyBits, hipStream_t s);
+
 // ---- the surface mesh (surface.hip; defined in DESIGN.md section 10d) ----
 struct SurfaceArgs {
     int nx, ny, nz;          // lattice points per axis, each >= 2; point (ix, iy, iz) has L = (iz ny + iy) nx + ix

@@ -1,5 +1,5 @@
 // The handle behind include/sph_c_api.h and the few helpers its host translation units share (sph_api.hip,
-// sph_step.hip, sph_readback.hip, sph_slab.hip, sph_snapshot.hip, sph_frame.hip, sph_sample.hip, sph_surface.hip, sph_diag.hip).
+// sph_step.hip, sph_readback.hip, sph_slab.hip, sph_snapshot.hip, sph_frame.hip, sph_sample.hip, sph_surface.hip, sph_diag.hip, sph_tracers.hip).
 // Host code only.
 // Ownership: every device buffer, pinned block and event below is a DeviceBuf / PinnedBuf / Event (sph_owned.h) and goes
 // with the handle; a raw pointer member is a view of one of them (or of the caller's memory) and says so.
@@ -43,6 +43,7 @@ using sph_owned::PinnedBuf;
 //   SPH_SAMPLE_PLAIN      0        call    non-zero: sph_sample_field takes the one-thread-per-point check path
 //   SPH_DIAG_PLAIN        0        call    non-zero: sph_diagnose / sph_slab_diagnose take the check path
 //   SPH_SURFACE_PLAIN     0        call    non-zero: sph_extract_surface takes the check path, for its sample and its extraction
+//   SPH_TRACER_PLAIN      0        call    non-zero: sph_tracers_advect takes the one-thread-per-tracer check path
 //   SPH_MGPU_THREADS      0        (libsph_mgpu.so, its own object: sph_mgpu_create in mgpu_state.cpp) non-zero: one
 //                                          host thread per local slab
 // (The SPH_* variables the command-line front end reads -- SPH_SWEEP, SPH_GPUS, SPH_TRANSPORT, SPH_RECUT_EVERY,
@@ -267,6 +268,22 @@ struct sph_handle {
     bool diagAuto = false;           // ... and whether its histogram took the reduced range
     double diagSeconds = 0;          // clear + reduce + histogram, from HIP events (PairEvent ring)
     long long diagCount = 0;
+
+    // ---- sph_tracers.hip ----
+    // Passive tracers (tracers.hip): (x, y, z, den) and (ux, uy, uz, 0) per tracer in the caller's order, on the
+    // device and in pinned memory, grown on demand by sph_tracers_set; the tracers' own sort workspace and the walk
+    // kernel's three counters, allocated by the first advect that needs them.
+    sph_host::DeviceBuf<float4> tracerPosDen, tracerVel;
+    sph_host::PinnedBuf<float4> tracerPosDenHost, tracerVelHost;
+    size_t tracerCap = 0;            // tracers either pair of buffers holds
+    int tracerCount = 0;             // m of the last sph_tracers_set
+    sph_host::DeviceBuf<uint32_t> tracerKeys[2], tracerVals[2], tracerBlockHist, tracerDigitTotal;
+    SortWorkspace tracerWs{};        // views of the six above (capacity 0: not allocated yet)
+    sph_host::DeviceBuf<unsigned long long> tracerCounters; // waves_shared, waves_direct, groups
+    sph_host::PinnedBuf<unsigned long long> tracerCountersHost;
+    sph_host::Outbound tracerOut;    // the results on their way to tracerPosDenHost / tracerVelHost
+    double tracerSeconds = 0;        // key + sort + walk, from HIP events (PairEvent ring)
+    long long tracerCalls = 0;
 };
 
 #define HIPCHK(h, call)                                                               \

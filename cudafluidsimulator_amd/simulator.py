@@ -312,6 +312,38 @@ class Simulator:
                     "sph_get_diagnostics_time")
         return sec.value, cnt.value
 
+    # -- passive tracers: caller-seeded points carried by the interpolated velocity field (sph_tracers_*) --
+    def set_tracers(self, pos):
+        """Replace the tracers by the (m, 3) points `pos` (any float32 values; m == 0 clears them).  They belong to
+        the caller: setup(), upload_state() and load_state() leave them alone."""
+        pos = np.ascontiguousarray(pos, dtype=np.float32).reshape(-1, 3)
+        self._check(self._L.sph_tracers_set(self._h, _fp(pos) if len(pos) else None, len(pos)), "sph_tracers_set")
+
+    def advect_tracers(self, dt=None):
+        """One explicit Euler move of every tracer through the velocity field of the current state; dt = None:
+        settings.timestep, dt = 0: sample without moving.  Queues the work; does not block."""
+        dt = self.settings.timestep if dt is None else dt
+        self._check(self._L.sph_tracers_advect(self._h, C.c_float(dt)), "sph_tracers_advect")
+
+    def tracers(self):
+        """{"pos": (m, 3), "den": (m,), "vel": (m, 3)} float32 arrays of their own, in the order the tracers were
+        set: the positions after the last advect, the density sum and the velocity it sampled before the move."""
+        pd, u, m = C.POINTER(C.c_float)(), C.POINTER(C.c_float)(), C.c_int(0)
+        self._check(self._L.sph_tracers_host(self._h, C.byref(pd), C.byref(u), C.byref(m)), "sph_tracers_host")
+        if m.value == 0:
+            return dict(pos=np.zeros((0, 3), np.float32), den=np.zeros(0, np.float32), vel=np.zeros((0, 3), np.float32))
+        pd = np.ctypeslib.as_array(pd, shape=(m.value, 4))
+        u = np.ctypeslib.as_array(u, shape=(m.value, 4))
+        return dict(pos=np.array(pd[:, :3], copy=True), den=np.array(pd[:, 3], copy=True), vel=np.array(u[:, :3], copy=True))
+
+    def tracer_stats(self, reset=False):
+        """dict(calls, waves_shared, waves_direct, groups, seconds): sums since create or the last reset; `seconds`
+        is the GPU time of key + sort + walk, the three counters are what the walk kernel counted."""
+        st = _lib.SphTracerStats()
+        self._check(self._L.sph_get_tracer_stats(self._h, C.byref(st), 1 if reset else 0), "sph_get_tracer_stats")
+        return dict(calls=st.calls, waves_shared=st.waves_shared, waves_direct=st.waves_direct, groups=st.groups,
+                    seconds=st.seconds)
+
     def phase(self, name):
         self._check(getattr(self._L, "sph_phase_" + name)(self._h), "sph_phase_" + name)
 

@@ -105,6 +105,14 @@ class Simulator {
     // the library answers SPH_ESTATE.
     bool extractSurface(float iso, const float origin[3], const float spacing[3], int nx, int ny, int nz,
                         const float **vertices, long long *numVertices, const unsigned **triangles, long long *numTriangles);
+    // Passive tracers (sph_tracers_* in sph_c_api.h): m points (x, y, z interleaved) that the caller seeds and that
+    // advectTracers carries through the velocity field of the current state, one explicit Euler move of `dt` per call
+    // (dt == 0: sample without moving).  getTracers: m x 4 floats each, (x, y, z, den) and (ux, uy, uz, 0), owned by
+    // the simulator, valid until the next advectTracers or setTracers.  false (with a message on stderr) with
+    // SPH_GPUS > 1 and where the library answers SPH_ESTATE.
+    bool setTracers(const float *pos_xyz, int m);
+    bool advectTracers(float dt);
+    bool getTracers(const float **posDen, const float **vel, int *m);
     // Run diagnostics of the current state, reduced on the GPU (sph_diagnose in sph_c_api.h): total kinetic and
     // potential energy, momentum, centre of mass, the fastest particle, the CFL number, the spread of density.
     // *raw, if given, receives the exact words behind them.  With SPH_GPUS > 1 through the multi-GPU driver

@@ -565,6 +565,50 @@ int sph_get_diagnostics_time(sph_handle *h, double *seconds, int64_t *calls, int
  * range. */
 int sph_slab_diagnose(sph_handle *h, int buf, int i_begin, int i_end, const SphDiagnosticsOptions *opt);
 
+/* ---- passive tracers: points the caller seeds, carried by the interpolated velocity field step after step ----
+ * Additive to version 3: test for SPH_HAS_TRACERS.  Defined to the bit in DESIGN.md section 10e ("Tracers"); all
+ * fp32, every operation rounded on its own, in both math modes.  A handle holds m tracers, 0 <= m <= 1 << 24, in
+ * the caller's order, each with a position p, the velocity u and the density sum den sampled by the last advect.
+ * Cell, outside rule and walk are the field sample's (above).  Candidate j with d2 <= h h weighs
+ * m_j = MASS (((d_kernel_coeff diff) diff) diff), diff = h h - d2; den = sum(m_j) and n = sum(m_j v_j) per axis,
+ * all from +0, v_j the velocity sph_download_state returns for row j.  u = n / den per axis where den > 0, else +0.
+ * Where den > 0 and dt != 0 the tracer moves to p + u dt (one multiply, one add per axis); everywhere else -- an
+ * outside tracer, a NaN, empty space, dt == 0 -- its three position words are copied unchanged.  Tracers are not
+ * reflected at the walls and carry no mass: one that leaves the grid is outside from the next call on and stays.
+ * Tracers belong to the caller, not to the state: sph_setup, sph_upload_state and sph_load_state leave them alone,
+ * and sph_save_state does not store them. */
+#define SPH_HAS_TRACERS 1
+/* Replaces the handle's tracers by m points (x, y, z interleaved; any float values; m == 0 clears them).
+ * SPH_EINVAL: m < 0, m > 1 << 24, a NULL pos_xyz with m > 0.  SPH_ESTATE for SPH_FLAG_EXTERNAL_STATE handles.
+ * Blocks until the points are on the device. */
+int sph_tracers_set(sph_handle *h, const float *pos_xyz, int m);
+/* One explicit Euler move of every tracer through the velocity field of the state the handle holds NOW.
+ * dt == 0 samples without moving.  Queues the kernels and the copy of the results; does not block.
+ * State rules, grid handling and error codes are sph_sample_field's: the grid is found (phase 1) or built ahead
+ * (phase 0), the next step consumes it, a click, upload or load drops it, and no result of any step changes.
+ * SPH_ESTATE before any state, inside an open phase-split step, for SPH_FLAG_EXTERNAL_STATE handles, with
+ * SPH_SWEEP_LINKED and with SPH_KEY_MORTON.  SPH_EINVAL: a dt that is not finite.  No tracers set: SPH_OK, nothing
+ * happens.  No particles: every tracer gets den = u = +0 and keeps its words.  SPH_TRACER_PLAIN=1 in the environment
+ * selects the check path (one thread per tracer in caller order, every candidate loaded from global memory;
+ * identical words). */
+int sph_tracers_advect(sph_handle *h, float dt);
+/* m x 4 floats each, owned by the handle, valid until the next advect or set.
+ * pos_den = (x, y, z, den): den was sampled at the position before the move.  vel = (ux, uy, uz, +0).
+ * Blocks until the copy has landed.  Before the first advect after a set: the positions as set, den = u = +0.
+ * Any out-pointer may be NULL; with no tracers the pointers returned may be NULL and *m is 0. */
+int sph_tracers_host(sph_handle *h, const float **pos_den, const float **vel, int *m);
+typedef struct SphTracerStats {
+    int32_t struct_size, pad_;  /* sizeof(SphTracerStats), 0: both written by the call */
+    int64_t calls;              /* advects that ran kernels (either path) */
+    uint64_t waves_shared;      /* waves of 64 sorted tracers that walked their groups' candidates from LDS ... */
+    uint64_t waves_direct;      /* ... and waves that held too many groups and walked lane by lane */
+    uint64_t groups;            /* distinct (row of cells, block of 8 cells in x) groups, summed over the waves */
+    double seconds;             /* GPU time of key + sort + walk (HIP events on the compute stream) */
+} SphTracerStats;
+/* Sums since create or since the last reset; the three counters are what the walk kernel counted (the check path
+ * counts none).  Blocks. */
+int sph_get_tracer_stats(sph_handle *h, SphTracerStats *out, int reset);
+
 const char *sph_build_info(void);
 
 #ifdef __cplusplus
