@@ -30,6 +30,7 @@ EXPORTED_SYMBOLS = [
     "sph_diagnose", "sph_diagnostics_host", "sph_diagnostics_values", "sph_diagnostics_add",
     "sph_get_diagnostics_time", "sph_slab_diagnose",
     "sph_tracers_set", "sph_tracers_advect", "sph_tracers_host", "sph_get_tracer_stats",
+    "sph_derive", "sph_derived_host", "sph_get_derive_stats",
 ]
 SPH_API_VERSION = 3
 SPH_SHADE_FLAT, SPH_SHADE_COUNT = 0, 1
@@ -42,6 +43,7 @@ SPH_HAS_SURFACE = 1
 SPH_HAS_DIAGNOSTICS = 1
 SPH_HAS_TRACERS = 1
 MAX_TRACERS = 1 << 24
+SPH_HAS_DERIVED = 1
 DIAG_SUMS = ("x", "y", "z", "vx", "vy", "vz", "rho", "prs", "v2")   # SPH_DIAG_SUM_*
 DIAG_EXTREMA = ("x", "y", "z", "speed", "rho", "prs")               # SPH_DIAG_EXT_*
 DIAG_BINS = 256
@@ -159,6 +161,11 @@ class SphTracerStats(C.Structure):
                 ("seconds", C.c_double)]
 
 
+class SphDeriveStats(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("pad_", C.c_int32), ("calls", C.c_int64),
+                ("runs_staged", C.c_uint64), ("runs_direct", C.c_uint64), ("seconds", C.c_double)]
+
+
 class SphKernelTimes(C.Structure):
     _fields_ = [("hash", C.c_double), ("sort", C.c_double), ("gather", C.c_double),
                 ("density", C.c_double), ("force", C.c_double), ("readback", C.c_double),
@@ -250,5 +257,8 @@ def load_library():
     L.sph_tracers_advect.argtypes = [hp, C.c_float]
     L.sph_tracers_host.argtypes = [hp, C.POINTER(fp), C.POINTER(fp), C.POINTER(C.c_int)]
     L.sph_get_tracer_stats.argtypes = [hp, C.POINTER(SphTracerStats), C.c_int]
+    L.sph_derive.argtypes = [hp]
+    L.sph_derived_host.argtypes = [hp, C.POINTER(fp), C.POINTER(fp), C.POINTER(u32p), C.POINTER(C.c_int)]
+    L.sph_get_derive_stats.argtypes = [hp, C.POINTER(SphDeriveStats), C.c_int]
     _lib = L
     return L

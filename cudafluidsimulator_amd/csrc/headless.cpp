@@ -158,6 +158,43 @@ static bool write_tracers(Simulator *simulator, const char *dir, int f) {
     return (fclose(out) == 0) && ok;
 }
 
+// SPH_FREE_PARTICLES=1: beside each written frame the particles with their derived fields (sph_derive) as
+// <dir>/particles_%04d.ply: binary little-endian PLY, one vertex per particle in id order, properties
+// `float x y z vx vy vz rho wx wy wz divergence gx gy gz` and `uint neighbours`.
+static bool write_particles(Simulator *simulator, const char *dir, int f) {
+    const int n = simulator->settings->numParticles;
+    const float *wd = NULL, *gr = NULL;
+    const uint32_t *nb = NULL;
+    if (!simulator->deriveFlow(&wd, &gr, &nb)) return false;
+    const float3 *p = simulator->getPosition();
+    std::string vel((size_t)(n > 0 ? n : 1) * 12, '\0');
+    if (!p || !simulator->getVelocity(reinterpret_cast<float *>(&vel[0]))) return false;
+    char name[32];
+    snprintf(name, sizeof name, "/particles_%04d.ply", f);
+    const std::string path = std::string(dir) + name;
+    FILE *out = fopen(path.c_str(), "wb");
+    if (!out) {
+        fprintf(stderr, "sph: cannot write %s\n", path.c_str());
+        return false;
+    }
+    fprintf(out, "ply\nformat binary_little_endian 1.0\nelement vertex %d\n", n);
+    for (const char *k : {"x", "y", "z", "vx", "vy", "vz", "rho", "wx", "wy", "wz", "divergence", "gx", "gy", "gz"})
+        fprintf(out, "property float %s\n", k);
+    fprintf(out, "property uint neighbours\nend_header\n");
+    std::string rows((size_t)n * 60, '\0');
+    for (int i = 0; i < n; ++i) {
+        char *r = &rows[(size_t)i * 60];
+        memcpy(r, &p[i], 12);
+        memcpy(r + 12, &vel[(size_t)i * 12], 12);
+        memcpy(r + 24, gr + 4 * (size_t)i + 3, 4);  // rho
+        memcpy(r + 28, wd + 4 * (size_t)i, 16);     // wx wy wz divergence
+        memcpy(r + 44, gr + 4 * (size_t)i, 12);     // gx gy gz
+        memcpy(r + 56, nb + i, 4);
+    }
+    const bool ok = fwrite(rows.data(), 1, rows.size(), out) == rows.size();
+    return (fclose(out) == 0) && ok;
+}
+
 // SPH_FREE_STATS=1: for each written frame one JSON line of run diagnostics (Simulator::diagnostics) in
 // <dir>/stats.jsonl; doubles as %.17g, which reads back to the same double
 static bool write_stats(Simulator *simulator, FILE *out, int f) {
@@ -202,6 +239,12 @@ void startVisualization(Simulator *simulator) {
             if (tracers > 0 && !seed_tracers(simulator, tracers)) tracers = 0;
         }
     }
+    bool particles = false;
+    if (framesDir && getenv("SPH_FREE_PARTICLES")) {
+        const char *e = getenv("SPH_FREE_PARTICLES");
+        particles = strcmp(e, "1") == 0;
+        if (!particles) fprintf(stderr, "sph: SPH_FREE_PARTICLES=%s is not 1 -- writing no particle files\n", e);
+    }
     FILE *stats = NULL;
     if (framesDir && getenv("SPH_FREE_STATS") && atoi(getenv("SPH_FREE_STATS")) != 0) {
         const std::string path = std::string(framesDir) + "/stats.jsonl";
@@ -216,6 +259,7 @@ void startVisualization(Simulator *simulator) {
         simulator->simulate();
         if (tracers > 0 && !simulator->advectTracers(simulator->settings->timestep)) tracers = 0;
         if (framesDir && tracers > 0 && f % every == 0 && !write_tracers(simulator, framesDir, f)) tracers = 0;
+        if (framesDir && particles && f % every == 0 && !write_particles(simulator, framesDir, f)) particles = false;
         if (framesDir && f % every == 0 && !write_frame(simulator, framesDir, f, field)) framesDir = NULL;
         if (framesDir && slice >= 0 && f % every == 0 && !write_slice(simulator, framesDir, f, slice)) slice = -1;
         if (framesDir && surfaceIso > 0.f && f % every == 0 && !write_surface(simulator, framesDir, f, surfaceIso)) surfaceIso = 0.f;

@@ -227,6 +227,28 @@ bool Simulator::getTracers(const float **posDen, const float **vel, int *m) {
     return tracer_call(impl, multi, (multi || !impl) ? SPH_OK : sph_tracers_host(impl, posDen, vel, m), "getTracers");
 }
 
+bool Simulator::deriveFlow(const float **vortDiv, const float **gradRho, const uint32_t **neighbours) {
+    if (multi) {
+        fprintf(stderr, "sph: deriveFlow: a multi-GPU run (SPH_GPUS > 1) derives no fields\n");
+        return false;
+    }
+    if (!impl) return false;
+    const int rc = sph_derive(impl);
+    if (rc == SPH_ESTATE) { // (SPH_SWEEP=linked, a step split into phases, ...): nothing computed, nothing broken
+        fprintf(stderr, "sph: deriveFlow: %s\n", sph_last_error(impl));
+        return false;
+    }
+    check(impl, rc, "sph_derive");
+    check(impl, sph_derived_host(impl, vortDiv, gradRho, neighbours, NULL), "sph_derived_host");
+    return true;
+}
+
+bool Simulator::getVelocity(float *vel_xyz) {
+    if (multi || !impl || !vel_xyz) return false;
+    check(impl, sph_download_state(impl, NULL, vel_xyz, NULL, NULL), "sph_download_state");
+    return true;
+}
+
 bool Simulator::diagnostics(SphDiagnostics *out, SphDiagnosticsRaw *raw) {
     if (!out || (!impl && !multi)) {
         fprintf(stderr, "sph: diagnostics: setup() must come first\n");

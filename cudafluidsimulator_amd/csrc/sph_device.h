@@ -282,6 +282,22 @@ constexpr int kTracerCounters = 3;
 // key + sort + walk (plain: the one-thread-per-tracer check path alone); `ws` is the tracers' own sort workspace
 void sph_launch_tracers(const DevParams &P, TracerArgs A, bool plain, const SortWorkspace &ws, int keyBits, hipStream_t s);
 
+// ---- derived per-particle fields (derived.hip; defined in DESIGN.md section 10f) ----
+struct DeriveArgs {
+    const float4 *pos;       // the sorted stream, as SampleArgs reads it: row j at pos[j stride] / vel[j stride]
+    const float4 *vel;
+    int stride;
+    const int2 *cellRange;   // {start, end} per flattened cell (SPH_KEY_FLATTENED only)
+    int n;                   // rows of the stream, > 0
+    float4 *vortDiv;         // [n] particle-id order: (wx, wy, wz, divergence)
+    float4 *gradRho;         // [n] particle-id order: (gx, gy, gz, rho)
+    uint32_t *neighbours;    // [n] particle-id order: taken candidates
+    unsigned long long *counters; // [2] runs_staged, runs_direct (default path)
+};
+constexpr int kDeriveCounters = 2;
+// one sweep over rows [0, n); plain = the one-thread-per-row check path
+void sph_launch_derive(const DevParams &P, const DeriveArgs &A, bool plain, hipStream_t s);
+
 // ---- the surface mesh (surface.hip; defined in DESIGN.md section 10d) ----
 struct SurfaceArgs {
     int nx, ny, nz;          // lattice points per axis, each >= 2; point (ix, iy, iz) has L = (iz ny + iy) nx + ix

@@ -1,5 +1,5 @@
 // The handle behind include/sph_c_api.h and the few helpers its host translation units share (sph_api.hip,
-// sph_step.hip, sph_readback.hip, sph_slab.hip, sph_snapshot.hip, sph_frame.hip, sph_sample.hip, sph_surface.hip, sph_diag.hip, sph_tracers.hip).
+// sph_step.hip, sph_readback.hip, sph_slab.hip, sph_snapshot.hip, sph_frame.hip, sph_sample.hip, sph_surface.hip, sph_diag.hip, sph_tracers.hip, sph_derived.hip).
 // Host code only.
 // Ownership: every device buffer, pinned block and event below is a DeviceBuf / PinnedBuf / Event (sph_owned.h) and goes
 // with the handle; a raw pointer member is a view of one of them (or of the caller's memory) and says so.
@@ -44,6 +44,7 @@ using sph_owned::PinnedBuf;
 //   SPH_DIAG_PLAIN        0        call    non-zero: sph_diagnose / sph_slab_diagnose take the check path
 //   SPH_SURFACE_PLAIN     0        call    non-zero: sph_extract_surface takes the check path, for its sample and its extraction
 //   SPH_TRACER_PLAIN      0        call    non-zero: sph_tracers_advect takes the one-thread-per-tracer check path
+//   SPH_DERIVE_PLAIN      0        call    non-zero: sph_derive takes the one-thread-per-row check path
 //   SPH_MGPU_THREADS      0        (libsph_mgpu.so, its own object: sph_mgpu_create in mgpu_state.cpp) non-zero: one
 //                                          host thread per local slab
 // (The SPH_* variables the command-line front end reads -- SPH_SWEEP, SPH_GPUS, SPH_TRANSPORT, SPH_RECUT_EVERY,
@@ -284,6 +285,23 @@ struct sph_handle {
     sph_host::Outbound tracerOut;    // the results on their way to tracerPosDenHost / tracerVelHost
     double tracerSeconds = 0;        // key + sort + walk, from HIP events (PairEvent ring)
     long long tracerCalls = 0;
+
+    // ---- sph_derived.hip ----
+    // Derived per-particle fields (derived.hip): (wx, wy, wz, div), (gx, gy, gz, rho) and the neighbour count per
+    // particle in id order, on the device and in pinned memory, grown on demand by sph_derive; the default path's
+    // two counters, allocated by the first derive that needs them.
+    sph_host::DeviceBuf<float4> deriveVortDiv, deriveGradRho;
+    sph_host::DeviceBuf<uint32_t> deriveNeighbours;
+    sph_host::PinnedBuf<float4> deriveVortDivHost, deriveGradRhoHost;
+    sph_host::PinnedBuf<uint32_t> deriveNeighboursHost;
+    size_t deriveCap = 0;            // particles each of the six buffers holds
+    int deriveN = 0;                 // rows of the last sph_derive
+    bool deriveValid = false;        // a derive has been queued: the pinned buffers hold (or will hold) its results
+    sph_host::DeviceBuf<unsigned long long> deriveCounters; // runs_staged, runs_direct
+    sph_host::PinnedBuf<unsigned long long> deriveCountersHost;
+    sph_host::Outbound deriveOut;    // the results on their way to the three pinned buffers
+    double deriveSeconds = 0;        // the sweep, from HIP events (PairEvent ring)
+    long long deriveCalls = 0;
 };
 
 #define HIPCHK(h, call)                                                               \

@@ -344,6 +344,31 @@ class Simulator:
         return dict(calls=st.calls, waves_shared=st.waves_shared, waves_direct=st.waves_direct, groups=st.groups,
                     seconds=st.seconds)
 
+    # -- derived per-particle fields: vorticity, divergence, density gradient, neighbour count (sph_derive) --
+    def derive(self):
+        """{"vorticity": (n, 3), "divergence": (n,), "grad_rho": (n, 3), "rho": (n,)} float32 and {"neighbours": (n,)}
+        uint32 arrays of their own, in particle-id order, of the current state: the SPH curl and divergence of the
+        velocity, the gradient of the density (it points into the fluid at a free surface), the density sum itself
+        and the number of particles within h (the particle included)."""
+        self._check(self._L.sph_derive(self._h), "sph_derive")
+        wd, gr, nb, n = C.POINTER(C.c_float)(), C.POINTER(C.c_float)(), C.POINTER(C.c_uint32)(), C.c_int(0)
+        self._check(self._L.sph_derived_host(self._h, C.byref(wd), C.byref(gr), C.byref(nb), C.byref(n)), "sph_derived_host")
+        if n.value == 0:
+            z3, z1 = np.zeros((0, 3), np.float32), np.zeros(0, np.float32)
+            return dict(vorticity=z3, divergence=z1, grad_rho=z3.copy(), rho=z1.copy(), neighbours=np.zeros(0, np.uint32))
+        wd = np.ctypeslib.as_array(wd, shape=(n.value, 4))
+        gr = np.ctypeslib.as_array(gr, shape=(n.value, 4))
+        nb = np.ctypeslib.as_array(nb, shape=(n.value,))
+        return dict(vorticity=np.array(wd[:, :3], copy=True), divergence=np.array(wd[:, 3], copy=True),
+                    grad_rho=np.array(gr[:, :3], copy=True), rho=np.array(gr[:, 3], copy=True), neighbours=np.array(nb, copy=True))
+
+    def derive_stats(self, reset=False):
+        """dict(calls, runs_staged, runs_direct, seconds): sums since create or the last reset; `seconds` is the GPU
+        time of the sweep, the two counters are the runs the default path walked from LDS and from global memory."""
+        st = _lib.SphDeriveStats()
+        self._check(self._L.sph_get_derive_stats(self._h, C.byref(st), 1 if reset else 0), "sph_get_derive_stats")
+        return dict(calls=st.calls, runs_staged=st.runs_staged, runs_direct=st.runs_direct, seconds=st.seconds)
+
     def phase(self, name):
         self._check(getattr(self._L, "sph_phase_" + name)(self._h), "sph_phase_" + name)
 

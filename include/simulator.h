@@ -10,6 +10,7 @@
 #ifndef SPH_SIMULATOR_H
 #define SPH_SIMULATOR_H
 
+#include <stdint.h>
 #include <stdio.h>
 
 #ifndef __HIP_PLATFORM_AMD__
@@ -113,6 +114,14 @@ class Simulator {
     bool setTracers(const float *pos_xyz, int m);
     bool advectTracers(float dt);
     bool getTracers(const float **posDen, const float **vel, int *m);
+    // Derived per-particle fields of the current state (sph_derive in sph_c_api.h), in particle-id order: n x 4
+    // floats each, (wx, wy, wz, divergence) and (gx, gy, gz, rho), and n neighbour counts, owned by the simulator,
+    // valid until the next deriveFlow.  Any out-pointer may be NULL.  false (with a message on stderr) with
+    // SPH_GPUS > 1 and where the library answers SPH_ESTATE.
+    bool deriveFlow(const float **vortDiv, const float **gradRho, const uint32_t **neighbours);
+    // The velocities of the current state (sph_download_state), n x 3 floats in particle-id order, into the caller's
+    // buffer.  false with SPH_GPUS > 1 and before setup().
+    bool getVelocity(float *vel_xyz);
     // Run diagnostics of the current state, reduced on the GPU (sph_diagnose in sph_c_api.h): total kinetic and
     // potential energy, momentum, centre of mass, the fastest particle, the CFL number, the spread of density.
     // *raw, if given, receives the exact words behind them.  With SPH_GPUS > 1 through the multi-GPU driver

@@ -609,6 +609,42 @@ typedef struct SphTracerStats {
  * counts none).  Blocks. */
 int sph_get_tracer_stats(sph_handle *h, SphTracerStats *out, int reset);
 
+/* ---- derived per-particle fields: vorticity, divergence, density gradient and neighbour count ----
+ * Additive to version 3: test for SPH_HAS_DERIVED.  Defined to the bit in DESIGN.md section 10f ("Derived fields");
+ * all fp32, every operation rounded on its own, in both math modes.  Row i of the grid's sorted stream walks the
+ * density sweep's candidates (its own cell clamped into the grid, the 27 cells around it in dz, dy, dx order, each
+ * cell's rows in stream order, itself included).  With e = p_j - p_i, u = v_j - v_i (the words sph_download_state
+ * returns), d2 = (ex ex + ey ey) + ez ez, candidate j is taken unless d2 > h h; then diff = h h - d2,
+ * a = (d_kernel_coeff diff) diff, m = MASS (a diff), w = MASS a, and from +0:
+ *   rho += m;  g += w e (per axis);  s += w ((ux ex + uy ey) + uz ez);  c += w (e x u) (per axis);  count += 1.
+ * grad_rho = 6 g, divergence = (6 s) / rho, vorticity = (6 c) / rho per axis; where rho is not > 0 the last two are
+ * +0.  rho is this walk's own sum without the EPS_F clamp: the call works before the first step, and the density the
+ * next step's sweep stores is max(rho, EPS_F). */
+#define SPH_HAS_DERIVED 1
+/* Queues the sweep over the particles of the state the handle holds NOW and the copies of its results; does not
+ * block.  State rules and grid handling are sph_tracers_advect's: the grid is found (phase 1) or built ahead
+ * (phase 0), the next step consumes it, a click, upload or load drops it, and no result of any step changes; the
+ * sweep's GPU time lands in that step's SphKernelTimes.density.  SPH_ESTATE before any state, inside an open
+ * phase-split step, for SPH_FLAG_EXTERNAL_STATE handles, with SPH_SWEEP_LINKED and with SPH_KEY_MORTON.  No
+ * particles: SPH_OK, n = 0.  SPH_DERIVE_PLAIN=1 in the environment selects the check path (one thread per row, every
+ * candidate loaded from global memory; identical words). */
+int sph_derive(sph_handle *h);
+/* The results of the last sph_derive in particle-id order, owned by the handle, valid until the next sph_derive:
+ * vort_div = n x (wx, wy, wz, divergence), grad_rho = n x (gx, gy, gz, rho), neighbours = n counts.  Blocks until the
+ * copies have landed.  Any out-pointer may be NULL; with n == 0 the pointers returned may be NULL.  SPH_ESTATE
+ * before the first sph_derive. */
+int sph_derived_host(sph_handle *h, const float **vort_div, const float **grad_rho, const uint32_t **neighbours, int *n);
+typedef struct SphDeriveStats {
+    int32_t struct_size, pad_;  /* sizeof(SphDeriveStats), 0: both written by the call */
+    int64_t calls;              /* derives that ran a kernel (either path) */
+    uint64_t runs_staged;       /* non-empty runs (of nine per wave of 64 rows) the default path walked from LDS ... */
+    uint64_t runs_direct;       /* ... and runs longer than the LDS slice, walked from global memory */
+    double seconds;             /* GPU time of the sweep (HIP events on the compute stream) */
+} SphDeriveStats;
+/* Sums since create or since the last reset; the two counters are what the default path's kernel counted (the check
+ * path counts none).  Blocks. */
+int sph_get_derive_stats(sph_handle *h, SphDeriveStats *out, int reset);
+
 const char *sph_build_info(void);
 
 #ifdef __cplusplus

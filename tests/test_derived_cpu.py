@@ -1,0 +1,266 @@
+"""The derived fields' numpy restatement (tests/derived_restatement.py) against the field sample's restatement, which
+is pinned to the oracle's density sum, against hand-derived values, in a uniform translation and against float64
+within a derived rounding bound; and the C-ABI's new declarations.  Comparisons are of raw fp32 words unless a bound
+is derived."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import cudafluidsimulator_amd as sph
+from cudafluidsimulator_amd import _lib
+
+import derived_restatement as DR
+import field_sample_restatement as FS
+from oracle import oracle as O
+
+F = np.float32
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLD = os.path.join(ROOT, "tests", "golden")
+NAMES = ("dense4096", "random4096")
+_cache = {}
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=F).view(np.uint32)
+
+
+def state(name):
+    """settings, the oracle's grid of the golden state (sorted pos, vel, cell ranges) and its restated derived fields
+    per row of that grid: computed once, shared, never written to"""
+    if name not in _cache:
+        data = np.load(os.path.join(GOLD, name + ".npz"))
+        pos, vel = np.ascontiguousarray(data["pos_1"], dtype=F), np.ascontiguousarray(data["vel_1"], dtype=F)
+        s = O.make_settings(len(pos), True)
+        D = int(s.numCellsPerDim)
+        keys = O.cell_keys(s, pos)
+        perm = O.stable_sort(keys, D ** 3)
+        cs, ce = O.cell_table(keys[perm], D ** 3)
+        grid = (pos[perm], vel[perm], np.stack([cs, ce], axis=1))
+        out = DR.derive(grid[0], grid[1], grid[2], s.h, s.d_kernel_coeff, D)
+        _cache[name] = dict(s=s, D=D, pos=pos, vel=vel, grid=grid, out=out)
+    return _cache[name]
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_rho_is_the_field_samples_density_at_the_particle(name):
+    st = state(name)
+    s, grid, out = st["s"], st["grid"], st["out"]
+    none = np.zeros(len(grid[0]), F)
+    for i, p in enumerate(grid[0]):
+        at = tuple(float(v) for v in p)
+        want = FS.sample(grid[0], grid[1], none, grid[2], s.h, s.d_kernel_coeff, s.numCellsPerDim, "density", at, (0.1,) * 3, (1, 1, 1))
+        assert bits(out["rho"][i]).item() == bits(want).item(), (name, i)
+    assert (out["rho"] > 0).all() and (out["neighbours"] >= 1).all()
+    assert int(out["neighbours"].sum()) > len(grid[0]), "no row has a neighbour but itself: the state pins nothing"
+
+
+# ---- hand-derived known answers: every operation an np.float32 operation, written out ----
+
+def by_hand(s, p, v, i, order):
+    """the nine sums of row i over the candidates `order`, and the results, with scalar np.float32 operations"""
+    h2 = F(s.h) * F(s.h)
+    c = F(s.d_kernel_coeff)
+    rho = gx = gy = gz = sd = cx = cy = cz = F(0)
+    count = 0
+    for j in order:
+        ex, ey, ez = p[j][0] - p[i][0], p[j][1] - p[i][1], p[j][2] - p[i][2]
+        d2 = (ex * ex + ey * ey) + ez * ez
+        if d2 > h2:
+            continue
+        diff = h2 - d2
+        a = (c * diff) * diff
+        m = F(0.02) * (a * diff)
+        w = F(0.02) * a
+        ux, uy, uz = v[j][0] - v[i][0], v[j][1] - v[i][1], v[j][2] - v[i][2]
+        rho = rho + m
+        gx, gy, gz = gx + w * ex, gy + w * ey, gz + w * ez
+        sd = sd + w * ((ux * ex + uy * ey) + uz * ez)
+        cx = cx + w * (ey * uz - ez * uy)
+        cy = cy + w * (ez * ux - ex * uz)
+        cz = cz + w * (ex * uy - ey * ux)
+        count += 1
+    for x in (rho, gx, gy, gz, sd, cx, cy, cz, d2):
+        assert type(x) is F
+    six = F(6)
+    return dict(rho=rho, grad_rho=[six * gx, six * gy, six * gz], divergence=(six * sd) / rho,
+                vorticity=[(six * cx) / rho, (six * cy) / rho, (six * cz) / rho], neighbours=count)
+
+
+def tiny_grid(s, p):
+    """the cell table of a few sorted particles (the caller gives them in key order)"""
+    D = int(s.numCellsPerDim)
+    c = DR.row_cells(p, s.h, D)
+    key = (c[:, 2] * D + c[:, 1]) * D + c[:, 0]
+    assert (np.diff(key) >= 0).all()
+    cells = np.zeros((D ** 3, 2), np.int32)
+    for k in np.unique(key):
+        rows = np.flatnonzero(key == k)
+        cells[k] = (rows[0], rows[-1] + 1)
+    return cells, key
+
+
+def restated(s, p, v):
+    cells, key = tiny_grid(s, p)
+    return DR.derive(p, v, cells, s.h, s.d_kernel_coeff, int(s.numCellsPerDim)), key
+
+
+def assert_row(out, i, want, what):
+    assert bits(out["rho"][i]).item() == bits(want["rho"]).item(), what
+    assert int(out["neighbours"][i]) == want["neighbours"], what
+    assert bits(out["divergence"][i]).item() == bits(want["divergence"]).item(), what
+    for a in range(3):
+        assert bits(out["grad_rho"][i, a]).item() == bits(want["grad_rho"][a]).item(), (what, a)
+        assert bits(out["vorticity"][i, a]).item() == bits(want["vorticity"][a]).item(), (what, a)
+
+
+def test_known_answer_one_particle():
+    s = O.make_settings(1, False)
+    p, v = np.array([[0.55, 0.55, 0.55]], F), np.array([[3, -4, 12]], F)
+    out, _ = restated(s, p, v)
+    h2 = F(s.h) * F(s.h)
+    self_term = F(0.02) * (((F(s.d_kernel_coeff) * h2) * h2) * h2)      # d2 = 0: diff = h*h
+    assert self_term > 0 and bits(out["rho"][0]).item() == bits(F(0) + self_term).item()
+    assert out["neighbours"].tolist() == [1]
+    for k in ("vorticity", "divergence", "grad_rho"):
+        assert (bits(out[k]) == 0).all(), k
+    assert_row(out, 0, by_hand(s, p, v, 0, [0]), "one particle")
+
+
+def test_known_answers_pairs():
+    s = O.make_settings(2, False)
+    r, omega = F(0.02), F(7)
+    centre = np.array([0.55, 0.55, 0.55], F)
+    p = np.stack([centre - [r, 0, 0], centre + [r, 0, 0]]).astype(F)
+    # rigid rotation about z through the centre: v = omega z^ x (p - centre)
+    v = np.array([[0, -(omega * r), 0], [0, omega * r, 0]], F)
+    out, key = restated(s, p, v)
+    assert key[0] == key[1], "premise: both in one cell"
+    for i in range(2):
+        assert_row(out, i, by_hand(s, p, v, i, [0, 1]), f"rotation, row {i}")
+        assert out["neighbours"][i] == 2 and out["vorticity"][i, 2] > 0
+        assert bits(out["vorticity"][i, 0]) == 0 and bits(out["vorticity"][i, 1]) == 0 and bits(out["divergence"][i]) == 0
+    # each row sees half the pair's rotation rate times the kernel's share: 6 w (2r)(2 omega r) / rho, w from a at d = 2r
+    h2 = F(s.h) * F(s.h)
+    d2 = ((p[1, 0] - p[0, 0]) * (p[1, 0] - p[0, 0]) + F(0)) + F(0)
+    diff = h2 - d2
+    a = (F(s.d_kernel_coeff) * diff) * diff
+    w = F(0.02) * a
+    ex, uy = p[1, 0] - p[0, 0], v[1, 1] - v[0, 1]
+    rho = (F(0) + F(0.02) * (((F(s.d_kernel_coeff) * h2) * h2) * h2)) + F(0.02) * (a * diff)
+    assert bits(out["vorticity"][0, 2]).item() == bits((F(6) * (F(0) + w * (ex * uy - F(0) * F(0)))) / rho).item()
+    # moving apart along x: positive divergence, no rotation; grad_rho points from each particle to the other
+    v = np.array([[-1, 0, 0], [1, 0, 0]], F)
+    out, _ = restated(s, p, v)
+    for i in range(2):
+        assert_row(out, i, by_hand(s, p, v, i, [0, 1]), f"apart, row {i}")
+        assert out["divergence"][i] > 0 and (bits(out["vorticity"][i]) == 0).all()
+    assert out["grad_rho"][0, 0] > 0 and out["grad_rho"][1, 0] < 0
+    assert (bits(out["grad_rho"][:, 1:]) == 0).all()
+    # ... and approaching: negative
+    out, _ = restated(s, p, -v)
+    assert (out["divergence"] < 0).all()
+
+
+def test_known_answer_three_particles_in_two_cells():
+    s = O.make_settings(3, False)
+    # rows 0, 1 in cell (5, 5, 5), row 2 in cell (6, 5, 5): within h of row 1, beyond h of row 0
+    p = np.array([[0.51, 0.52, 0.53], [0.58, 0.55, 0.56], [0.64, 0.57, 0.52]], F)
+    v = np.array([[0.3, -1.2, 0.5], [-0.7, 0.4, 0.9], [1.1, 0.2, -0.6]], F)
+    out, key = restated(s, p, v)
+    assert key[0] == key[1] == key[2] - 1
+    # the walk of rows 0 and 1 (cell 5): dx = -1 empty, own cell (rows 0, 1), dx = +1 (row 2); of row 2 (cell 6): cell 5, own
+    for i in range(3):
+        assert_row(out, i, by_hand(s, p, v, i, [0, 1, 2]), f"row {i}")
+    assert out["neighbours"].tolist() == [2, 3, 2]
+    for k in ("vorticity", "grad_rho"):
+        assert (out[k] != 0).all(), k
+    assert (out["divergence"] != 0).all()
+
+
+def test_uniform_translation_has_no_vorticity_and_no_divergence():
+    st = state("random4096")
+    rows = np.unique(bits(st["vel"]), axis=0)
+    assert len(rows) == 1 and (rows.view(F) != 0).any(), "premise: every row of vel_1 is the same, and moving"
+    out = st["out"]
+    assert (bits(out["vorticity"]) == 0).all() and (bits(out["divergence"]) == 0).all()
+    assert (out["grad_rho"] != 0).any()
+
+
+def test_no_sum_is_minus_zero():
+    for name in NAMES:
+        assert not (bits(state(name)["out"]["sums"]) == 0x80000000).any(), name
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_fp32_stays_within_its_rounding_bound_of_float64(name):
+    """Model: every fp32 operation returns its exact result times (1 + d), |d| <= u = 2^-24 (nothing underflows: the
+    smallest non-zero diff is an ulp of h*h, 2^-34, and the velocities are zero or of order one).
+
+    One candidate.  e = pj - pi and the velocity difference are one operation each.  d2 = (ex ex + ey ey) + ez ez is
+    a sum of non-negative terms, each through three roundings (two inputs, one product) and up to two adds: its
+    error is at most d2 g5, g5 = (1 + u)^5 - 1.  diff = h h - d2 cancels, so its error is bounded absolutely:
+    dd = d2 g5 (1 + u) + u |diff|.  The factor q that multiplies w (1 for rho; e; the dot product; a cross-product
+    component) carries dq = u |e|, g5 (|ux ex| + |uy ey| + |uz ez|), or g4 (|ey uz| + |ez uy|): products of two
+    rounded inputs, then the adds.  The term C diff^p q (C = MASS c; p = 3 for rho, else 2) takes four more
+    multiplies, so |computed term| <= top = C (|diff| + dd)^p (|q| + dq) (1 + u)^4 and
+    |computed term - term| <= top - |term|, the error of a product of perturbed factors.
+
+    The sum of the K taken terms, added left to right from +0 (the first add is exact), is off by at most
+    ((1 + u)^(K - 1) - 1) sum(top) more.  bound(u) = sum(top - |term|) + ((1 + u)^(K - 1) - 1) sum(top): it is made
+    of K, the operation counts and the float64 sums of absolute products alone.  The float64 sums are such an
+    evaluation with u = 2^-53, so |fp32 sum - float64 sum| <= B = bound(2^-24) + bound(2^-53).
+
+    Results.  grad_rho = 6 g: one more multiply, E = 6 B + u (6 |g| + 6 B).  A quotient (6 N) / rho: the numerator
+    is off by E_N like grad_rho, rho by B_rho < rho, the divide rounds once:
+    (|6 N| + E_N) / (rho - B_rho) (1 + u) - |6 N| / rho.  The float64 results add two roundings of 2^-53."""
+    st = state(name)
+    s, grid, out = st["s"], st["grid"], st["out"]
+    u32, u64 = 2.0 ** -24, 2.0 ** -53
+    ref = DR.derive_f64(grid[0], grid[1], grid[2], s.h, s.d_kernel_coeff, st["D"], u32)
+    B = ref["bound"] + DR.derive_f64(grid[0], grid[1], grid[2], s.h, s.d_kernel_coeff, st["D"], u64)["bound"]
+    assert np.array_equal(ref["taken"], out["neighbours"].astype(np.int64)) and ref["taken"].sum() > len(grid[0])
+    err = np.abs(out["sums"].astype(np.float64) - ref["sums"])
+    worst = np.where(B > 0, err / np.where(B > 0, B, 1.0), 0.0)
+    print("%s: largest |fp32 - float64| / bound over the eight sums: %s" % (name, np.round(worst.max(axis=0), 3).tolist()))
+    assert (err <= B).all()
+    own = (1 + u64) ** 2 - 1
+    top = 6.0 * np.abs(ref["sums"])
+    E = 6.0 * B + u32 * (top + 6.0 * B)
+    g_err = np.abs(out["grad_rho"].astype(np.float64) - ref["grad_rho"])
+    assert (g_err <= E[:, 1:4] + own * np.abs(ref["grad_rho"])).all()
+    rho, Brho = ref["rho"], B[:, 0]
+    assert (Brho < rho).all()
+    quot = (top[:, 4:8] + E[:, 4:8]) / (rho - Brho)[:, None] * (1 + u32) - top[:, 4:8] / rho[:, None]
+    got = np.concatenate([out["divergence"][:, None], out["vorticity"]], axis=1).astype(np.float64)
+    want = np.concatenate([ref["divergence"][:, None], ref["vorticity"]], axis=1)
+    q_err = np.abs(got - want)
+    print("%s: largest result error / bound: grad %.3f, div and vorticity %.3f" % (
+        name, (g_err / np.maximum(E[:, 1:4], 1e-300)).max(), (q_err / np.maximum(quot, 1e-300)).max()))
+    assert (q_err <= quot + own * np.abs(want)).all()
+
+
+def test_header_library_and_binding_carry_the_derived_fields():
+    text = open(os.path.join(ROOT, "include", "sph_c_api.h")).read()
+    assert re.search(r"#define\s+SPH_HAS_DERIVED\s+1", text) and re.search(r"#define\s+SPH_API_VERSION\s+3\b", text)
+    assert getattr(_lib, "SPH_HAS_DERIVED", 0) == 1
+    names = ("sph_derive", "sph_derived_host", "sph_get_derive_stats")
+    code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    for name in names:
+        assert re.search(r"\bint\s+" + name + r"\s*\(", code), name
+        assert name in _lib.EXPORTED_SYMBOLS
+    out = subprocess.check_output(["nm", "-D", "--defined-only", sph.library_path()], text=True)
+    exported = set(re.findall(r" T (sph_\w+)", out))
+    assert set(names) <= exported
+    m = re.search(r"typedef struct SphDeriveStats \{(.*?)\} SphDeriveStats;", code, flags=re.S)
+    size = {"int32_t": 4, "int64_t": 8, "uint64_t": 8, "double": 8}
+    fields = re.findall(r"(int32_t|int64_t|uint64_t|double)\s+([^;]+);", m.group(1))
+    declared = [(n.strip(), size[t]) for t, decl in fields for n in decl.split(",")]
+    assert [n for n, _ in declared] == [n for n, _ in _lib.SphDeriveStats._fields_]
+    assert [b for _, b in declared] == [C.sizeof(t) for _, t in _lib.SphDeriveStats._fields_]
+    assert C.sizeof(_lib.SphDeriveStats) == sum(b for _, b in declared) == 40
+    assert _lib.SphDeriveStats.seconds.offset == 32
+    assert callable(getattr(sph.Simulator, "derive", None)) and callable(getattr(sph.Simulator, "derive_stats", None))
