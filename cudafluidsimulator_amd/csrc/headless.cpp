@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "sha256.h"
 #include "simulator.h"
@@ -195,6 +196,47 @@ static bool write_particles(Simulator *simulator, const char *dir, int f) {
     return (fclose(out) == 0) && ok;
 }
 
+// SPH_FREE_BODIES=<f>, f in (0, 1], the link length in units of h: beside each written frame the particles with the
+// body they belong to (sph_label_bodies) as <dir>/bodies_%04d.ply: binary little-endian PLY, one vertex per particle in
+// id order, properties `float x y z`, `uint label` and `uint body_count`; and one line on stderr,
+// `bodies <frame> <num_bodies> <largest count>`.
+static bool write_bodies(Simulator *simulator, const char *dir, int f, float link) {
+    const int n = simulator->settings->numParticles;
+    const uint32_t *labels = NULL, *table = NULL;
+    int bodies = 0;
+    uint32_t largest = 0;
+    if (!simulator->labelBodies(link, &labels, &table, &bodies, &largest)) return false;
+    const float3 *p = simulator->getPosition();
+    if (!p) return false;
+    // a label's row of the table: the labels ascend in it
+    std::vector<uint32_t> countOf((size_t)(n > 0 ? n : 0), 0u);
+    uint32_t most = 0;
+    for (int b = 0; b < bodies; ++b) {
+        countOf[table[8 * (size_t)b]] = table[8 * (size_t)b + 1];
+        if (table[8 * (size_t)b] == largest) most = table[8 * (size_t)b + 1];
+    }
+    char name[32];
+    snprintf(name, sizeof name, "/bodies_%04d.ply", f);
+    const std::string path = std::string(dir) + name;
+    FILE *out = fopen(path.c_str(), "wb");
+    if (!out) {
+        fprintf(stderr, "sph: cannot write %s\n", path.c_str());
+        return false;
+    }
+    fprintf(out, "ply\nformat binary_little_endian 1.0\nelement vertex %d\n", n);
+    fprintf(out, "property float x\nproperty float y\nproperty float z\nproperty uint label\nproperty uint body_count\nend_header\n");
+    std::string rows((size_t)n * 20, '\0');
+    for (int i = 0; i < n; ++i) {
+        char *r = &rows[(size_t)i * 20];
+        memcpy(r, &p[i], 12);
+        memcpy(r + 12, labels + i, 4);
+        memcpy(r + 16, &countOf[labels[i]], 4);
+    }
+    const bool ok = fwrite(rows.data(), 1, rows.size(), out) == rows.size();
+    fprintf(stderr, "bodies %d %d %u\n", f, bodies, most);
+    return (fclose(out) == 0) && ok;
+}
+
 // SPH_FREE_STATS=1: for each written frame one JSON line of run diagnostics (Simulator::diagnostics) in
 // <dir>/stats.jsonl; doubles as %.17g, which reads back to the same double
 static bool write_stats(Simulator *simulator, FILE *out, int f) {
@@ -245,6 +287,16 @@ void startVisualization(Simulator *simulator) {
         particles = strcmp(e, "1") == 0;
         if (!particles) fprintf(stderr, "sph: SPH_FREE_PARTICLES=%s is not 1 -- writing no particle files\n", e);
     }
+    float bodyLink = 0.f; // 0: no body files
+    if (framesDir && getenv("SPH_FREE_BODIES")) {
+        const char *e = getenv("SPH_FREE_BODIES");
+        char *end = NULL;
+        const float v = strtof(e, &end);
+        if (end == e || *end || !std::isfinite(v) || !(v > 0.f) || v > 1.f)
+            fprintf(stderr, "sph: SPH_FREE_BODIES=%s is not a link length in (0, 1] (units of h) -- writing no body files\n", e);
+        else
+            bodyLink = v * simulator->settings->h;
+    }
     FILE *stats = NULL;
     if (framesDir && getenv("SPH_FREE_STATS") && atoi(getenv("SPH_FREE_STATS")) != 0) {
         const std::string path = std::string(framesDir) + "/stats.jsonl";
@@ -260,6 +312,7 @@ void startVisualization(Simulator *simulator) {
         if (tracers > 0 && !simulator->advectTracers(simulator->settings->timestep)) tracers = 0;
         if (framesDir && tracers > 0 && f % every == 0 && !write_tracers(simulator, framesDir, f)) tracers = 0;
         if (framesDir && particles && f % every == 0 && !write_particles(simulator, framesDir, f)) particles = false;
+        if (framesDir && bodyLink > 0.f && f % every == 0 && !write_bodies(simulator, framesDir, f, bodyLink)) bodyLink = 0.f;
         if (framesDir && f % every == 0 && !write_frame(simulator, framesDir, f, field)) framesDir = NULL;
         if (framesDir && slice >= 0 && f % every == 0 && !write_slice(simulator, framesDir, f, slice)) slice = -1;
         if (framesDir && surfaceIso > 0.f && f % every == 0 && !write_surface(simulator, framesDir, f, surfaceIso)) surfaceIso = 0.f;

@@ -243,6 +243,25 @@ bool Simulator::deriveFlow(const float **vortDiv, const float **gradRho, const u
     return true;
 }
 
+bool Simulator::labelBodies(float link, const uint32_t **labels, const uint32_t **table, int *numBodies, uint32_t *largest) {
+    if (multi) {
+        fprintf(stderr, "sph: labelBodies: a multi-GPU run (SPH_GPUS > 1) labels no bodies\n");
+        return false;
+    }
+    if (!impl) return false;
+    SphBodyOptions o;
+    o.struct_size = (int32_t)sizeof o;
+    o.link = link;
+    const int rc = sph_label_bodies(impl, &o);
+    if (rc == SPH_ESTATE || rc == SPH_EINVAL) { // (SPH_SWEEP=linked, a link longer than h, ...): nothing computed, nothing broken
+        fprintf(stderr, "sph: labelBodies: %s\n", sph_last_error(impl));
+        return false;
+    }
+    check(impl, rc, "sph_label_bodies");
+    check(impl, sph_bodies_host(impl, labels, NULL, table, numBodies, largest), "sph_bodies_host");
+    return true;
+}
+
 bool Simulator::getVelocity(float *vel_xyz) {
     if (multi || !impl || !vel_xyz) return false;
     check(impl, sph_download_state(impl, NULL, vel_xyz, NULL, NULL), "sph_download_state");

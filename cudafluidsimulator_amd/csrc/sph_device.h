@@ -298,6 +298,46 @@ constexpr int kDeriveCounters = 2;
 // one sweep over rows [0, n); plain = the one-thread-per-row check path
 void sph_launch_derive(const DevParams &P, const DeriveArgs &A, bool plain, hipStream_t s);
 
+// ---- bodies: connected components of the link graph (bodies.hip; defined in DESIGN.md section 10g) ----
+// What one call counts and the few words the host waits for, on the device: every word written by integer atomics
+// (or by one thread), cleared by the first launch of a call.
+struct BodyCounters {
+    unsigned long long links;    // unordered linked pairs
+    unsigned long long unions;   // successful merges (default path)
+    unsigned long long largest;  // count << 32 | ~label of the body with the greatest count (smallest label on a tie)
+    uint32_t numBodies;          // the scan's total
+    uint32_t gaveUp;             // lanes that left a bounded loop at its bound (default path; always 0)
+    uint32_t changed;            // check path: a row's label went down in this round
+    uint32_t pad;
+};
+struct BodyArgs {
+    const float4 *pos;       // the sorted stream: row j at pos[j stride] = (x, y, z, id)
+    int stride;
+    const int2 *cellRange;   // {start, end} per flattened cell (SPH_KEY_FLATTENED only)
+    int n;                   // rows of the stream, > 0
+    float r2;                // link length squared, rounded once
+    uint32_t *parent;        // [n] default path: the union-find forest over rows; parent[i] <= i always
+    uint32_t *root;          // [n] default path: the root of every row, written by the flatten launch
+    uint32_t *rootId;        // [n] default path: per root the smallest particle id of its tree
+    uint32_t *rowLabel;      // [n] the label of every row (check path: propagated in place)
+    uint32_t *flag;          // [n] per particle id: 1 = it is a label
+    uint32_t *rank;          // [n] per particle id: labels below it (exclusive scan of flag)
+    uint32_t *blockSum;      // [sph_body_scan_blocks(n)] the scan's per-block sums, then offsets
+    uint32_t *labels;        // [n] particle-id order: the result
+    uint32_t *table;         // [8 numBodies] the result (table launches only)
+    BodyCounters *counters;
+};
+int sph_body_scan_blocks(int n);
+// default path: clear + link sweep + flatten + label + mark + scan, which leaves counters->numBodies
+void sph_launch_bodies_unite(const DevParams &P, const BodyArgs &A, hipStream_t s);
+// check path: clear (rowLabel = particle id); one round of min-label propagation (first: also counts the links),
+// which sets counters->changed; mark + scan after the last round
+void sph_launch_bodies_plain_begin(const BodyArgs &A, hipStream_t s);
+void sph_launch_bodies_plain_round(const DevParams &P, const BodyArgs &A, bool first, hipStream_t s);
+void sph_launch_bodies_plain_end(const BodyArgs &A, hipStream_t s);
+// both paths: the table of numBodies rows, labels in id order, counters->largest
+void sph_launch_bodies_table(const BodyArgs &A, int numBodies, hipStream_t s);
+
 // ---- the surface mesh (surface.hip; defined in DESIGN.md section 10d) ----
 struct SurfaceArgs {
     int nx, ny, nz;          // lattice points per axis, each >= 2; point (ix, iy, iz) has L = (iz ny + iy) nx + ix

@@ -1,5 +1,6 @@
 // The handle behind include/sph_c_api.h and the few helpers its host translation units share (sph_api.hip,
-// sph_step.hip, sph_readback.hip, sph_slab.hip, sph_snapshot.hip, sph_frame.hip, sph_sample.hip, sph_surface.hip, sph_diag.hip, sph_tracers.hip, sph_derived.hip).
+// sph_step.hip, sph_readback.hip, sph_slab.hip, sph_snapshot.hip, sph_frame.hip, sph_sample.hip, sph_surface.hip, sph_diag.hip, sph_tracers.hip, sph_derived.hip,
+// sph_bodies.hip).
 // Host code only.
 // Ownership: every device buffer, pinned block and event below is a DeviceBuf / PinnedBuf / Event (sph_owned.h) and goes
 // with the handle; a raw pointer member is a view of one of them (or of the caller's memory) and says so.
@@ -45,6 +46,7 @@ using sph_owned::PinnedBuf;
 //   SPH_SURFACE_PLAIN     0        call    non-zero: sph_extract_surface takes the check path, for its sample and its extraction
 //   SPH_TRACER_PLAIN      0        call    non-zero: sph_tracers_advect takes the one-thread-per-tracer check path
 //   SPH_DERIVE_PLAIN      0        call    non-zero: sph_derive takes the one-thread-per-row check path
+//   SPH_BODIES_PLAIN      0        call    non-zero: sph_label_bodies takes the check path (min-label propagation in rounds)
 //   SPH_MGPU_THREADS      0        (libsph_mgpu.so, its own object: sph_mgpu_create in mgpu_state.cpp) non-zero: one
 //                                          host thread per local slab
 // (The SPH_* variables the command-line front end reads -- SPH_SWEEP, SPH_GPUS, SPH_TRANSPORT, SPH_RECUT_EVERY,
@@ -302,6 +304,24 @@ struct sph_handle {
     sph_host::Outbound deriveOut;    // the results on their way to the three pinned buffers
     double deriveSeconds = 0;        // the sweep, from HIP events (PairEvent ring)
     long long deriveCalls = 0;
+
+    // ---- sph_bodies.hip ----
+    // Bodies (bodies.hip): the working arrays over rows and particle ids, the labels in id order and the table on the
+    // device and in pinned memory, all grown on demand by sph_label_bodies; the counter block on the device, its
+    // pinned copy the call waits for (the number of bodies) and the one that leaves with the results (the largest).
+    sph_host::DeviceBuf<uint32_t> bodyParent, bodyRoot, bodyRootId, bodyRowLabel, bodyFlag, bodyRank, bodyBlockSum;
+    sph_host::DeviceBuf<uint32_t> bodyLabels, bodyTable;
+    sph_host::PinnedBuf<uint32_t> bodyLabelsHost, bodyTableHost;
+    sph_host::DeviceBuf<BodyCounters> bodyCounters;
+    sph_host::PinnedBuf<BodyCounters> bodyCountersHost, bodyFinalHost;
+    sph_host::Event bodyCounted;     // the counter block has landed
+    size_t bodyCap = 0, bodyTableCap = 0; // particles / table rows the buffers hold
+    int bodyN = 0, bodyCount = 0;    // rows and bodies of the last sph_label_bodies
+    bool bodyValid = false;          // a labelling has been queued: the pinned buffers hold (or will hold) its results
+    sph_host::Outbound bodyOut;      // the results on their way to the pinned buffers
+    double bodySeconds = 0;          // every kernel of the call, from HIP events (PairEvent ring)
+    long long bodyCalls = 0;
+    unsigned long long bodyLinks = 0, bodyUnions = 0, bodyRounds = 0, bodyGaveUp = 0; // sums over calls
 };
 
 #define HIPCHK(h, call)                                                               \

@@ -369,6 +369,31 @@ class Simulator:
         self._check(self._L.sph_get_derive_stats(self._h, C.byref(st), 1 if reset else 0), "sph_get_derive_stats")
         return dict(calls=st.calls, runs_staged=st.runs_staged, runs_direct=st.runs_direct, seconds=st.seconds)
 
+    # -- bodies: the connected pieces of fluid and the piece every particle belongs to (sph_label_bodies) --
+    def label_bodies(self, link=0.0):
+        """{"labels": (n,) uint32 in particle-id order, "table": (num_bodies, 8) uint32 in ascending label order with
+        the columns of _lib.BODY_TABLE (label, count, the bounding box's minimum and maximum as float32 bit patterns:
+        table[:, 2:].view(np.float32)), "num_bodies", "largest"}: arrays of their own.  Two particles closer than
+        `link` (0: h; else 0 < link <= h) are linked, a body is a connected component of that graph, its label the
+        smallest particle id in it; `largest` is the label of the body with the most particles."""
+        opt = _lib.SphBodyOptions(C.sizeof(_lib.SphBodyOptions), link)
+        self._check(self._L.sph_label_bodies(self._h, C.byref(opt)), "sph_label_bodies")
+        lab, tab, n, k, big = C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint32)(), C.c_int(0), C.c_int(0), C.c_uint32(0)
+        self._check(self._L.sph_bodies_host(self._h, C.byref(lab), C.byref(n), C.byref(tab), C.byref(k), C.byref(big)), "sph_bodies_host")
+        if n.value == 0:
+            return dict(labels=np.zeros(0, np.uint32), table=np.zeros((0, 8), np.uint32), num_bodies=0, largest=0)
+        return dict(labels=np.array(np.ctypeslib.as_array(lab, shape=(n.value,)), copy=True),
+                    table=np.array(np.ctypeslib.as_array(tab, shape=(k.value, 8)), copy=True),
+                    num_bodies=k.value, largest=big.value)
+
+    def body_stats(self, reset=False):
+        """dict(calls, links, unions, rounds, gave_up, seconds): sums since create or the last reset; `links` is the
+        number of linked pairs, `unions` n - num_bodies, `rounds` the sweeps of the check path (SPH_BODIES_PLAIN=1),
+        `seconds` the GPU time of the kernels."""
+        st = _lib.SphBodyStats()
+        self._check(self._L.sph_get_body_stats(self._h, C.byref(st), 1 if reset else 0), "sph_get_body_stats")
+        return dict(calls=st.calls, links=st.links, unions=st.unions, rounds=st.rounds, gave_up=st.gave_up, seconds=st.seconds)
+
     def phase(self, name):
         self._check(getattr(self._L, "sph_phase_" + name)(self._h), "sph_phase_" + name)
 

@@ -119,6 +119,12 @@ class Simulator {
     // valid until the next deriveFlow.  Any out-pointer may be NULL.  false (with a message on stderr) with
     // SPH_GPUS > 1 and where the library answers SPH_ESTATE.
     bool deriveFlow(const float **vortDiv, const float **gradRho, const uint32_t **neighbours);
+    // The bodies of the current state (sph_label_bodies in sph_c_api.h): the connected pieces of fluid at link length
+    // `link` (0: h; else 0 < link <= h).  n labels in particle-id order, numBodies table rows of 8 words (label,
+    // count, bounding box), owned by the simulator, valid until the next labelBodies; *largest is the label of the
+    // body with the most particles.  Any out-pointer may be NULL.  false (with a message on stderr) with SPH_GPUS > 1
+    // and where the library answers SPH_ESTATE or SPH_EINVAL.
+    bool labelBodies(float link, const uint32_t **labels, const uint32_t **table, int *numBodies, uint32_t *largest);
     // The velocities of the current state (sph_download_state), n x 3 floats in particle-id order, into the caller's
     // buffer.  false with SPH_GPUS > 1 and before setup().
     bool getVelocity(float *vel_xyz);

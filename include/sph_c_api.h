@@ -645,6 +645,47 @@ typedef struct SphDeriveStats {
  * path counts none).  Blocks. */
 int sph_get_derive_stats(sph_handle *h, SphDeriveStats *out, int reset);
 
+/* ---- bodies: the connected pieces of fluid (droplets, sheets) and the piece every particle belongs to ----
+ * Additive to version 3: test for SPH_HAS_BODIES.  Defined to the bit in DESIGN.md section 10g ("Bodies"); all fp32,
+ * every operation rounded on its own, in both math modes.  With r2 = link link, two particles i != j are linked when
+ * d2 <= r2, e = p_j - p_i (the words sph_download_state returns), d2 = (ex ex + ey ey) + ez ez; a NaN d2 is no link.
+ * A body is a connected component of that graph, its label the smallest particle id in it; a particle without a
+ * link is a body of one.  Every result is an integer reduced by commutative operations: the same words for any
+ * schedule, kernel path or sweep backend. */
+#define SPH_HAS_BODIES 1
+typedef struct SphBodyOptions {
+    int32_t struct_size;        /* sizeof(SphBodyOptions) */
+    float link;                 /* link length: 0 = h, else finite with 0 < link <= h */
+} SphBodyOptions;
+/* Labels the bodies of the state the handle holds NOW.  opt == NULL: link = h.  State rules, grid handling and error
+ * codes are sph_derive's: the grid is found (phase 1) or built ahead (phase 0), the next step consumes it and no
+ * result of any step changes; SPH_ESTATE before any state, inside an open phase-split step, for
+ * SPH_FLAG_EXTERNAL_STATE handles, with SPH_SWEEP_LINKED and with SPH_KEY_MORTON; SPH_EINVAL for an unset struct_size
+ * and for a link that is not finite, negative or greater than h.  No particles: SPH_OK, no bodies.  Like
+ * sph_extract_surface the call waits on the host once, for the number of bodies, which sizes the table; the table's
+ * kernels and the copies are queued and the call returns.  SPH_BODIES_PLAIN=1 in the environment selects the check
+ * path (min-label propagation, one thread per row, repeated until nothing changes; identical words).  SPH_EHIP, and no
+ * results, if a bounded loop of the default path ran out of trips (SphBodyStats.gave_up; never with a correct kernel). */
+int sph_label_bodies(sph_handle *h, const SphBodyOptions *opt);
+/* The results of the last sph_label_bodies, owned by the handle, valid until the next one: labels = n words in
+ * particle-id order; table = num_bodies rows of 8 words in ascending label order: label, count, the bounding box's
+ * minimum x y z and maximum x y z as fp32 bit patterns (extrema by the diagnostics' ordering key); largest = the label
+ * of the body with the greatest count, the smallest such label on a tie (0 without particles).  Blocks until the
+ * copies have landed.  Any out-pointer may be NULL; pointers returned for empty results may be NULL.  SPH_ESTATE before
+ * the first sph_label_bodies. */
+int sph_bodies_host(sph_handle *h, const uint32_t **labels, int *n, const uint32_t **table, int *num_bodies, uint32_t *largest);
+typedef struct SphBodyStats {
+    int32_t struct_size, pad_;  /* sizeof(SphBodyStats), 0: both written by the call */
+    int64_t calls;              /* labellings that ran a kernel (either path) */
+    uint64_t links;             /* unordered linked pairs found (exact) */
+    uint64_t unions;            /* successful merges: n - num_bodies, whatever the schedule */
+    uint64_t rounds;            /* sweeps the check path needed (the default path: 0) */
+    uint64_t gave_up;           /* lanes of the default path that left a bounded loop at its bound: always 0 */
+    double seconds;             /* GPU time of the kernels (HIP events on the compute stream) */
+} SphBodyStats;
+/* Sums since create or since the last reset.  Blocks. */
+int sph_get_body_stats(sph_handle *h, SphBodyStats *out, int reset);
+
 const char *sph_build_info(void);
 
 #ifdef __cplusplus
