@@ -21,7 +21,7 @@
 //
 // Both paths then share mark + scan (which particle ids are labels, and how many labels lie below each) and the
 // table launches.  Candidates are read from global memory on both paths (no LDS staging; section 10g says why).
-#include "sweep_common.h"
+#include "walk_common.h"
 
 namespace {
 
@@ -59,15 +59,6 @@ __device__ __forceinline__ bool linked(const float4 pi, const float4 c, float r2
     const float ex = c.x - pi.x, ey = c.y - pi.y, ez = c.z - pi.z;
     const float d2 = (ex * ex + ey * ey) + ez * ez;
     return d2 <= r2; // (false for a NaN)
-}
-
-__device__ __forceinline__ void body_runs(const DevParams &P, const BodyArgs &A, const float4 pi, bool valid, int (&js)[9], int (&je)[9]) {
-    load_runs(P, A.cellRange, sweep_cell(P, pi.x, pi.y, pi.z), valid, js, je);
-#pragma unroll
-    for (int r = 0; r < 9; ++r) {
-        js[r] = max(js[r], 0);
-        je[r] = min(je[r], A.n);
-    }
 }
 
 __device__ __forceinline__ uint32_t trip_bound(int n) {
@@ -119,10 +110,10 @@ __device__ __forceinline__ uint32_t unite(const BodyArgs &A, uint32_t a, uint32_
 // first launch of a call: every row its own tree (check path: its own label), no particle id a label yet
 __global__ __launch_bounds__(256) void k_body_clear(BodyArgs A, bool plain) {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= A.n) return;
+    if (i >= A.S.n) return;
     A.flag[i] = 0;
     if (plain) {
-        A.rowLabel[i] = __float_as_uint(A.pos[(size_t)i * A.stride].w);
+        A.rowLabel[i] = __float_as_uint(A.S.position(i).w);
     } else {
         A.parent[i] = (uint32_t)i;
         A.rootId[i] = kNoId;
@@ -134,11 +125,11 @@ __global__ __launch_bounds__(256) void k_body_clear(BodyArgs A, bool plain) {
 // so every unordered pair is met once, by its later row.
 __global__ __launch_bounds__(256) void k_body_link(DevParams P, BodyArgs A) {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    const bool valid = i < A.n;
-    const float4 pi = A.pos[(size_t)(valid ? i : 0) * A.stride];
+    const bool valid = i < A.S.n;
+    const float4 pi = A.S.position(valid ? i : 0);
     int js[9], je[9];
-    body_runs(P, A, pi, valid, js, je);
-    const uint32_t budget = trip_bound(A.n);
+    clipped_runs(P, A.S, pi, valid, js, je);
+    const uint32_t budget = trip_bound(A.S.n);
     uint32_t links = 0, unions = 0;
     bool gave = false;
     uint32_t mine = (uint32_t)(valid ? i : 0); // a row of i's tree, at or near its root
@@ -146,7 +137,7 @@ __global__ __launch_bounds__(256) void k_body_link(DevParams P, BodyArgs A) {
     for (int r = 0; r < 5; ++r) {
         const int end = min(je[r], i);
         for (int j = js[r]; j < end; ++j) {
-            if (!linked(pi, A.pos[(size_t)j * A.stride], A.r2)) continue;
+            if (!linked(pi, A.S.position(j), A.r2)) continue;
             links += 1;
             // j hangs right under mine: one tree already (whatever parent[j] holds is a row of j's component)
             if (load_shared(&A.parent[j]) == mine) continue;
@@ -167,8 +158,8 @@ __global__ __launch_bounds__(256) void k_body_link(DevParams P, BodyArgs A) {
 // climbs go on halving paths for each other, which moves no row to another tree
 __global__ __launch_bounds__(256) void k_body_flatten(BodyArgs A) {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= A.n) return;
-    uint32_t budget = trip_bound(A.n);
+    if (i >= A.S.n) return;
+    uint32_t budget = trip_bound(A.S.n);
     bool gave = false;
     A.root[i] = climb(A, (uint32_t)i, budget, gave);
     if (gave) atomicAdd(&A.counters->gaveUp, 1u);
@@ -202,9 +193,9 @@ __global__ __launch_bounds__(256) void k_body_root_id(BodyArgs A) {
 #pragma unroll 1
     for (int k = 0; k < kBodyFold; ++k) {
         const int i = base + k * 256 + threadIdx.x;
-        const bool valid = i < A.n;
+        const bool valid = i < A.S.n;
         const uint32_t rt = valid ? A.root[i] : 0u;
-        const uint32_t id = valid ? __float_as_uint(A.pos[(size_t)i * A.stride].w) : kNoId;
+        const uint32_t id = valid ? __float_as_uint(A.S.position(i).w) : kNoId;
         unsigned long long rest = __ballot(valid);
         while (rest) {
             uint32_t r0;
@@ -225,12 +216,12 @@ __global__ __launch_bounds__(256) void k_body_root_id(BodyArgs A) {
 // rowLabel (default path: from the roots) and the flag of every particle id that is a label
 __global__ __launch_bounds__(256) void k_body_mark(BodyArgs A, bool plain) {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= A.n) return;
-    const uint32_t id = __float_as_uint(A.pos[(size_t)i * A.stride].w);
+    if (i >= A.S.n) return;
+    const uint32_t id = __float_as_uint(A.S.position(i).w);
     uint32_t lab;
     if (plain) lab = A.rowLabel[i];
     else A.rowLabel[i] = lab = A.rootId[A.root[i]];
-    if (lab == id && id < (uint32_t)A.n) A.flag[id] = 1;
+    if (lab == id && id < (uint32_t)A.S.n) A.flag[id] = 1;
 }
 
 // ---- exclusive scan of flag[0, n) into rank: block sums, their offsets (one block), ranks ----
@@ -261,7 +252,7 @@ __device__ __forceinline__ uint32_t scan_slice(const BodyArgs &A, uint32_t (&f)[
     uint32_t sum = 0;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-        f[k] = first + k < A.n ? A.flag[first + k] : 0u;
+        f[k] = first + k < A.S.n ? A.flag[first + k] : 0u;
         sum += f[k];
     }
     return sum;
@@ -294,7 +285,7 @@ __global__ __launch_bounds__(256) void k_body_scan_ranks(BodyArgs A) {
     const int first = blockIdx.x * kBodyScanTile + threadIdx.x * 8;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-        if (first + k < A.n) A.rank[first + k] = before;
+        if (first + k < A.S.n) A.rank[first + k] = before;
         before += f[k];
     }
 }
@@ -302,16 +293,16 @@ __global__ __launch_bounds__(256) void k_body_scan_ranks(BodyArgs A) {
 // ---- the check path's round ----
 __global__ __launch_bounds__(256) void k_body_plain_round(DevParams P, BodyArgs A, bool first) {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    const bool valid = i < A.n;
-    const float4 pi = A.pos[(size_t)(valid ? i : 0) * A.stride];
+    const bool valid = i < A.S.n;
+    const float4 pi = A.S.position(valid ? i : 0);
     int js[9], je[9];
-    body_runs(P, A, pi, valid, js, je);
+    clipped_runs(P, A.S, pi, valid, js, je);
     const uint32_t mine = valid ? load_shared(&A.rowLabel[i]) : 0u;
     uint32_t m = mine, links = 0;
 #pragma unroll
     for (int r = 0; r < 9; ++r)
         for (int j = js[r]; j < je[r]; ++j) {
-            if (j == i || !linked(pi, A.pos[(size_t)j * A.stride], A.r2)) continue;
+            if (j == i || !linked(pi, A.S.position(j), A.r2)) continue;
             links += j < i ? 1u : 0u;
             m = min(m, load_shared(&A.rowLabel[j]));
         }
@@ -329,7 +320,7 @@ __global__ __launch_bounds__(256) void k_body_plain_round(DevParams P, BodyArgs 
 // the row of every label: label, count 0, the identities of the key minima and maxima
 __global__ __launch_bounds__(256) void k_body_table_init(BodyArgs A, int numBodies) {
     const int id = blockIdx.x * 256 + threadIdx.x;
-    if (id >= A.n || !A.flag[id]) return;
+    if (id >= A.S.n || !A.flag[id]) return;
     const uint32_t b = A.rank[id];
     if (b >= (uint32_t)numBodies) return; // (never: the ranks of the flagged ids are 0 .. numBodies - 1)
     uint32_t *t = A.table + 8 * (size_t)b;
@@ -354,7 +345,7 @@ __global__ __launch_bounds__(256) void k_body_table_fill(BodyArgs A, int numBodi
     const int lane = threadIdx.x & 63;
     if (threadIdx.x == 0) {
         const uint32_t lab = A.rowLabel[base];
-        const uint32_t b = lab < (uint32_t)A.n ? A.rank[lab] : kNoId;
+        const uint32_t b = lab < (uint32_t)A.S.n ? A.rank[lab] : kNoId;
         fold[0] = b < (uint32_t)numBodies ? b : kNoId; // (kNoId: no row of the block matches, nothing is folded)
         fold[1] = 0;
         fold[2] = fold[3] = fold[4] = 0xFFFFFFFFu;
@@ -365,11 +356,11 @@ __global__ __launch_bounds__(256) void k_body_table_fill(BodyArgs A, int numBodi
 #pragma unroll 1
     for (int k = 0; k < kBodyFold; ++k) {
         const int i = base + k * 256 + threadIdx.x;
-        bool valid = i < A.n;
-        const float4 p = A.pos[(size_t)(valid ? i : 0) * A.stride];
+        bool valid = i < A.S.n;
+        const float4 p = A.S.position(valid ? i : 0);
         const uint32_t id = __float_as_uint(p.w);
         const uint32_t lab = valid ? A.rowLabel[i] : 0u;
-        valid = valid && id < (uint32_t)A.n && lab < (uint32_t)A.n;
+        valid = valid && id < (uint32_t)A.S.n && lab < (uint32_t)A.S.n;
         const uint32_t b = valid ? A.rank[lab] : 0u;
         valid = valid && b < (uint32_t)numBodies; // (never false for a state whose ids are a permutation of [0, n))
         if (valid) A.labels[id] = lab;
@@ -414,8 +405,8 @@ inline int blocks_of(int n) { return (n + 255) / 256; }
 inline int fold_blocks_of(int n) { return (n + 256 * kBodyFold - 1) / (256 * kBodyFold); }
 
 void launch_mark_and_scan(const BodyArgs &A, bool plain, hipStream_t s) {
-    const int sb = sph_body_scan_blocks(A.n);
-    k_body_mark<<<blocks_of(A.n), 256, 0, s>>>(A, plain);
+    const int sb = sph_body_scan_blocks(A.S.n);
+    k_body_mark<<<blocks_of(A.S.n), 256, 0, s>>>(A, plain);
     k_body_scan_sums<<<sb, 256, 0, s>>>(A);
     k_body_scan_offsets<<<1, 256, 0, s>>>(A, sb);
     k_body_scan_ranks<<<sb, 256, 0, s>>>(A);
@@ -426,35 +417,35 @@ void launch_mark_and_scan(const BodyArgs &A, bool plain, hipStream_t s) {
 int sph_body_scan_blocks(int n) { return n > 0 ? (n + kBodyScanTile - 1) / kBodyScanTile : 0; }
 
 void sph_launch_bodies_unite(const DevParams &P, const BodyArgs &A, hipStream_t s) {
-    if (A.n <= 0) return;
+    if (A.S.n <= 0) return;
     (void)hipMemsetAsync(A.counters, 0, sizeof(BodyCounters), s);
-    k_body_clear<<<blocks_of(A.n), 256, 0, s>>>(A, false);
-    k_body_link<<<blocks_of(A.n), 256, 0, s>>>(P, A);
-    k_body_flatten<<<blocks_of(A.n), 256, 0, s>>>(A);
-    k_body_root_id<<<fold_blocks_of(A.n), 256, 0, s>>>(A);
+    k_body_clear<<<blocks_of(A.S.n), 256, 0, s>>>(A, false);
+    k_body_link<<<blocks_of(A.S.n), 256, 0, s>>>(P, A);
+    k_body_flatten<<<blocks_of(A.S.n), 256, 0, s>>>(A);
+    k_body_root_id<<<fold_blocks_of(A.S.n), 256, 0, s>>>(A);
     launch_mark_and_scan(A, false, s);
 }
 
 void sph_launch_bodies_plain_begin(const BodyArgs &A, hipStream_t s) {
-    if (A.n <= 0) return;
+    if (A.S.n <= 0) return;
     (void)hipMemsetAsync(A.counters, 0, sizeof(BodyCounters), s);
-    k_body_clear<<<blocks_of(A.n), 256, 0, s>>>(A, true);
+    k_body_clear<<<blocks_of(A.S.n), 256, 0, s>>>(A, true);
 }
 
 void sph_launch_bodies_plain_round(const DevParams &P, const BodyArgs &A, bool first, hipStream_t s) {
-    if (A.n <= 0) return;
+    if (A.S.n <= 0) return;
     (void)hipMemsetAsync(&A.counters->changed, 0, sizeof(uint32_t), s);
-    k_body_plain_round<<<blocks_of(A.n), 256, 0, s>>>(P, A, first);
+    k_body_plain_round<<<blocks_of(A.S.n), 256, 0, s>>>(P, A, first);
 }
 
 void sph_launch_bodies_plain_end(const BodyArgs &A, hipStream_t s) {
-    if (A.n <= 0) return;
+    if (A.S.n <= 0) return;
     launch_mark_and_scan(A, true, s);
 }
 
 void sph_launch_bodies_table(const BodyArgs &A, int numBodies, hipStream_t s) {
-    if (A.n <= 0 || numBodies <= 0) return;
-    k_body_table_init<<<blocks_of(A.n), 256, 0, s>>>(A, numBodies);
-    k_body_table_fill<<<fold_blocks_of(A.n), 256, 0, s>>>(A, numBodies);
+    if (A.S.n <= 0 || numBodies <= 0) return;
+    k_body_table_init<<<blocks_of(A.S.n), 256, 0, s>>>(A, numBodies);
+    k_body_table_fill<<<fold_blocks_of(A.S.n), 256, 0, s>>>(A, numBodies);
     k_body_table_finish<<<blocks_of(numBodies), 256, 0, s>>>(A, numBodies);
 }

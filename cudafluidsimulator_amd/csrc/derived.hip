@@ -8,14 +8,11 @@
 // already, so their runs overlap -- and for each of the nine runs stages the UNION of its lanes' ranges in LDS as
 // 32-byte records (x, y, z, id, vx, vy, vz, .); every lane then walks its own range [js[r], je[r]) from the staged
 // slice, four candidates per trip, with unconditional reads (an exhausted lane reads the slice's last record again)
-// and SELECTED terms: take ? term : 0.f, never a product with a mask, because the term of a candidate that is not
-// taken is garbage of either sign.  Adding the selected +0.f changes no bit: a float sum that starts at +0.f is
-// never -0.f under round-to-nearest (x + y is -0 only when both are, an exact cancellation gives +0), although the
-// terms are signed.  A run whose union is longer than the slice (a wave that spans two rows of cells, a crowded
+// and selected terms, which change no bit (walk_common.h).  A run whose union is longer than the slice (a wave that spans two rows of cells, a crowded
 // cell) is walked by every lane from global memory, in the same order with the same arithmetic, so both walks give
 // the same words.  One workgroup is one wave; its barriers are wave-uniform (u0, u1 and the trip count are made
 // uniform through readfirstlane); nothing spins and no workgroup talks to another.
-#include "sweep_common.h"
+#include "walk_common.h"
 
 namespace {
 
@@ -45,12 +42,10 @@ struct DeriveTerms {
 __device__ __forceinline__ DeriveTerms derive_terms(const DevParams &P, const float4 pi, const float4 vi, const float4 c, const float4 v) {
     DeriveTerms T;
     const float ex = c.x - pi.x, ey = c.y - pi.y, ez = c.z - pi.z;
-    const float d2 = (ex * ex + ey * ey) + ez * ez;
-    T.taken = !(d2 > P.h2);
-    const float diff = P.h2 - d2;
-    const float a = (P.dcoef * diff) * diff;
-    T.m = SPH_MASS * (a * diff);
-    const float w = SPH_MASS * a;
+    const Poly6 K = poly6_mass(P, (ex * ex + ey * ey) + ez * ez);
+    T.taken = K.taken;
+    T.m = K.m;
+    const float w = SPH_MASS * K.a;
     const float ux = v.x - vi.x, uy = v.y - vi.y, uz = v.z - vi.z;
     T.gx = w * ex;
     T.gy = w * ey;
@@ -96,7 +91,7 @@ __device__ __forceinline__ void derive_add(const DevParams &P, const float4 pi, 
 // results and the three stores of the row whose position words are pi: to the slot of its particle id
 __device__ __forceinline__ void derive_finish(const DeriveArgs &A, const float4 pi, const DeriveAcc &S) {
     const uint32_t id = __float_as_uint(pi.w);
-    if (id >= (uint32_t)A.n) return; // (the ids of a state are a permutation of [0, n): never taken)
+    if (id >= (uint32_t)A.S.n) return; // (the ids of a state are a permutation of [0, n): never taken)
     float4 w = make_float4(0.f, 0.f, 0.f, 0.f);
     if (S.rho > 0.f) {
         w.x = (6.f * S.cx) / S.rho;
@@ -109,28 +104,17 @@ __device__ __forceinline__ void derive_finish(const DeriveArgs &A, const float4 
     A.neighbours[id] = S.count;
 }
 
-// the nine runs of a row, clipped to the stream
-__device__ __forceinline__ void derive_runs(const DevParams &P, const DeriveArgs &A, const float4 pi, bool valid, int (&js)[9], int (&je)[9]) {
-    load_runs(P, A.cellRange, sweep_cell(P, pi.x, pi.y, pi.z), valid, js, je);
-#pragma unroll
-    for (int r = 0; r < 9; ++r) {
-        js[r] = max(js[r], 0);
-        je[r] = min(je[r], A.n);
-    }
-}
-
 // the check path (SPH_DERIVE_PLAIN=1): one thread per row of the sorted stream, every candidate from global memory
 __global__ __launch_bounds__(256) void k_derive_plain(DevParams P, DeriveArgs A) {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    const bool valid = i < A.n;
-    const size_t row = (size_t)(valid ? i : 0) * A.stride;
-    const float4 pi = A.pos[row], vi = A.vel[row];
+    const bool valid = i < A.S.n;
+    const float4 pi = A.S.position(valid ? i : 0), vi = A.S.velocity(valid ? i : 0);
     int js[9], je[9];
-    derive_runs(P, A, pi, valid, js, je);
+    clipped_runs(P, A.S, pi, valid, js, je);
     DeriveAcc S;
 #pragma unroll
     for (int r = 0; r < 9; ++r)
-        for (int j = js[r]; j < je[r]; ++j) derive_add(P, pi, vi, A.pos[(size_t)j * A.stride], A.vel[(size_t)j * A.stride], S);
+        for (int j = js[r]; j < je[r]; ++j) derive_add(P, pi, vi, A.S.position(j), A.S.velocity(j), S);
     if (valid) derive_finish(A, pi, S);
 }
 
@@ -139,11 +123,10 @@ __global__ __launch_bounds__(64) void k_derive_wave(DevParams P, DeriveArgs A) {
     __shared__ float4 slice[2 * kDeriveSlice];
     const int lane = threadIdx.x;
     const int i = blockIdx.x * 64 + lane;
-    const bool valid = i < A.n;
-    const size_t row = (size_t)(valid ? i : 0) * A.stride;
-    const float4 pi = A.pos[row], vi = A.vel[row];
+    const bool valid = i < A.S.n;
+    const float4 pi = A.S.position(valid ? i : 0), vi = A.S.velocity(valid ? i : 0);
     int js[9], je[9];
-    derive_runs(P, A, pi, valid, js, je);
+    clipped_runs(P, A.S, pi, valid, js, je);
     DeriveAcc S;
     uint32_t staged = 0, direct = 0;
     // one copy of the loop body (not nine): r is wave-uniform, picking this run's bounds is 16 conditional moves
@@ -163,12 +146,12 @@ __global__ __launch_bounds__(64) void k_derive_wave(DevParams P, DeriveArgs A) {
         const int len = u1 - u0;
         if (len > kDeriveSlice) {
             direct += 1;
-            for (int j = jsr; j < jer; ++j) derive_add(P, pi, vi, A.pos[(size_t)j * A.stride], A.vel[(size_t)j * A.stride], S);
+            for (int j = jsr; j < jer; ++j) derive_add(P, pi, vi, A.S.position(j), A.S.velocity(j), S);
             continue;
         }
         staged += 1;
         // 32 bytes per candidate; with the interleaved records (vel = pos + 1, stride 2) a plain copy
-        for (int t = lane; t < 2 * len; t += 64) slice[t] = ((t & 1) ? A.vel : A.pos)[(size_t)(u0 + (t >> 1)) * A.stride];
+        for (int t = lane; t < 2 * len; t += 64) slice[t] = ((t & 1) ? A.S.vel : A.S.pos)[(size_t)(u0 + (t >> 1)) * A.S.stride];
         __syncthreads();
         // this lane's range in slots of the slice, [a, b) within [0, len); every read is clamped to slot len - 1
         const int a = nonempty ? jsr - u0 : 0, b = nonempty ? jer - u0 : 0;
@@ -195,7 +178,8 @@ __global__ __launch_bounds__(64) void k_derive_wave(DevParams P, DeriveArgs A) {
 } // namespace
 
 void sph_launch_derive(const DevParams &P, const DeriveArgs &A, bool plain, hipStream_t s) {
-    if (A.n <= 0) return;
-    if (plain) k_derive_plain<<<(A.n + 255) / 256, 256, 0, s>>>(P, A);
-    else k_derive_wave<<<(A.n + 63) / 64, 64, 0, s>>>(P, A);
+    const int n = A.S.n;
+    if (n <= 0) return;
+    if (plain) k_derive_plain<<<(n + 255) / 256, 256, 0, s>>>(P, A);
+    else k_derive_wave<<<(n + 63) / 64, 64, 0, s>>>(P, A);
 }

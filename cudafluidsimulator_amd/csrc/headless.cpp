@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -33,23 +34,51 @@ static int env_field(const char *var, const char *instead) {
 // SPH_FREE_SHADE: the field that colours the frames; unset: the reference's flat blue
 static int shade_field() { return env_field("SPH_FREE_SHADE", "writing flat frames"); }
 
+// <dir>/<pattern with the frame number f> opened for writing bytes, or NULL after a complaint on stderr
+static FILE *open_out(const char *dir, const char *pattern, int f) {
+    char name[32];
+    snprintf(name, sizeof name, pattern, f);
+    const std::string path = std::string(dir) + "/" + name;
+    FILE *out = fopen(path.c_str(), "wb");
+    if (!out) fprintf(stderr, "sph: cannot write %s\n", path.c_str());
+    return out;
+}
+
+static bool write_bytes(FILE *out, const void *p, size_t bytes) { return bytes == 0 || fwrite(p, 1, bytes, out) == bytes; }
+
+// a w x h image of RGB bytes, row 0 on top, as binary P6
+static bool write_ppm(const char *dir, const char *pattern, int f, int w, int h, const void *rgb) {
+    FILE *out = open_out(dir, pattern, f);
+    if (!out) return false;
+    fprintf(out, "P6\n%d %d\n255\n", w, h);
+    const bool ok = write_bytes(out, rgb, (size_t)w * (size_t)h * 3);
+    return (fclose(out) == 0) && ok;
+}
+
+// Binary little-endian PLY (binary keeps the floats' bits): `count` vertices whose properties are `props`, as the
+// packed rows of `rowBytes` each say; with faces >= 0 also that many triangles, `list uchar int vertex_indices`, as
+// packed 13-byte rows (the count 3, then three 32-bit indices).
+struct PlyProp {
+    const char *type, *name;
+};
+static bool write_ply(const char *dir, const char *pattern, int f, long long count, std::initializer_list<PlyProp> props,
+                      const void *rows, size_t rowBytes, long long faces = -1, const void *faceRows = NULL) {
+    FILE *out = open_out(dir, pattern, f);
+    if (!out) return false;
+    fprintf(out, "ply\nformat binary_little_endian 1.0\nelement vertex %lld\n", count);
+    for (const PlyProp &p : props) fprintf(out, "property %s %s\n", p.type, p.name);
+    if (faces >= 0) fprintf(out, "element face %lld\nproperty list uchar int vertex_indices\n", faces);
+    fprintf(out, "end_header\n");
+    bool ok = write_bytes(out, rows, (size_t)count * rowBytes);
+    if (faces > 0) ok = ok && write_bytes(out, faceRows, (size_t)faces * 13);
+    return (fclose(out) == 0) && ok;
+}
+
 // SPH_FREE_FRAMES_DIR=<dir>: what the window would have shown after frame f, as <dir>/frame_%04d.ppm (binary P6)
 static bool write_frame(Simulator *simulator, const char *dir, int f, int field) {
     int w = 0, h = 0;
     const unsigned char *rgb = field < 0 ? simulator->renderFrame(&w, &h) : simulator->renderField(field, &w, &h);
-    if (!rgb) return false;
-    char name[32];
-    snprintf(name, sizeof name, "/frame_%04d.ppm", f);
-    const std::string path = std::string(dir) + name;
-    FILE *out = fopen(path.c_str(), "wb");
-    if (!out) {
-        fprintf(stderr, "sph: cannot write %s\n", path.c_str());
-        return false;
-    }
-    fprintf(out, "P6\n%d %d\n255\n", w, h);
-    const size_t bytes = (size_t)w * (size_t)h * 3;
-    const bool ok = fwrite(rgb, 1, bytes, out) == bytes;
-    return (fclose(out) == 0) && ok;
+    return rgb && write_ppm(dir, "frame_%04d.ppm", f, w, h, rgb);
 }
 
 // SPH_FREE_SLICE=speed|density|pressure: beside each frame the cut plane z = 5 of that field, sampled on 400 x 400
@@ -80,22 +109,11 @@ static bool write_slice(Simulator *simulator, const char *dir, int f, int field)
             else if (q < 192u) p[0] = (unsigned char)(4u * (q - 128u)), p[1] = 255, p[2] = 0;
             else p[0] = 255, p[1] = (unsigned char)(255u - 4u * (q - 192u)), p[2] = 0;
         }
-    char name[32];
-    snprintf(name, sizeof name, "/slice_%04d.ppm", f);
-    const std::string path = std::string(dir) + name;
-    FILE *out = fopen(path.c_str(), "wb");
-    if (!out) {
-        fprintf(stderr, "sph: cannot write %s\n", path.c_str());
-        return false;
-    }
-    fprintf(out, "P6\n%d %d\n255\n", N, N);
-    const bool ok = fwrite(rgb.data(), 1, rgb.size(), out) == rgb.size();
-    return (fclose(out) == 0) && ok;
+    return write_ppm(dir, "slice_%04d.ppm", f, N, N, rgb.data());
 }
 
 // SPH_FREE_SURFACE=<iso>: beside each frame the surface density == iso (sph_extract_surface) over 101^3 lattice
-// points on [0, boxDim]^3, as <dir>/surface_%04d.ply: binary little-endian PLY, `float x y z` vertices and
-// `list uchar int vertex_indices` faces -- binary keeps the vertices' bits.
+// points on [0, boxDim]^3, as <dir>/surface_%04d.ply: `float x y z` vertices and triangles.
 static bool write_surface(Simulator *simulator, const char *dir, int f, float iso) {
     const int N = 101;
     const float sp = simulator->settings->boxDim / (float)(N - 1);
@@ -104,29 +122,17 @@ static bool write_surface(Simulator *simulator, const char *dir, int f, float is
     const unsigned *tris = NULL;
     long long nv = 0, nt = 0;
     if (!simulator->extractSurface(iso, origin, spacing, N, N, N, &verts, &nv, &tris, &nt)) return false;
-    char name[32];
-    snprintf(name, sizeof name, "/surface_%04d.ply", f);
-    const std::string path = std::string(dir) + name;
-    FILE *out = fopen(path.c_str(), "wb");
-    if (!out) {
-        fprintf(stderr, "sph: cannot write %s\n", path.c_str());
-        return false;
-    }
-    fprintf(out, "ply\nformat binary_little_endian 1.0\nelement vertex %lld\nproperty float x\nproperty float y\nproperty float z\n"
-                 "element face %lld\nproperty list uchar int vertex_indices\nend_header\n", nv, nt);
-    bool ok = nv == 0 || fwrite(verts, 12, (size_t)nv, out) == (size_t)nv;
-    std::string faces((size_t)nt * 13, '\0'); // per face: the count 3, then three 32-bit indices
+    std::string faces((size_t)nt * 13, '\0');
     for (long long t = 0; t < nt; ++t) {
         faces[(size_t)t * 13] = 3;
         memcpy(&faces[(size_t)t * 13 + 1], tris + 3 * t, 12);
     }
-    ok = ok && fwrite(faces.data(), 1, faces.size(), out) == faces.size();
-    return (fclose(out) == 0) && ok;
+    return write_ply(dir, "surface_%04d.ply", f, nv, {{"float", "x"}, {"float", "y"}, {"float", "z"}}, verts, 12, nt, faces.data());
 }
 
 // SPH_FREE_TRACERS=<count>: `count` passive tracers (sph_tracers_*), seeded at the setup positions of the particles
 // with ids k n / count, advected by `timestep` after every frame; beside each written frame their state as
-// <dir>/tracers_%04d.ply: binary little-endian PLY, vertex properties `float x y z vx vy vz density`.
+// <dir>/tracers_%04d.ply: vertex properties `float x y z vx vy vz density`.
 static bool seed_tracers(Simulator *simulator, int count) {
     const int n = simulator->settings->numParticles;
     const float3 *p = simulator->getPosition();
@@ -139,28 +145,19 @@ static bool write_tracers(Simulator *simulator, const char *dir, int f) {
     const float *pd = NULL, *u = NULL;
     int m = 0;
     if (!simulator->getTracers(&pd, &u, &m)) return false;
-    char name[32];
-    snprintf(name, sizeof name, "/tracers_%04d.ply", f);
-    const std::string path = std::string(dir) + name;
-    FILE *out = fopen(path.c_str(), "wb");
-    if (!out) {
-        fprintf(stderr, "sph: cannot write %s\n", path.c_str());
-        return false;
-    }
-    fprintf(out, "ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
-                 "property float vx\nproperty float vy\nproperty float vz\nproperty float density\nend_header\n", m);
     std::string rows((size_t)m * 28, '\0');
     for (int i = 0; i < m; ++i) {
         memcpy(&rows[(size_t)i * 28], pd + 4 * (size_t)i, 12);
         memcpy(&rows[(size_t)i * 28 + 12], u + 4 * (size_t)i, 12);
         memcpy(&rows[(size_t)i * 28 + 24], pd + 4 * (size_t)i + 3, 4);
     }
-    const bool ok = fwrite(rows.data(), 1, rows.size(), out) == rows.size();
-    return (fclose(out) == 0) && ok;
+    return write_ply(dir, "tracers_%04d.ply", f, m,
+                     {{"float", "x"}, {"float", "y"}, {"float", "z"}, {"float", "vx"}, {"float", "vy"}, {"float", "vz"}, {"float", "density"}},
+                     rows.data(), 28);
 }
 
 // SPH_FREE_PARTICLES=1: beside each written frame the particles with their derived fields (sph_derive) as
-// <dir>/particles_%04d.ply: binary little-endian PLY, one vertex per particle in id order, properties
+// <dir>/particles_%04d.ply: one vertex per particle in id order, properties
 // `float x y z vx vy vz rho wx wy wz divergence gx gy gz` and `uint neighbours`.
 static bool write_particles(Simulator *simulator, const char *dir, int f) {
     const int n = simulator->settings->numParticles;
@@ -170,18 +167,6 @@ static bool write_particles(Simulator *simulator, const char *dir, int f) {
     const float3 *p = simulator->getPosition();
     std::string vel((size_t)(n > 0 ? n : 1) * 12, '\0');
     if (!p || !simulator->getVelocity(reinterpret_cast<float *>(&vel[0]))) return false;
-    char name[32];
-    snprintf(name, sizeof name, "/particles_%04d.ply", f);
-    const std::string path = std::string(dir) + name;
-    FILE *out = fopen(path.c_str(), "wb");
-    if (!out) {
-        fprintf(stderr, "sph: cannot write %s\n", path.c_str());
-        return false;
-    }
-    fprintf(out, "ply\nformat binary_little_endian 1.0\nelement vertex %d\n", n);
-    for (const char *k : {"x", "y", "z", "vx", "vy", "vz", "rho", "wx", "wy", "wz", "divergence", "gx", "gy", "gz"})
-        fprintf(out, "property float %s\n", k);
-    fprintf(out, "property uint neighbours\nend_header\n");
     std::string rows((size_t)n * 60, '\0');
     for (int i = 0; i < n; ++i) {
         char *r = &rows[(size_t)i * 60];
@@ -192,14 +177,16 @@ static bool write_particles(Simulator *simulator, const char *dir, int f) {
         memcpy(r + 44, gr + 4 * (size_t)i, 12);     // gx gy gz
         memcpy(r + 56, nb + i, 4);
     }
-    const bool ok = fwrite(rows.data(), 1, rows.size(), out) == rows.size();
-    return (fclose(out) == 0) && ok;
+    return write_ply(dir, "particles_%04d.ply", f, n,
+                     {{"float", "x"}, {"float", "y"}, {"float", "z"}, {"float", "vx"}, {"float", "vy"}, {"float", "vz"}, {"float", "rho"},
+                      {"float", "wx"}, {"float", "wy"}, {"float", "wz"}, {"float", "divergence"}, {"float", "gx"}, {"float", "gy"},
+                      {"float", "gz"}, {"uint", "neighbours"}},
+                     rows.data(), 60);
 }
 
 // SPH_FREE_BODIES=<f>, f in (0, 1], the link length in units of h: beside each written frame the particles with the
-// body they belong to (sph_label_bodies) as <dir>/bodies_%04d.ply: binary little-endian PLY, one vertex per particle in
-// id order, properties `float x y z`, `uint label` and `uint body_count`; and one line on stderr,
-// `bodies <frame> <num_bodies> <largest count>`.
+// body they belong to (sph_label_bodies) as <dir>/bodies_%04d.ply: one vertex per particle in id order, properties
+// `float x y z`, `uint label` and `uint body_count`; and one line on stderr, `bodies <frame> <num_bodies> <largest count>`.
 static bool write_bodies(Simulator *simulator, const char *dir, int f, float link) {
     const int n = simulator->settings->numParticles;
     const uint32_t *labels = NULL, *table = NULL;
@@ -215,16 +202,6 @@ static bool write_bodies(Simulator *simulator, const char *dir, int f, float lin
         countOf[table[8 * (size_t)b]] = table[8 * (size_t)b + 1];
         if (table[8 * (size_t)b] == largest) most = table[8 * (size_t)b + 1];
     }
-    char name[32];
-    snprintf(name, sizeof name, "/bodies_%04d.ply", f);
-    const std::string path = std::string(dir) + name;
-    FILE *out = fopen(path.c_str(), "wb");
-    if (!out) {
-        fprintf(stderr, "sph: cannot write %s\n", path.c_str());
-        return false;
-    }
-    fprintf(out, "ply\nformat binary_little_endian 1.0\nelement vertex %d\n", n);
-    fprintf(out, "property float x\nproperty float y\nproperty float z\nproperty uint label\nproperty uint body_count\nend_header\n");
     std::string rows((size_t)n * 20, '\0');
     for (int i = 0; i < n; ++i) {
         char *r = &rows[(size_t)i * 20];
@@ -232,9 +209,10 @@ static bool write_bodies(Simulator *simulator, const char *dir, int f, float lin
         memcpy(r + 12, labels + i, 4);
         memcpy(r + 16, &countOf[labels[i]], 4);
     }
-    const bool ok = fwrite(rows.data(), 1, rows.size(), out) == rows.size();
-    fprintf(stderr, "bodies %d %d %u\n", f, bodies, most);
-    return (fclose(out) == 0) && ok;
+    const bool ok = write_ply(dir, "bodies_%04d.ply", f, n,
+                              {{"float", "x"}, {"float", "y"}, {"float", "z"}, {"uint", "label"}, {"uint", "body_count"}}, rows.data(), 20);
+    if (ok) fprintf(stderr, "bodies %d %d %u\n", f, bodies, most);
+    return ok;
 }
 
 // SPH_FREE_STATS=1: for each written frame one JSON line of run diagnostics (Simulator::diagnostics) in

@@ -10,8 +10,7 @@
 // chunk, and every lane reads every staged candidate by broadcast; a lane TAKES candidate k only if k lies in
 // its own run, two integer compares.  The distance test alone would not do: a candidate two cells off can round
 // to within h and add a non-zero term, and the sum would no longer be the plain walk's, bit for bit.
-#include "sph_c_api.h"
-#include "sph_device.h"
+#include "walk_common.h"
 
 namespace {
 
@@ -23,40 +22,26 @@ __device__ __forceinline__ float sample_scalar(const float4 v, int field) {
     return fmaxf(0.f, SPH_GAS_CONSTANT * (v.w - SPH_REST_DENSITY));
 }
 
-// the cell of a coordinate, (int)(p / h) like the cell hash, or -1 for a point outside the grid
-// (the range tests come before the conversion: a float beyond the int range must not reach it)
-__device__ __forceinline__ int sample_cell(const DevParams &P, float p) {
-    if (!(p >= 0.f)) return -1;
-    const float q = p / P.h;
-    if (!(q < (float)P.D)) return -1; // (int)q >= D
-    return (int)q;
-}
-
 // one candidate: c = (x, y, z, a_j)
 template <bool kShepard>
 __device__ __forceinline__ void sample_add(const DevParams &P, float px, float py, float pz, const float4 c, float &den,
                                            float &num) {
     const float dx = px - c.x, dy = py - c.y, dz = pz - c.z;
-    const float d2 = (dx * dx + dy * dy) + dz * dz;
-    if (d2 > P.h2) return;
-    const float diff = P.h2 - d2;
-    const float m = SPH_MASS * (((P.dcoef * diff) * diff) * diff);
-    if (kShepard) num += m * c.w;
-    den += m;
+    const Poly6 K = poly6_mass(P, (dx * dx + dy * dy) + dz * dz);
+    if (!K.taken) return;
+    if (kShepard) num += K.m * c.w;
+    den += K.m;
 }
 
-// the same without a branch: a candidate that is not taken, or lies beyond h, adds +0 (den and num never fall
-// below +0: m >= +0 and a_j >= +0, so the sums keep their bits)
+// the same with selected terms (walk_common.h): a candidate that is not taken, or lies beyond h, adds +0
 template <bool kShepard>
 __device__ __forceinline__ void sample_add(const DevParams &P, float px, float py, float pz, const float4 c, bool take,
                                            float &den, float &num) {
     const float dx = px - c.x, dy = py - c.y, dz = pz - c.z;
-    const float d2 = (dx * dx + dy * dy) + dz * dz;
-    take = take && !(d2 > P.h2);
-    const float diff = P.h2 - d2;
-    const float m = SPH_MASS * (((P.dcoef * diff) * diff) * diff);
-    if (kShepard) num += take ? m * c.w : 0.f;
-    den += take ? m : 0.f;
+    const Poly6 K = poly6_mass(P, (dx * dx + dy * dy) + dz * dz);
+    take = take && K.taken;
+    if (kShepard) num += take ? K.m * c.w : 0.f;
+    den += take ? K.m : 0.f;
 }
 
 template <bool kShepard>
@@ -67,37 +52,22 @@ __device__ __forceinline__ float sample_value(float den, float num) {
 
 template <bool kShepard>
 __device__ __forceinline__ float4 sample_candidate(const SampleArgs &A, int j) {
-    float4 c = A.pos[(size_t)j * A.stride];
-    if (kShepard) c.w = sample_scalar(A.vel[(size_t)j * A.stride], A.field);
+    float4 c = A.S.position(j);
+    if (kShepard) c.w = sample_scalar(A.S.velocity(j), A.field);
     return c;
 }
 
-// the check path (SPH_SAMPLE_PLAIN=1): one thread per lattice point, nine runs of direct global loads
+// the check path (SPH_SAMPLE_PLAIN=1): one thread per lattice point, 27 cells of direct global loads
 template <bool kShepard>
 __global__ __launch_bounds__(256) void k_sample_plain(DevParams P, SampleArgs A, float *__restrict__ out) {
     const int g = blockIdx.x * 256 + threadIdx.x;
     if (g >= A.nx * A.ny * A.nz) return;
     const int ix = g % A.nx, r = g / A.nx, iy = r % A.ny, iz = r / A.ny;
     const float px = A.ox + (float)ix * A.sx, py = A.oy + (float)iy * A.sy, pz = A.oz + (float)iz * A.sz;
-    const int cx = sample_cell(P, px), cy = sample_cell(P, py), cz = sample_cell(P, pz);
+    const int cx = point_cell(P, px), cy = point_cell(P, py), cz = point_cell(P, pz);
     float den = 0.f, num = 0.f;
-    if (cx >= 0 && cy >= 0 && cz >= 0) {
-        for (int dz = -1; dz < 2; ++dz) {
-            const int sz = cz + dz;
-            if (sz < 0 || sz >= P.D) continue;
-            for (int dy = -1; dy < 2; ++dy) {
-                const int sy = cy + dy;
-                if (sy < 0 || sy >= P.D) continue;
-                for (int dx = -1; dx < 2; ++dx) {
-                    const int sx = cx + dx;
-                    if (sx < 0 || sx >= P.D) continue;
-                    const int2 run = A.cellRange[(sz * P.D + sy) * P.D + sx];
-                    for (int j = max(run.x, 0); j < min(run.y, A.n); ++j)
-                        sample_add<kShepard>(P, px, py, pz, sample_candidate<kShepard>(A, j), den, num);
-                }
-            }
-        }
-    }
+    if (cx >= 0 && cy >= 0 && cz >= 0)
+        for_each_candidate_27(P, A.S, cx, cy, cz, [&](int j) WALK_LAMBDA { sample_add<kShepard>(P, px, py, pz, sample_candidate<kShepard>(A, j), den, num); });
     out[g] = sample_value<kShepard>(den, num);
 }
 
@@ -111,9 +81,9 @@ __global__ __launch_bounds__(64) void k_sample_tile(DevParams P, SampleArgs A, i
     const int ix = brick * 64 + lane;
     const bool valid = ix < A.nx;
     const float px = A.ox + (float)ix * A.sx, py = A.oy + (float)iy * A.sy, pz = A.oz + (float)iz * A.sz;
-    const int cx = valid ? sample_cell(P, px) : -1;
+    const int cx = valid ? point_cell(P, px) : -1;
     // (the same for every lane: the branches and barriers below are wave-uniform)
-    const int cy = __builtin_amdgcn_readfirstlane(sample_cell(P, py)), cz = __builtin_amdgcn_readfirstlane(sample_cell(P, pz));
+    const int cy = __builtin_amdgcn_readfirstlane(point_cell(P, py)), cz = __builtin_amdgcn_readfirstlane(point_cell(P, pz));
     float den = 0.f, num = 0.f;
     if (cy >= 0 && cz >= 0) {
         for (int dz = -1; dz < 2; ++dz) {
@@ -122,40 +92,17 @@ __global__ __launch_bounds__(64) void k_sample_tile(DevParams P, SampleArgs A, i
             for (int dy = -1; dy < 2; ++dy) {
                 const int sy = cy + dy;
                 if (sy < 0 || sy >= P.D) continue;
-                // this lane's window of the stream: the rows of cells cx - 1 .. cx + 1 of this (y, z) row, one
-                // contiguous run (empty cells hold {0, 0} and add nothing); empty for a lane without a point
-                int ws = 0x7fffffff, we = 0;
-                if (cx >= 0) {
-                    const int2 *cells = A.cellRange + (sz * P.D + sy) * P.D;
-                    for (int sx = max(cx - 1, 0); sx <= min(cx + 1, P.D - 1); ++sx) {
-                        const int2 run = cells[sx];
-                        if (run.y > run.x) {
-                            ws = min(ws, run.x);
-                            we = max(we, run.y);
-                        }
-                    }
-                }
-                // the stretch the wave stages: from the first window's start to the last one's end
-                const int s0 = max(__builtin_amdgcn_readfirstlane(wave_min_i32(ws)), 0);
-                const int s1 = min(__builtin_amdgcn_readfirstlane(wave_max_i32(we)), A.n);
+                int ws, we, s0, s1; // this lane's window (empty for a lane without a point), the wave's stretch
+                lane_window(P, A.S, sy, sz, cx, cx >= 0, ws, we);
+                wave_hull(ws, we, A.S.n, s0, s1);
                 for (int base = s0; base < s1; base += kSampleChunk) {
                     const int cnt = min(kSampleChunk, s1 - base);
                     __syncthreads(); // the previous chunk has been read
+                    // 16 bytes per candidate: the scalar folded into .w
                     for (int k = lane; k < cnt; k += 64) cand[k] = sample_candidate<kShepard>(A, base + k);
                     __syncthreads();
-                    // every lane reads every candidate (one LDS address per read: a broadcast) and takes those of
-                    // its own window, in stream order.  Reads and arithmetic are unconditional and a candidate
-                    // that is not taken adds +0, which changes no bit of a sum that is never below +0: the four
-                    // reads of a round are in flight together instead of one wait per candidate.  (Slots past
-                    // cnt hold stale rows: they lie outside every [lo, hi).)
-                    const int lo = max(ws - base, 0), hi = min(we - base, cnt);
-                    for (int k = 0; k < cnt; k += 4) {
-                        float4 c[4];
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) c[u] = cand[k + u];
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) sample_add<kShepard>(P, px, py, pz, c[u], k + u >= lo && k + u < hi, den, num);
-                    }
+                    take_staged<1>(cand, cnt, ws - base, we - base,
+                                   [&](const float4(&c)[1], bool mine) WALK_LAMBDA { sample_add<kShepard>(P, px, py, pz, c[0], mine, den, num); });
                 }
             }
         }
@@ -167,7 +114,7 @@ __global__ __launch_bounds__(64) void k_sample_tile(DevParams P, SampleArgs A, i
 
 void sph_launch_sample(const DevParams &P, const SampleArgs &A, bool plain, float *out, hipStream_t s) {
     const int points = A.nx * A.ny * A.nz;
-    if (A.n <= 0) { // no particle: every sum is empty
+    if (A.S.n <= 0) { // no particle: every sum is empty
         (void)hipMemsetAsync(out, 0, (size_t)points * sizeof(float), s);
         return;
     }

@@ -7,25 +7,15 @@ using namespace sph_host;
 
 namespace {
 
-// nothing queued reads or writes the bodies' buffers any more
-int body_quiesce(sph_handle *h) {
-    HIPCHK(h, hipStreamSynchronize(h->compute));
-    HIPCHK(h, hipStreamSynchronize(h->copy));
-    h->bodyOut.pending = false;
-    h->bodyValid = false;
-    return SPH_OK;
-}
-
 // (re)allocate the per-row and per-id buffers for n particles
 int body_reserve(sph_handle *h, size_t n) {
     if (!h->bodyCounters) {
         HIPCHK(h, h->bodyCounters.alloc(1));
         HIPCHK(h, h->bodyCountersHost.alloc(1));
         HIPCHK(h, h->bodyFinalHost.alloc(1));
-        HIPCHK(h, h->bodyCounted.create(hipEventDisableTiming));
     }
     if (n <= h->bodyCap) return SPH_OK;
-    int rc = body_quiesce(h);
+    int rc = pass_quiesce(h, h->body);
     if (rc) return rc;
     h->bodyCap = 0;
     for (auto *b : {&h->bodyParent, &h->bodyRoot, &h->bodyRootId, &h->bodyRowLabel, &h->bodyFlag, &h->bodyRank, &h->bodyLabels})
@@ -40,7 +30,7 @@ int body_reserve(sph_handle *h, size_t n) {
 int body_reserve_table(sph_handle *h, size_t bodies) {
     if (bodies <= h->bodyTableCap) return SPH_OK;
     HIPCHK(h, hipStreamSynchronize(h->copy)); // the last table may still be on its way out of the old buffer
-    h->bodyOut.pending = false;
+    h->body.out.pending = false;
     h->bodyTableCap = 0;
     HIPCHK(h, h->bodyTable.alloc(bodies * 8));
     HIPCHK(h, h->bodyTableHost.alloc(bodies * 8));
@@ -50,10 +40,7 @@ int body_reserve_table(sph_handle *h, size_t bodies) {
 
 // the counter block to pinned memory, and the one wait of the call (the check path: one per round)
 int body_fetch_counters(sph_handle *h) {
-    HIPCHK(h, hipMemcpyAsync(h->bodyCountersHost.get(), h->bodyCounters.get(), sizeof(BodyCounters), hipMemcpyDeviceToHost, h->compute));
-    HIPCHK(h, hipEventRecord(h->bodyCounted, h->compute));
-    HIPCHK(h, hipEventSynchronize(h->bodyCounted));
-    return SPH_OK;
+    return fetch_small(h, h->bodyCountersHost.get(), h->bodyCounters.get(), sizeof(BodyCounters), h->bodyCounted);
 }
 
 } // namespace
@@ -63,65 +50,52 @@ extern "C" {
 int sph_label_bodies(sph_handle *h, const SphBodyOptions *opt) {
     if (!h) return SPH_EINVAL;
     SPH_ON_DEVICE(h);
-    if (h->external) return reject_slab_mode(h, ": multi-GPU runs label no bodies");
-    if (!h->ready) return fail(h, SPH_ESTATE, "setup()/upload_state() must come first");
-    if (h->opt.sweep == SPH_SWEEP_LINKED) return fail(h, SPH_ESTATE, "the bodies need a cell table: not available with SPH_SWEEP_LINKED");
-    if (h->P.morton) return fail(h, SPH_ESTATE, "the bodies walk rows of cells as runs of the stream: not available with SPH_KEY_MORTON");
-    if (h->phase != 0 && h->phase != 1) return fail(h, SPH_ESTATE, "a step split into phases is still open");
-    SphBodyOptions o{};
-    int rc = copy_options(h, opt, o, "SphBodyOptions.struct_size is not set");
+    int rc = analysis_begin(h, "the bodies' labelling", ": multi-GPU runs label no bodies");
     if (rc) return rc;
+    SphBodyOptions o{};
+    if ((rc = copy_options(h, opt, o, "SphBodyOptions.struct_size is not set"))) return rc;
     if (!std::isfinite(o.link) || o.link < 0.f || o.link > h->P.h) return fail(h, SPH_EINVAL, "link must be 0 (= h) or finite with 0 < link <= h");
     const float link = o.link == 0.f ? h->P.h : o.link;
     const int n = h->n;
     if (n == 0) { // nothing to sweep, nothing to copy
-        if ((rc = outbound_fence(h, h->bodyOut))) return rc;
+        if ((rc = outbound_fence(h, h->body.out))) return rc;
         h->bodyN = h->bodyCount = 0;
-        h->bodyValid = true;
+        h->body.valid = true;
         return SPH_OK;
     }
     if ((rc = body_reserve(h, (size_t)n))) return rc;
-    // a grid of the state the handle holds NOW, found or built ahead exactly as sph_derive does
-    if (h->phase == 0 && (rc = build_grid_ahead(h))) return rc;
-    if ((rc = outbound_fence(h, h->bodyOut))) return rc; // the previous call's copies still read the device buffers
-    h->bodyValid = false; // (until the copies are queued: the pinned buffers still hold the previous results)
+    if ((rc = analysis_grid(h))) return rc;
+    if ((rc = outbound_fence(h, h->body.out))) return rc; // the previous call's copies still read the device buffers
+    h->body.valid = false; // (until the copies are queued: the pinned buffers still hold the previous results)
     const bool plain = plain_path("SPH_BODIES_PLAIN");
     BodyArgs A{};
-    A.n = n;
-    A.cellRange = h->cellRange;
-    if (h->opt.sweep == SPH_SWEEP_LIST && h->pv8) { // the gather left no sorted pos4 of its own in this mode
-        A.pos = h->pv8;
-        A.stride = 2;
-    } else {
-        A.pos = h->pos4[h->sorted];
-        A.stride = 1;
-    }
+    A.S = sorted_stream(h);
     A.r2 = link * link;
     A.parent = h->bodyParent, A.root = h->bodyRoot, A.rootId = h->bodyRootId, A.rowLabel = h->bodyRowLabel;
     A.flag = h->bodyFlag, A.rank = h->bodyRank, A.blockSum = h->bodyBlockSum;
     A.labels = h->bodyLabels;
     A.counters = h->bodyCounters;
-    PairEvent *pe = nullptr;
-    if ((rc = pair_begin(h, &h->bodySeconds, &pe))) return rc;
     unsigned long long rounds = 0;
-    if (!plain) {
-        sph_launch_bodies_unite(h->P, A, h->compute);
-    } else {
+    rc = timed_launch(h, &h->body.seconds, [&]() -> int {
+        if (!plain) {
+            sph_launch_bodies_unite(h->P, A, h->compute);
+            return SPH_OK;
+        }
         // at most n rounds: a label moves at least one link closer to every row of its body in each
         sph_launch_bodies_plain_begin(A, h->compute);
         for (bool changed = true; changed && rounds < (unsigned long long)n; ++rounds) {
             sph_launch_bodies_plain_round(h->P, A, rounds == 0, h->compute);
             HIPCHK(h, hipGetLastError());
-            if ((rc = body_fetch_counters(h))) return rc;
+            if (int rc2 = body_fetch_counters(h)) return rc2;
             changed = h->bodyCountersHost->changed != 0;
         }
         sph_launch_bodies_plain_end(A, h->compute);
-    }
-    HIPCHK(h, hipEventRecord(pe->b, h->compute));
-    HIPCHK(h, hipGetLastError());
+        return SPH_OK;
+    });
+    if (rc) return rc;
     if ((rc = body_fetch_counters(h))) return rc;
     const BodyCounters C = *h->bodyCountersHost.get();
-    h->bodyCalls += 1;
+    h->body.calls += 1;
     h->bodyRounds += rounds;
     h->bodyGaveUp += C.gaveUp;
     if (C.gaveUp) return fail(h, SPH_EHIP, "sph_label_bodies: a bounded loop of the union-find ran out of trips; no results");
@@ -131,25 +105,22 @@ int sph_label_bodies(sph_handle *h, const SphBodyOptions *opt) {
     h->bodyUnions += plain ? (unsigned long long)n - bodies : C.unions;
     if ((rc = body_reserve_table(h, bodies))) return rc;
     A.table = h->bodyTable;
-    if ((rc = pair_begin(h, &h->bodySeconds, &pe))) return rc;
-    sph_launch_bodies_table(A, (int)bodies, h->compute);
-    HIPCHK(h, hipEventRecord(pe->b, h->compute));
-    HIPCHK(h, hipGetLastError());
-    if ((rc = outbound_send(h, h->bodyOut, {{h->bodyLabelsHost.get(), h->bodyLabels.get(), (size_t)n * sizeof(uint32_t)},
+    if ((rc = timed_launch(h, &h->body.seconds, [&] { sph_launch_bodies_table(A, (int)bodies, h->compute); }))) return rc;
+    if ((rc = outbound_send(h, h->body.out, {{h->bodyLabelsHost.get(), h->bodyLabels.get(), (size_t)n * sizeof(uint32_t)},
                                             {h->bodyTableHost.get(), h->bodyTable.get(), bodies * 8 * sizeof(uint32_t)},
                                             {h->bodyFinalHost.get(), h->bodyCounters.get(), sizeof(BodyCounters)}})))
         return rc;
     h->bodyN = n;
     h->bodyCount = (int)bodies;
-    h->bodyValid = true;
+    h->body.valid = true;
     return SPH_OK;
 }
 
 int sph_bodies_host(sph_handle *h, const uint32_t **labels, int *n, const uint32_t **table, int *num_bodies, uint32_t *largest) {
     if (!h) return SPH_EINVAL;
     SPH_ON_DEVICE(h);
-    if (!h->bodyValid) return fail(h, SPH_ESTATE, "sph_label_bodies must come first");
-    HIPCHK(h, outbound_wait(h->bodyOut));
+    if (!h->body.valid) return fail(h, SPH_ESTATE, "sph_label_bodies must come first");
+    HIPCHK(h, outbound_wait(h->body.out));
     const bool any = h->bodyN > 0;
     if (labels) *labels = any ? h->bodyLabelsHost.get() : nullptr;
     if (n) *n = h->bodyN;
@@ -163,7 +134,7 @@ int sph_get_body_stats(sph_handle *h, SphBodyStats *out, int reset) {
     if (!h || !out) return SPH_EINVAL;
     SphBodyStats S{};
     S.struct_size = (int32_t)sizeof S;
-    int rc = timed_total(h, &h->bodySeconds, &h->bodyCalls, &S.seconds, &S.calls, reset);
+    int rc = timed_total(h, &h->body.seconds, &h->body.calls, &S.seconds, &S.calls, reset);
     if (rc) return rc;
     S.links = h->bodyLinks, S.unions = h->bodyUnions, S.rounds = h->bodyRounds, S.gave_up = h->bodyGaveUp;
     if (reset) h->bodyLinks = h->bodyUnions = h->bodyRounds = h->bodyGaveUp = 0;

@@ -248,28 +248,36 @@ __device__ __forceinline__ uint32_t field_bits(const float4 v, int field) {
     return __float_as_uint(s);
 }
 
+// ---- the analysis passes ----
+// The cell-sorted stream of the last grid build, as every pass that walks it reads it: sorted row j is
+// position(j) = (x, y, z, id) and velocity(j) = (vx, vy, vz, rho).  Two layouts, told apart by the stride alone: the
+// sorted pos4 / vel4 streams (stride 1), or -- SPH_SWEEP_LIST, whose gather leaves no sorted vel4 -- the interleaved
+// records pv8 (pos = pv8, vel = pv8 + 1, stride 2).  cellRange holds {start, end} per flattened cell
+// (SPH_KEY_FLATTENED only).  n == 0: no particle, every pointer null, nothing is walked.  Filled by sorted_stream()
+// (sph_step.hip) and by nobody else.
+struct StreamView {
+    const float4 *pos, *vel;
+    int stride;
+    const int2 *cellRange;
+    int n;
+    __device__ __forceinline__ float4 position(int j) const { return pos[(size_t)j * stride]; }
+    __device__ __forceinline__ float4 velocity(int j) const { return vel[(size_t)j * stride]; }
+};
+
 // ---- the field sample (sample.hip; defined in DESIGN.md section 10b) ----
 struct SampleArgs {
     int nx, ny, nz;          // lattice points per axis; point (ix, iy, iz) -> out[(iz ny + iy) nx + ix]
     float ox, oy, oz;        // origin
     float sx, sy, sz;        // spacing
     int field;               // SPH_FIELD_*
-    const float4 *pos;       // sorted row j: pos[j stride] = (x, y, z, id) and vel[j stride] = (vx, vy, vz, rho) --
-    const float4 *vel;       // the sorted pos4 / vel4 streams (stride 1) or the interleaved records (pv8, pv8 + 1; stride 2)
-    int stride;
-    const int2 *cellRange;   // {start, end} per flattened cell (SPH_KEY_FLATTENED only)
-    int n;                   // rows of the stream
+    StreamView S;            // the candidates
 };
 // one value per lattice point into out[0, nx ny nz); plain = the one-thread-per-point check path
 void sph_launch_sample(const DevParams &P, const SampleArgs &A, bool plain, float *out, hipStream_t s);
 
 // ---- passive tracers (tracers.hip; defined in DESIGN.md section 10e) ----
 struct TracerArgs {
-    const float4 *pos;       // the candidates, as SampleArgs reads them: sorted row j at pos[j stride] / vel[j stride]
-    const float4 *vel;
-    int stride;
-    const int2 *cellRange;   // {start, end} per flattened cell (SPH_KEY_FLATTENED only)
-    int n;                   // rows of the stream (0: no particle, nothing is walked)
+    StreamView S;            // the candidates
     int m;                   // tracers
     float dt;
     float4 *posDen;          // [m] caller order: (x, y, z, den); read, then rewritten in place by the tracer's own lane
@@ -284,11 +292,7 @@ void sph_launch_tracers(const DevParams &P, TracerArgs A, bool plain, const Sort
 
 // ---- derived per-particle fields (derived.hip; defined in DESIGN.md section 10f) ----
 struct DeriveArgs {
-    const float4 *pos;       // the sorted stream, as SampleArgs reads it: row j at pos[j stride] / vel[j stride]
-    const float4 *vel;
-    int stride;
-    const int2 *cellRange;   // {start, end} per flattened cell (SPH_KEY_FLATTENED only)
-    int n;                   // rows of the stream, > 0
+    StreamView S;            // the rows and their candidates, n > 0
     float4 *vortDiv;         // [n] particle-id order: (wx, wy, wz, divergence)
     float4 *gradRho;         // [n] particle-id order: (gx, gy, gz, rho)
     uint32_t *neighbours;    // [n] particle-id order: taken candidates
@@ -311,10 +315,7 @@ struct BodyCounters {
     uint32_t pad;
 };
 struct BodyArgs {
-    const float4 *pos;       // the sorted stream: row j at pos[j stride] = (x, y, z, id)
-    int stride;
-    const int2 *cellRange;   // {start, end} per flattened cell (SPH_KEY_FLATTENED only)
-    int n;                   // rows of the stream, > 0
+    StreamView S;            // the rows and their candidates, n > 0 (the velocities are not read)
     float r2;                // link length squared, rounded once
     uint32_t *parent;        // [n] default path: the union-find forest over rows; parent[i] <= i always
     uint32_t *root;          // [n] default path: the root of every row, written by the flatten launch

@@ -28,7 +28,7 @@ int diag_run(sph_handle *h, const float4 *pos, const float4 *vel, int n, const S
     if (!h->diagDev) HIPCHK(h, h->diagDev.alloc(1));
     if (!h->diagHost) HIPCHK(h, h->diagHost.alloc(1));
     const bool plain = plain_path("SPH_DIAG_PLAIN");
-    int rc = outbound_fence(h, h->diagOut); // the previous call's copy still reads the block the clear is about to rewrite
+    int rc = outbound_fence(h, h->diag.out); // the previous call's copy still reads the block the clear is about to rewrite
     if (rc) return rc;
     DiagArgs A{};
     A.pos = pos, A.vel = vel, A.stride = 1;
@@ -36,18 +36,14 @@ int diag_run(sph_handle *h, const float4 *pos, const float4 *vel, int n, const S
     A.histField = o.hist_field;
     A.autoRange = o.hist_field >= 0 && o.value_lo == 0.f && o.value_hi == 0.f;
     A.lo = o.value_lo, A.hi = o.value_hi;
-    PairEvent *pe = nullptr;
-    if ((rc = pair_begin(h, &h->diagSeconds, &pe))) return rc;
-    sph_launch_diagnose(A, plain, h->diagDev, h->compute);
-    HIPCHK(h, hipEventRecord(pe->b, h->compute));
-    HIPCHK(h, hipGetLastError());
-    h->diagCount += 1;
-    h->diagValid = false; // (until the copy is queued: the pinned block still holds the previous result)
-    if ((rc = outbound_send(h, h->diagOut, {{h->diagHost.get(), h->diagDev.get(), sizeof(DiagBlock)}}))) return rc;
+    if ((rc = timed_launch(h, &h->diag.seconds, [&] { sph_launch_diagnose(A, plain, h->diagDev, h->compute); }))) return rc;
+    h->diag.calls += 1;
+    h->diag.valid = false; // (until the copy is queued: the pinned block still holds the previous result)
+    if ((rc = outbound_send(h, h->diag.out, {{h->diagHost.get(), h->diagDev.get(), sizeof(DiagBlock)}}))) return rc;
     h->diagN = n;
     h->diagOpt = o;
     h->diagAuto = A.autoRange != 0;
-    h->diagValid = true;
+    h->diag.valid = true;
     return SPH_OK;
 }
 
@@ -92,9 +88,9 @@ int sph_slab_diagnose(sph_handle *h, int buf, int i_begin, int i_end, const SphD
 
 int sph_diagnostics_host(sph_handle *h, SphDiagnosticsRaw *out) {
     if (!h || !out) return SPH_EINVAL;
-    if (!h->diagValid) return fail(h, SPH_ESTATE, "sph_diagnose must come first");
+    if (!h->diag.valid) return fail(h, SPH_ESTATE, "sph_diagnose must come first");
     SPH_ON_DEVICE(h);
-    HIPCHK(h, outbound_wait(h->diagOut));
+    HIPCHK(h, outbound_wait(h->diag.out));
     const DiagBlock &B = *h->diagHost;
     SphDiagnosticsRaw R{};
     R.struct_size = (int32_t)sizeof R;
@@ -125,7 +121,7 @@ int sph_diagnostics_host(sph_handle *h, SphDiagnosticsRaw *out) {
 
 int sph_get_diagnostics_time(sph_handle *h, double *seconds, int64_t *calls, int reset) {
     if (!h) return SPH_EINVAL;
-    return timed_total(h, &h->diagSeconds, &h->diagCount, seconds, calls, reset);
+    return timed_total(h, &h->diag.seconds, &h->diag.calls, seconds, calls, reset);
 }
 
 } // extern "C"

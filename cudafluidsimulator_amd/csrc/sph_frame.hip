@@ -13,10 +13,8 @@ namespace {
 int render_resize(sph_handle *h, int width, int height) {
     if (h->rp.width == width && h->rp.height == height && h->rDepth) return SPH_OK;
     // the old buffers may still be read by a queued compose / frame copy
-    HIPCHK(h, hipStreamSynchronize(h->compute));
-    HIPCHK(h, hipStreamSynchronize(h->copy));
-    h->frameOut.pending = false;
-    h->frameValid = false;
+    int rc = pass_quiesce(h, h->frame);
+    if (rc) return rc;
     h->rPacked.reset(); // (sized by the image: the next field frame allocates it again)
     h->fieldFrame = false;
     h->rp.width = h->rp.height = 0;
@@ -40,9 +38,9 @@ int render_resize(sph_handle *h, int width, int height) {
 }
 
 // Both renderers up to their launch: state and option checks (`rest(o)`: the entry point's own, a message or
-// null), the buffers, the wait for the previous frame's copy, the start of the timed section.
+// null), the buffers, the wait for the previous frame's copy.
 template <class Opt, class Rest>
-int frame_begin(sph_handle *h, const Opt *opt, const char *unset, Rest rest, bool field, Opt &o, bool &plain, PairEvent *&pe) {
+int frame_begin(sph_handle *h, const Opt *opt, const char *unset, Rest rest, bool field, Opt &o, bool &plain) {
     SPH_ON_DEVICE(h);
     if (h->external) return reject_slab_mode(h, ": multi-GPU frames are not rendered");
     if (!h->ready) return fail(h, SPH_ESTATE, "setup()/upload_state() must come first");
@@ -61,21 +59,18 @@ int frame_begin(sph_handle *h, const Opt *opt, const char *unset, Rest rest, boo
     }
     h->rp.radius = (pointSize - 1) / 2;
     plain = plain_path("SPH_RENDER_PLAIN");
-    if ((rc = outbound_fence(h, h->frameOut))) return rc; // the previous frame's copy still reads the device frame the compose is about to rewrite
-    return pair_begin(h, &h->renderSeconds, &pe);
+    return outbound_fence(h, h->frame.out); // the previous frame's copy still reads the device frame the compose is about to rewrite
 }
 
-// ... and after it: the end of the timed section, the counters, the frame (a field frame: and the range of its
-// colour scale) on its way to pinned memory
-int frame_finish(sph_handle *h, PairEvent *pe, bool field) {
-    HIPCHK(h, hipEventRecord(pe->b, h->compute));
-    HIPCHK(h, hipGetLastError());
-    h->renderFrames += 1;
-    h->frameValid = true;
+// ... and after it: the counters, the frame (a field frame: and the range of its colour scale) on its way to pinned
+// memory
+int frame_finish(sph_handle *h, bool field) {
+    h->frame.calls += 1;
+    h->frame.valid = true;
     h->fieldFrame = field;
     const OutboundCopy frame{h->frameHost.get(), h->rRgb.get(), (size_t)h->rp.width * h->rp.height * 3};
-    if (!field) return outbound_send(h, h->frameOut, {frame});
-    return outbound_send(h, h->frameOut, {frame, {h->rangeHost.get(), h->rRange.get(), 2 * sizeof(uint32_t)}});
+    if (!field) return outbound_send(h, h->frame.out, {frame});
+    return outbound_send(h, h->frame.out, {frame, {h->rangeHost.get(), h->rRange.get(), 2 * sizeof(uint32_t)}});
 }
 
 } // namespace
@@ -86,27 +81,26 @@ int sph_render_frame(sph_handle *h, const SphRenderOptions *opt) {
     if (!h) return SPH_EINVAL;
     SphRenderOptions o{};
     bool plain = false;
-    PairEvent *pe = nullptr;
     auto rest = [](const SphRenderOptions &o) -> const char * {
         return o.shade != SPH_SHADE_FLAT && o.shade != SPH_SHADE_COUNT ? "unknown shade" : nullptr;
     };
-    int rc = frame_begin(h, opt, "SphRenderOptions.struct_size is not set", rest, false, o, plain, pe);
+    int rc = frame_begin(h, opt, "SphRenderOptions.struct_size is not set", rest, false, o, plain);
     if (rc) return rc;
     h->rp.shade = o.shade;
     // The current state: after a step the rows the force sweep wrote, still in that step's cell-sorted order;
     // after setup / upload / load (and always with SPH_SWEEP_LINKED) in particle-id order.  A grid built
     // ahead for the next step only reads these rows.
-    sph_launch_render(h->rp, h->pos4[h->cur], h->n, plain, h->rDepth, h->rCount, h->rEdge, h->rRgb, h->compute);
-    return frame_finish(h, pe, false);
+    rc = timed_launch(h, &h->frame.seconds, [&] { sph_launch_render(h->rp, h->pos4[h->cur], h->n, plain, h->rDepth, h->rCount, h->rEdge, h->rRgb, h->compute); });
+    return rc ? rc : frame_finish(h, false);
 }
 
 const uint8_t *sph_frame_host(sph_handle *h, int *width, int *height) {
     if (!h) return nullptr;
-    if (!h->frameValid) {
+    if (!h->frame.valid) {
         h->err = "sph_render_frame must come first";
         return nullptr;
     }
-    if (outbound_wait(h->frameOut) != hipSuccess) {
+    if (outbound_wait(h->frame.out) != hipSuccess) {
         h->err = "frame copy failed";
         return nullptr;
     }
@@ -118,7 +112,7 @@ const uint8_t *sph_frame_host(sph_handle *h, int *width, int *height) {
 int sph_download_frame_buffers(sph_handle *h, uint32_t *depth_bits, uint32_t *count, uint32_t *edge_depth_bits) {
     if (!h) return SPH_EINVAL;
     SPH_ON_DEVICE(h);
-    if (!h->frameValid) return fail(h, SPH_ESTATE, "sph_render_frame must come first");
+    if (!h->frame.valid) return fail(h, SPH_ESTATE, "sph_render_frame must come first");
     HIPCHK(h, hipStreamSynchronize(h->compute));
     const size_t bytes = (size_t)h->rp.width * h->rp.height * sizeof(uint32_t);
     if (depth_bits) HIPCHK(h, hipMemcpy(depth_bits, h->rDepth, bytes, hipMemcpyDeviceToHost));
@@ -129,32 +123,33 @@ int sph_download_frame_buffers(sph_handle *h, uint32_t *depth_bits, uint32_t *co
 
 int sph_get_render_time(sph_handle *h, double *seconds, int64_t *frames, int reset) {
     if (!h) return SPH_EINVAL;
-    return timed_total(h, &h->renderSeconds, &h->renderFrames, seconds, frames, reset);
+    return timed_total(h, &h->frame.seconds, &h->frame.calls, seconds, frames, reset);
 }
 
 int sph_render_field(sph_handle *h, const SphFieldFrameOptions *opt) {
     if (!h) return SPH_EINVAL;
     SphFieldFrameOptions o{};
     bool plain = false;
-    PairEvent *pe = nullptr;
     auto rest = [](const SphFieldFrameOptions &o) -> const char * {
         if (bad_field(o.field)) return "unknown field";
         if (!std::isfinite(o.value_lo) || !std::isfinite(o.value_hi)) return "value_lo / value_hi must be finite";
         return o.value_hi < o.value_lo ? "value_hi < value_lo" : nullptr;
     };
-    int rc = frame_begin(h, opt, "SphFieldFrameOptions.struct_size is not set", rest, true, o, plain, pe);
+    int rc = frame_begin(h, opt, "SphFieldFrameOptions.struct_size is not set", rest, true, o, plain);
     if (rc) return rc;
     const bool autoRange = o.value_lo == 0.f && o.value_hi == 0.f;
     // pos4[cur] / vel4[cur]: the rows sph_render_frame draws and the rows sph_download_state reads
-    sph_launch_render_field(h->rp, h->pos4[h->cur], h->vel4[h->cur], h->n, plain, o.field, autoRange, o.value_lo, o.value_hi,
-                            h->rPacked, h->rDepth, h->rCount, h->rEdge, h->rRange, h->rRgb, h->compute);
-    return frame_finish(h, pe, true);
+    rc = timed_launch(h, &h->frame.seconds, [&] {
+        sph_launch_render_field(h->rp, h->pos4[h->cur], h->vel4[h->cur], h->n, plain, o.field, autoRange, o.value_lo, o.value_hi,
+                                h->rPacked, h->rDepth, h->rCount, h->rEdge, h->rRange, h->rRgb, h->compute);
+    });
+    return rc ? rc : frame_finish(h, true);
 }
 
 int sph_download_field_buffer(sph_handle *h, uint32_t *value_bits) {
     if (!h || !value_bits) return SPH_EINVAL;
     SPH_ON_DEVICE(h);
-    if (!h->frameValid || !h->fieldFrame) return fail(h, SPH_ESTATE, "the last render was not a field frame (sph_render_field)");
+    if (!h->frame.valid || !h->fieldFrame) return fail(h, SPH_ESTATE, "the last render was not a field frame (sph_render_field)");
     HIPCHK(h, hipStreamSynchronize(h->compute));
     const size_t npix = (size_t)h->rp.width * h->rp.height;
     std::vector<unsigned long long> packed(npix);
@@ -166,8 +161,8 @@ int sph_download_field_buffer(sph_handle *h, uint32_t *value_bits) {
 int sph_field_range(sph_handle *h, float *lo, float *hi) {
     if (!h) return SPH_EINVAL;
     SPH_ON_DEVICE(h);
-    if (!h->frameValid || !h->fieldFrame) return fail(h, SPH_ESTATE, "the last render was not a field frame (sph_render_field)");
-    HIPCHK(h, outbound_wait(h->frameOut));
+    if (!h->frame.valid || !h->fieldFrame) return fail(h, SPH_ESTATE, "the last render was not a field frame (sph_render_field)");
+    HIPCHK(h, outbound_wait(h->frame.out));
     if (lo) memcpy(lo, &h->rangeHost[0], sizeof(float));
     if (hi) memcpy(hi, &h->rangeHost[1], sizeof(float));
     return SPH_OK;

@@ -1,6 +1,5 @@
-// The handle behind include/sph_c_api.h and the few helpers its host translation units share (sph_api.hip,
-// sph_step.hip, sph_readback.hip, sph_slab.hip, sph_snapshot.hip, sph_frame.hip, sph_sample.hip, sph_surface.hip, sph_diag.hip, sph_tracers.hip, sph_derived.hip,
-// sph_bodies.hip).
+// The handle behind include/sph_c_api.h and the few helpers its host translation units share (the sph_*.hip units of
+// the Makefile's SRCS).
 // Host code only.
 // Ownership: every device buffer, pinned block and event below is a DeviceBuf / PinnedBuf / Event (sph_owned.h) and goes
 // with the handle; a raw pointer member is a view of one of them (or of the caller's memory) and says so.
@@ -15,6 +14,7 @@
 #include <cstring>
 #include <initializer_list>
 #include <string>
+#include <type_traits>
 
 namespace sph_host {
 
@@ -90,6 +90,25 @@ struct OutboundCopy {
     void *dst;
     const void *src;
     size_t bytes;
+};
+
+// What every pass that queues work and hands back a result keeps: the result on its way out, whether the pinned
+// buffers hold (or will hold) one, and the GPU time and number of its calls (timed_total reads them).
+struct Pass {
+    Outbound out;
+    bool valid = false;
+    double seconds = 0; // from HIP events (PairEvent ring)
+    long long calls = 0;
+};
+
+// A few 64-bit counters a pass's kernels add to, on the device, with the pinned block they are read through.
+struct CounterBlock {
+    explicit CounterBlock(int words) : count(words) {}
+    DeviceBuf<unsigned long long> dev;
+    PinnedBuf<unsigned long long> host;
+    const int count;
+    int ensure(sph_handle *h);          // allocated and cleared by the first call that needs them
+    int read(sph_handle *h, int reset); // host[0, count) = the counters now (never allocated: nothing, host stays null); reset: cleared after
 };
 
 struct StepEvents {
@@ -211,10 +230,8 @@ struct sph_handle {
     RenderParams rp{};               // size / point radius / shade of the last render (width 0: none yet)
     sph_host::DeviceBuf<uint32_t> rDepth, rCount, rEdge, rRgb;
     sph_host::PinnedBuf<uint8_t> frameHost;
-    sph_host::Outbound frameOut;     // the frame (a field frame: and its range) on its way to frameHost / rangeHost
-    bool frameValid = false;         // the buffers hold a rendered frame of the size in rp
-    double renderSeconds = 0;        // clear + splat + compose, from HIP events (PairEvent ring)
-    long long renderFrames = 0;
+    sph_host::Pass frame;            // out: the frame (a field frame: and its range) on its way to frameHost / rangeHost; valid:
+                                     // the buffers hold a rendered frame of the size in rp; seconds: clear + splat + compose
     // The field frame (sph_render_field) adds the packed (depth bits << 32 | value bits) minimum per pixel and
     // the range of the colour scale: two words on the device, copied to pinned memory with the frame.
     sph_host::DeviceBuf<unsigned long long> rPacked;
@@ -229,10 +246,7 @@ struct sph_handle {
     sph_host::PinnedBuf<float> sampleHost;
     size_t sampleCap = 0;            // floats either buffer holds
     int sampleDim[3] = {0, 0, 0};    // nx, ny, nz of the last sample
-    sph_host::Outbound sampleOut;    // the values on their way to sampleHost
-    bool sampleValid = false;
-    double sampleSeconds = 0;        // the sampling kernel, from HIP events (PairEvent ring)
-    long long sampleCount = 0;
+    sph_host::Pass sample;           // out: the values on their way to sampleHost; seconds: the sampling kernel
     long long sampleTileCalls = 0, samplePlainCalls = 0; // which kernel ran (SPH_STEP_TRACE=1: printed by sph_destroy)
 
     // ---- sph_surface.hip ----
@@ -253,10 +267,8 @@ struct sph_handle {
     sph_host::PinnedBuf<uint32_t> surfTrisHost;
     size_t surfVertCap = 0, surfTriCap = 0; // vertices / triangles either buffer holds
     long long surfVerts = 0, surfTris = 0;  // of the last extraction
-    sph_host::Outbound surfOut;      // the mesh on its way to surfVertsHost / surfTrisHost
-    bool surfValid = false;
-    double surfSampleSeconds = 0, surfExtractSeconds = 0; // the sampling kernel; count + scan + emit (PairEvent ring)
-    long long surfCount = 0;
+    sph_host::Pass surf;             // out: the mesh on its way to surfVertsHost / surfTrisHost; seconds: count + scan + emit
+    double surfSampleSeconds = 0;    // ... and the sampling kernel
     long long surfWaveCalls = 0, surfPlainCalls = 0; // which path ran (SPH_STEP_TRACE=1: printed by sph_destroy)
 
     // ---- sph_diag.hip ----
@@ -264,13 +276,10 @@ struct sph_handle {
     // first sph_diagnose / sph_slab_diagnose.
     sph_host::DeviceBuf<DiagBlock> diagDev;
     sph_host::PinnedBuf<DiagBlock> diagHost;
-    sph_host::Outbound diagOut;      // the block on its way to diagHost
-    bool diagValid = false;
+    sph_host::Pass diag;             // out: the block on its way to diagHost; seconds: clear + reduce + histogram
     int diagN = 0;                   // rows of the last call
     SphDiagnosticsOptions diagOpt{}; // ... its options
     bool diagAuto = false;           // ... and whether its histogram took the reduced range
-    double diagSeconds = 0;          // clear + reduce + histogram, from HIP events (PairEvent ring)
-    long long diagCount = 0;
 
     // ---- sph_tracers.hip ----
     // Passive tracers (tracers.hip): (x, y, z, den) and (ux, uy, uz, 0) per tracer in the caller's order, on the
@@ -282,11 +291,9 @@ struct sph_handle {
     int tracerCount = 0;             // m of the last sph_tracers_set
     sph_host::DeviceBuf<uint32_t> tracerKeys[2], tracerVals[2], tracerBlockHist, tracerDigitTotal;
     SortWorkspace tracerWs{};        // views of the six above (capacity 0: not allocated yet)
-    sph_host::DeviceBuf<unsigned long long> tracerCounters; // waves_shared, waves_direct, groups
-    sph_host::PinnedBuf<unsigned long long> tracerCountersHost;
-    sph_host::Outbound tracerOut;    // the results on their way to tracerPosDenHost / tracerVelHost
-    double tracerSeconds = 0;        // key + sort + walk, from HIP events (PairEvent ring)
-    long long tracerCalls = 0;
+    sph_host::CounterBlock tracerCounters{kTracerCounters}; // waves_shared, waves_direct, groups
+    sph_host::Pass tracer;           // out: the results on their way to tracerPosDenHost / tracerVelHost (valid: unused, the
+                                     // tracers are the caller's); seconds: key + sort + walk
 
     // ---- sph_derived.hip ----
     // Derived per-particle fields (derived.hip): (wx, wy, wz, div), (gx, gy, gz, rho) and the neighbour count per
@@ -298,12 +305,8 @@ struct sph_handle {
     sph_host::PinnedBuf<uint32_t> deriveNeighboursHost;
     size_t deriveCap = 0;            // particles each of the six buffers holds
     int deriveN = 0;                 // rows of the last sph_derive
-    bool deriveValid = false;        // a derive has been queued: the pinned buffers hold (or will hold) its results
-    sph_host::DeviceBuf<unsigned long long> deriveCounters; // runs_staged, runs_direct
-    sph_host::PinnedBuf<unsigned long long> deriveCountersHost;
-    sph_host::Outbound deriveOut;    // the results on their way to the three pinned buffers
-    double deriveSeconds = 0;        // the sweep, from HIP events (PairEvent ring)
-    long long deriveCalls = 0;
+    sph_host::CounterBlock deriveCounters{kDeriveCounters}; // runs_staged, runs_direct
+    sph_host::Pass derive;           // out: the results on their way to the three pinned buffers; seconds: the sweep
 
     // ---- sph_bodies.hip ----
     // Bodies (bodies.hip): the working arrays over rows and particle ids, the labels in id order and the table on the
@@ -317,10 +320,7 @@ struct sph_handle {
     sph_host::Event bodyCounted;     // the counter block has landed
     size_t bodyCap = 0, bodyTableCap = 0; // particles / table rows the buffers hold
     int bodyN = 0, bodyCount = 0;    // rows and bodies of the last sph_label_bodies
-    bool bodyValid = false;          // a labelling has been queued: the pinned buffers hold (or will hold) its results
-    sph_host::Outbound bodyOut;      // the results on their way to the pinned buffers
-    double bodySeconds = 0;          // every kernel of the call, from HIP events (PairEvent ring)
-    long long bodyCalls = 0;
+    sph_host::Pass body;             // out: the results on their way to the pinned buffers; seconds: every kernel of the call
     unsigned long long bodyLinks = 0, bodyUnions = 0, bodyRounds = 0, bodyGaveUp = 0; // sums over calls
 };
 
@@ -366,10 +366,42 @@ int timed_total(sph_handle *h, double *seconds, long long *count, double *second
 int outbound_fence(sph_handle *h, Outbound &o);
 int outbound_send(sph_handle *h, Outbound &o, std::initializer_list<OutboundCopy> copies);
 hipError_t outbound_wait(const Outbound &o);
+// What the passes over the grid's sorted stream share (the field sample, the surface mesh, the tracers, the derived
+// fields, the bodies).  analysis_begin: the state checks, in this order -- a slab handle (`slab_hint` ends that message),
+// no state yet, SPH_SWEEP_LINKED, SPH_KEY_MORTON, a phase-split step still open; `what` names the pass in the messages.
+// analysis_grid: a grid of the state the handle holds NOW.  Phase 1: it exists (sph_phase_grid, or built ahead by a
+// timed step).  Phase 0: the table of the last step is the pre-integration one; the next step's grid is built here,
+// ahead, and that step consumes it.  Nothing to build without particles.  A pass checks its own options between the two.
+int analysis_begin(sph_handle *h, const char *what, const char *slab_hint);
+int analysis_grid(sph_handle *h);
+// ... and the stream of that grid, as the passes' kernels read it (all null, n = 0, without particles)
+StreamView sorted_stream(const sph_handle *h);
+// nothing queued reads or writes the pass's buffers any more: they may be reallocated; the pass holds no result
+int pass_quiesce(sph_handle *h, Pass &p);
+// a few words the call itself has to wait for (a total that sizes the next launch): copied behind what `compute` holds
+// now, waited for through `landed`
+int fetch_small(sph_handle *h, void *dst, const void *src, size_t bytes, Event &landed);
 int begin_step_events(sph_handle *h);
 int build_grid_ahead(sph_handle *h);
 int resolve_events(sph_handle *h, StepEvents &se);
 void drop_grid_ahead(sph_handle *h);
+// a timed section around launch() (void, or an int that ends the call when it is not SPH_OK): its GPU time is added
+// to *seconds when resolved; launch errors are reported
+template <class F>
+int timed_launch(sph_handle *h, double *seconds, F &&launch) {
+    PairEvent *pe = nullptr;
+    int rc = pair_begin(h, seconds, &pe);
+    if (rc) return rc;
+    if constexpr (std::is_void_v<decltype(launch())>) launch();
+    else if ((rc = launch())) return rc;
+    HIPCHK(h, hipEventRecord(pe->b, h->compute));
+    HIPCHK(h, hipGetLastError());
+    return SPH_OK;
+}
+// sph_sample.hip: what the field sample and the surface's sample share -- the lattice's checks (a message or null;
+// the smallest dimension allowed differs) and its kernel arguments over the stream of the current grid
+const char *bad_lattice(int nx, int ny, int nz, const float (&origin)[3], const float (&spacing)[3], int minDim);
+SampleArgs lattice_args(const sph_handle *h, int nx, int ny, int nz, const float (&origin)[3], const float (&spacing)[3], int field);
 // sph_readback.hip
 void sdma_init(sph_handle *h);
 int sdma_wait(sph_handle *h, int slot);

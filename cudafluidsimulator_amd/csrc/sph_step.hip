@@ -94,6 +94,23 @@ SweepArgs make_sweep_args(sph_handle *h) {
     return A;
 }
 
+StreamView sorted_stream(const sph_handle *h) {
+    StreamView S{};
+    S.n = h->n;
+    if (h->n <= 0) return S;
+    S.cellRange = h->cellRange;
+    if (h->opt.sweep == SPH_SWEEP_LIST && h->pv8) { // the gather left no sorted vel4 in this mode
+        S.pos = h->pv8;
+        S.vel = h->pv8 + 1;
+        S.stride = 2;
+    } else {
+        S.pos = h->pos4[h->sorted];
+        S.vel = h->vel4[h->sorted];
+        S.stride = 1;
+    }
+    return S;
+}
+
 // what rides on the gather launch of a grid build: the hit-stream cursors are cleared there
 GatherExtras gather_extras(sph_handle *h) {
     GatherExtras X;
@@ -229,6 +246,50 @@ int outbound_send(sph_handle *h, Outbound &o, std::initializer_list<OutboundCopy
 }
 
 hipError_t outbound_wait(const Outbound &o) { return o.pending ? hipEventSynchronize(o.copied) : hipSuccess; }
+
+int analysis_begin(sph_handle *h, const char *what, const char *slab_hint) {
+    if (h->external) return reject_slab_mode(h, slab_hint);
+    if (!h->ready) return fail(h, SPH_ESTATE, "setup()/upload_state() must come first");
+    const std::string w = what;
+    if (h->opt.sweep == SPH_SWEEP_LINKED) return fail(h, SPH_ESTATE, w + " needs a cell table: not available with SPH_SWEEP_LINKED");
+    if (h->P.morton) return fail(h, SPH_ESTATE, w + " walks rows of cells as runs of the stream: not available with SPH_KEY_MORTON");
+    if (h->phase != 0 && h->phase != 1) return fail(h, SPH_ESTATE, "a step split into phases is still open");
+    return SPH_OK;
+}
+
+int analysis_grid(sph_handle *h) { return h->phase == 0 && h->n > 0 ? build_grid_ahead(h) : SPH_OK; }
+
+int pass_quiesce(sph_handle *h, Pass &p) {
+    HIPCHK(h, hipStreamSynchronize(h->compute));
+    HIPCHK(h, hipStreamSynchronize(h->copy));
+    p.out.pending = false;
+    p.valid = false;
+    return SPH_OK;
+}
+
+int fetch_small(sph_handle *h, void *dst, const void *src, size_t bytes, Event &landed) {
+    HIPCHK(h, landed.create(hipEventDisableTiming));
+    HIPCHK(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->compute));
+    HIPCHK(h, hipEventRecord(landed, h->compute));
+    HIPCHK(h, hipEventSynchronize(landed));
+    return SPH_OK;
+}
+
+int CounterBlock::ensure(sph_handle *h) {
+    if (dev) return SPH_OK;
+    HIPCHK(h, dev.alloc(count));
+    HIPCHK(h, host.alloc(count));
+    HIPCHK(h, hipMemsetAsync(dev, 0, count * sizeof(unsigned long long), h->compute));
+    return SPH_OK;
+}
+
+int CounterBlock::read(sph_handle *h, int reset) {
+    if (!dev) return SPH_OK;
+    HIPCHK(h, hipMemcpyAsync(host, dev, count * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->compute));
+    if (reset) HIPCHK(h, hipMemsetAsync(dev, 0, count * sizeof(unsigned long long), h->compute));
+    HIPCHK(h, hipStreamSynchronize(h->compute));
+    return SPH_OK;
+}
 
 // the density sweep of the single domain and of a slab: counters on request, clean hit-stream cursors
 int launch_density(sph_handle *h, SweepArgs &A, hipStream_t stream) {

@@ -7,18 +7,9 @@ using namespace sph_host;
 
 namespace {
 
-// nothing queued reads or writes the surface's buffers any more
-int surface_quiesce(sph_handle *h) {
-    HIPCHK(h, hipStreamSynchronize(h->compute));
-    HIPCHK(h, hipStreamSynchronize(h->copy));
-    h->surfOut.pending = false;
-    h->surfValid = false;
-    return SPH_OK;
-}
-
 int surface_reserve_lattice(sph_handle *h, size_t points, size_t blocks) {
     if (points > h->surfPointCap || blocks > h->surfBlockCap || !h->surfTotalsDev) {
-        int rc = surface_quiesce(h);
+        int rc = pass_quiesce(h, h->surf);
         if (rc) return rc;
     }
     if (points > h->surfPointCap) {
@@ -37,7 +28,6 @@ int surface_reserve_lattice(sph_handle *h, size_t points, size_t blocks) {
     if (!h->surfTotalsDev) {
         HIPCHK(h, h->surfTotalsDev.alloc(2));
         HIPCHK(h, h->surfTotalsHost.alloc(2));
-        HIPCHK(h, h->surfCounted.create(hipEventDisableTiming));
     }
     return SPH_OK;
 }
@@ -61,18 +51,6 @@ int surface_reserve_mesh(sph_handle *h, size_t verts, size_t tris) {
     return SPH_OK;
 }
 
-const char *bad_surface(const SphSurfaceOptions &o) {
-    for (int d : {o.nx, o.ny, o.nz})
-        if (d < 2 || d > 4096) return "lattice dimensions must be 2..4096";
-    if ((long long)o.nx * o.ny * o.nz > (1ll << 24)) return "lattice holds more than 1 << 24 points";
-    for (float v : o.origin)
-        if (!std::isfinite(v)) return "origin must be finite";
-    for (float s : o.spacing)
-        if (!std::isfinite(s) || !(s > 0.f)) return "spacing must be finite and > 0";
-    if (!std::isfinite(o.iso) || !(o.iso > 0.f)) return "iso must be finite and > 0";
-    return nullptr;
-}
-
 } // namespace
 
 extern "C" {
@@ -80,17 +58,14 @@ extern "C" {
 int sph_extract_surface(sph_handle *h, const SphSurfaceOptions *opt) {
     if (!h) return SPH_EINVAL;
     SPH_ON_DEVICE(h);
-    if (h->external) return reject_slab_mode(h, ": multi-GPU runs are not meshed");
-    if (!h->ready) return fail(h, SPH_ESTATE, "setup()/upload_state() must come first");
-    if (h->opt.sweep == SPH_SWEEP_LINKED) return fail(h, SPH_ESTATE, "the surface mesh needs a cell table: not available with SPH_SWEEP_LINKED");
-    if (h->P.morton) return fail(h, SPH_ESTATE, "the surface mesh walks rows of cells as runs of the stream: not available with SPH_KEY_MORTON");
-    if (h->phase != 0 && h->phase != 1) return fail(h, SPH_ESTATE, "a step split into phases is still open");
+    int rc = analysis_begin(h, "the surface mesh", ": multi-GPU runs are not meshed");
+    if (rc) return rc;
     const char *unset = "SphSurfaceOptions.struct_size is not set";
     if (!opt) return fail(h, SPH_EINVAL, unset); // (no defaults: a lattice and a level have to be given)
     SphSurfaceOptions o{};
-    int rc = copy_options(h, opt, o, unset);
-    if (rc) return rc;
-    if (const char *bad = bad_surface(o)) return fail(h, SPH_EINVAL, bad);
+    if ((rc = copy_options(h, opt, o, unset))) return rc;
+    if (const char *bad = bad_lattice(o.nx, o.ny, o.nz, o.origin, o.spacing, 2)) return fail(h, SPH_EINVAL, bad);
+    if (!std::isfinite(o.iso) || !(o.iso > 0.f)) return fail(h, SPH_EINVAL, "iso must be finite and > 0");
     const bool plain = plain_path("SPH_SURFACE_PLAIN");
     SurfaceArgs S{};
     S.nx = o.nx, S.ny = o.ny, S.nz = o.nz;
@@ -99,68 +74,38 @@ int sph_extract_surface(sph_handle *h, const SphSurfaceOptions *opt) {
     S.iso = o.iso;
     const size_t points = (size_t)o.nx * o.ny * o.nz;
     if ((rc = surface_reserve_lattice(h, points, (size_t)sph_surface_blocks(S)))) return rc;
-    // the grid of the state the handle holds NOW, as sph_sample_field finds or builds it
-    if (h->phase == 0 && h->n > 0 && (rc = build_grid_ahead(h))) return rc;
-    if ((rc = outbound_fence(h, h->surfOut))) return rc; // the previous mesh's copy still reads the device buffers
-    h->surfValid = false;
+    if ((rc = analysis_grid(h))) return rc;
+    if ((rc = outbound_fence(h, h->surf.out))) return rc; // the previous mesh's copy still reads the device buffers
+    h->surf.valid = false;
 
-    SampleArgs A{};
-    A.nx = o.nx, A.ny = o.ny, A.nz = o.nz;
-    A.ox = S.ox, A.oy = S.oy, A.oz = S.oz;
-    A.sx = S.sx, A.sy = S.sy, A.sz = S.sz;
-    A.field = SPH_FIELD_DENSITY;
-    A.n = h->n;
-    if (h->n > 0) {
-        A.cellRange = h->cellRange;
-        if (h->opt.sweep == SPH_SWEEP_LIST && h->pv8) { // the gather left no sorted vel4 in this mode
-            A.pos = h->pv8;
-            A.vel = h->pv8 + 1;
-            A.stride = 2;
-        } else {
-            A.pos = h->pos4[h->sorted];
-            A.vel = h->vel4[h->sorted];
-            A.stride = 1;
-        }
-    }
-    PairEvent *pe = nullptr;
-    if ((rc = pair_begin(h, &h->surfSampleSeconds, &pe))) return rc;
-    sph_launch_sample(h->P, A, plain, h->surfField, h->compute);
-    HIPCHK(h, hipEventRecord(pe->b, h->compute));
-    HIPCHK(h, hipGetLastError());
-
+    const SampleArgs A = lattice_args(h, o.nx, o.ny, o.nz, o.origin, o.spacing, SPH_FIELD_DENSITY);
+    if ((rc = timed_launch(h, &h->surfSampleSeconds, [&] { sph_launch_sample(h->P, A, plain, h->surfField, h->compute); }))) return rc;
     SurfaceBuffers B{};
     B.field = h->surfField, B.bits = h->surfBits, B.local = h->surfLocal;
     B.blockSum = h->surfBlockSum, B.blockOff = h->surfBlockOff, B.totals = h->surfTotalsDev;
-    if ((rc = pair_begin(h, &h->surfExtractSeconds, &pe))) return rc;
-    sph_launch_surface_count(S, plain, B, h->compute);
-    HIPCHK(h, hipEventRecord(pe->b, h->compute));
-    HIPCHK(h, hipGetLastError());
+    if ((rc = timed_launch(h, &h->surf.seconds, [&] { sph_launch_surface_count(S, plain, B, h->compute); }))) return rc;
     // the one wait of this call: the two totals size the mesh
-    HIPCHK(h, hipMemcpyAsync(h->surfTotalsHost.get(), h->surfTotalsDev.get(), 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->compute));
-    HIPCHK(h, hipEventRecord(h->surfCounted, h->compute));
-    HIPCHK(h, hipEventSynchronize(h->surfCounted));
+    if ((rc = fetch_small(h, h->surfTotalsHost.get(), h->surfTotalsDev.get(), 2 * sizeof(unsigned long long), h->surfCounted))) return rc;
     const size_t verts = (size_t)h->surfTotalsHost[0], tris = (size_t)h->surfTotalsHost[1];
-    h->surfCount += 1;
+    h->surf.calls += 1;
     (plain ? h->surfPlainCalls : h->surfWaveCalls) += 1;
     if (verts > 0 || tris > 0) {
         if ((rc = surface_reserve_mesh(h, verts, tris))) return rc;
-        if ((rc = pair_begin(h, &h->surfExtractSeconds, &pe))) return rc;
-        sph_launch_surface_emit(S, plain, B, h->surfVertsDev, h->surfTrisDev, h->compute);
-        HIPCHK(h, hipEventRecord(pe->b, h->compute));
-        HIPCHK(h, hipGetLastError());
-        if ((rc = outbound_send(h, h->surfOut, {{h->surfVertsHost.get(), h->surfVertsDev.get(), verts * 3 * sizeof(float)},
-                                                {h->surfTrisHost.get(), h->surfTrisDev.get(), tris * 3 * sizeof(uint32_t)}})))
+        if ((rc = timed_launch(h, &h->surf.seconds, [&] { sph_launch_surface_emit(S, plain, B, h->surfVertsDev, h->surfTrisDev, h->compute); })))
+            return rc;
+        if ((rc = outbound_send(h, h->surf.out, {{h->surfVertsHost.get(), h->surfVertsDev.get(), verts * 3 * sizeof(float)},
+                                                 {h->surfTrisHost.get(), h->surfTrisDev.get(), tris * 3 * sizeof(uint32_t)}})))
             return rc;
     }
     h->surfVerts = (long long)verts, h->surfTris = (long long)tris;
-    h->surfValid = true;
+    h->surf.valid = true;
     return SPH_OK;
 }
 
 int sph_surface_host(sph_handle *h, const float **vertices_xyz, int64_t *num_vertices, const uint32_t **triangles, int64_t *num_triangles) {
     if (!h) return SPH_EINVAL;
-    if (!h->surfValid) return fail(h, SPH_ESTATE, "sph_extract_surface must come first");
-    if (outbound_wait(h->surfOut) != hipSuccess) return fail(h, SPH_EHIP, "surface copy failed");
+    if (!h->surf.valid) return fail(h, SPH_ESTATE, "sph_extract_surface must come first");
+    if (outbound_wait(h->surf.out) != hipSuccess) return fail(h, SPH_EHIP, "surface copy failed");
     if (vertices_xyz) *vertices_xyz = h->surfVerts ? h->surfVertsHost.get() : nullptr;
     if (num_vertices) *num_vertices = h->surfVerts;
     if (triangles) *triangles = h->surfTris ? h->surfTrisHost.get() : nullptr;
@@ -173,7 +118,7 @@ int sph_get_surface_time(sph_handle *h, double *sample_seconds, double *extract_
     long long unused = 0;
     int rc = timed_total(h, &h->surfSampleSeconds, &unused, sample_seconds, nullptr, reset);
     if (rc) return rc;
-    return timed_total(h, &h->surfExtractSeconds, &h->surfCount, extract_seconds, calls, reset);
+    return timed_total(h, &h->surf.seconds, &h->surf.calls, extract_seconds, calls, reset);
 }
 
 } // extern "C"

@@ -43,14 +43,6 @@ int tracer_sort_reserve(sph_handle *h) {
     return SPH_OK;
 }
 
-int tracer_counters(sph_handle *h) {
-    if (h->tracerCounters) return SPH_OK;
-    HIPCHK(h, h->tracerCounters.alloc(kTracerCounters));
-    HIPCHK(h, h->tracerCountersHost.alloc(kTracerCounters));
-    HIPCHK(h, hipMemsetAsync(h->tracerCounters, 0, kTracerCounters * sizeof(unsigned long long), h->compute));
-    return SPH_OK;
-}
-
 } // namespace
 
 extern "C" {
@@ -62,12 +54,10 @@ int sph_tracers_set(sph_handle *h, const float *pos_xyz, int m) {
     if (m < 0 || m > kMaxTracers) return fail(h, SPH_EINVAL, "the number of tracers must be 0..1 << 24");
     if (!pos_xyz && m > 0) return fail(h, SPH_EINVAL, "null argument");
     // the last advect may still write the device buffers, its copy the pinned ones
-    HIPCHK(h, hipStreamSynchronize(h->compute));
-    HIPCHK(h, hipStreamSynchronize(h->copy));
-    h->tracerOut.pending = false;
-    h->tracerCount = 0;
-    int rc = tracer_reserve(h, (size_t)m);
+    int rc = pass_quiesce(h, h->tracer);
     if (rc) return rc;
+    h->tracerCount = 0;
+    if ((rc = tracer_reserve(h, (size_t)m))) return rc;
     if (m > 0) {
         float4 *pd = h->tracerPosDenHost, *u = h->tracerVelHost;
         for (int i = 0; i < m; ++i) {
@@ -86,59 +76,38 @@ int sph_tracers_set(sph_handle *h, const float *pos_xyz, int m) {
 int sph_tracers_advect(sph_handle *h, float dt) {
     if (!h) return SPH_EINVAL;
     SPH_ON_DEVICE(h);
-    if (h->external) return reject_slab_mode(h, ": multi-GPU runs carry no tracers");
-    if (!h->ready) return fail(h, SPH_ESTATE, "setup()/upload_state() must come first");
-    if (h->opt.sweep == SPH_SWEEP_LINKED) return fail(h, SPH_ESTATE, "tracers need a cell table: not available with SPH_SWEEP_LINKED");
-    if (h->P.morton) return fail(h, SPH_ESTATE, "tracers walk rows of cells as runs of the stream: not available with SPH_KEY_MORTON");
-    if (h->phase != 0 && h->phase != 1) return fail(h, SPH_ESTATE, "a step split into phases is still open");
+    int rc = analysis_begin(h, "the tracers' advect", ": multi-GPU runs carry no tracers");
+    if (rc) return rc;
     if (!std::isfinite(dt)) return fail(h, SPH_EINVAL, "dt must be finite");
     const int m = h->tracerCount;
     if (m == 0) return SPH_OK;
-    int rc;
-    // a grid of the state the handle holds NOW, found or built ahead exactly as sph_sample_field does
-    if (h->phase == 0 && h->n > 0 && (rc = build_grid_ahead(h))) return rc;
+    if ((rc = analysis_grid(h))) return rc;
     const bool plain = plain_path("SPH_TRACER_PLAIN");
     if (!plain && h->n > 0) {
         if ((rc = tracer_sort_reserve(h))) return rc;
-        if ((rc = tracer_counters(h))) return rc;
+        if ((rc = h->tracerCounters.ensure(h))) return rc;
     }
-    if ((rc = outbound_fence(h, h->tracerOut))) return rc; // the previous advect's copy still reads the device buffers
+    if ((rc = outbound_fence(h, h->tracer.out))) return rc; // the previous advect's copy still reads the device buffers
     TracerArgs A{};
-    A.n = h->n;
+    A.S = sorted_stream(h);
     A.m = m;
     A.dt = dt;
     A.posDen = h->tracerPosDen;
     A.velOut = h->tracerVel;
-    A.counters = h->tracerCounters;
-    if (h->n > 0) {
-        A.cellRange = h->cellRange;
-        if (h->opt.sweep == SPH_SWEEP_LIST && h->pv8) { // the gather left no sorted vel4 in this mode
-            A.pos = h->pv8;
-            A.vel = h->pv8 + 1;
-            A.stride = 2;
-        } else {
-            A.pos = h->pos4[h->sorted];
-            A.vel = h->vel4[h->sorted];
-            A.stride = 1;
-        }
-    }
+    A.counters = h->tracerCounters.dev;
     // keys up to numCells itself (a tracer outside the grid)
     int bits = 1;
     while ((1ll << bits) <= (long long)h->P.numCells) ++bits;
-    PairEvent *pe = nullptr;
-    if ((rc = pair_begin(h, &h->tracerSeconds, &pe))) return rc;
-    sph_launch_tracers(h->P, A, plain, h->tracerWs, bits, h->compute);
-    HIPCHK(h, hipEventRecord(pe->b, h->compute));
-    HIPCHK(h, hipGetLastError());
-    h->tracerCalls += 1;
-    return outbound_send(h, h->tracerOut, {{h->tracerPosDenHost.get(), h->tracerPosDen.get(), (size_t)m * sizeof(float4)},
+    if ((rc = timed_launch(h, &h->tracer.seconds, [&] { sph_launch_tracers(h->P, A, plain, h->tracerWs, bits, h->compute); }))) return rc;
+    h->tracer.calls += 1;
+    return outbound_send(h, h->tracer.out, {{h->tracerPosDenHost.get(), h->tracerPosDen.get(), (size_t)m * sizeof(float4)},
                                            {h->tracerVelHost.get(), h->tracerVel.get(), (size_t)m * sizeof(float4)}});
 }
 
 int sph_tracers_host(sph_handle *h, const float **pos_den, const float **vel, int *m) {
     if (!h) return SPH_EINVAL;
     SPH_ON_DEVICE(h);
-    HIPCHK(h, outbound_wait(h->tracerOut));
+    HIPCHK(h, outbound_wait(h->tracer.out));
     const bool any = h->tracerCount > 0;
     if (pos_den) *pos_den = any ? &h->tracerPosDenHost.get()->x : nullptr;
     if (vel) *vel = any ? &h->tracerVelHost.get()->x : nullptr;
@@ -150,17 +119,10 @@ int sph_get_tracer_stats(sph_handle *h, SphTracerStats *out, int reset) {
     if (!h || !out) return SPH_EINVAL;
     SphTracerStats S{};
     S.struct_size = (int32_t)sizeof S;
-    int rc = timed_total(h, &h->tracerSeconds, &h->tracerCalls, &S.seconds, &S.calls, reset);
+    int rc = timed_total(h, &h->tracer.seconds, &h->tracer.calls, &S.seconds, &S.calls, reset);
     if (rc) return rc;
-    if (h->tracerCounters) {
-        HIPCHK(h, hipMemcpyAsync(h->tracerCountersHost, h->tracerCounters, kTracerCounters * sizeof(unsigned long long),
-                                 hipMemcpyDeviceToHost, h->compute));
-        if (reset) HIPCHK(h, hipMemsetAsync(h->tracerCounters, 0, kTracerCounters * sizeof(unsigned long long), h->compute));
-        HIPCHK(h, hipStreamSynchronize(h->compute));
-        S.waves_shared = h->tracerCountersHost[0];
-        S.waves_direct = h->tracerCountersHost[1];
-        S.groups = h->tracerCountersHost[2];
-    }
+    if ((rc = h->tracerCounters.read(h, reset))) return rc;
+    if (const unsigned long long *c = h->tracerCounters.host) S.waves_shared = c[0], S.waves_direct = c[1], S.groups = c[2];
     *out = S;
     return SPH_OK;
 }

@@ -10,15 +10,12 @@
 // contiguous run of the stream, the wave stages the hull of those runs in LDS and every lane reads every staged
 // candidate by broadcast.  A lane TAKES candidate k only if k lies in its own run and the lane belongs to the group
 // being walked (integer compares); the distance test alone would not do, for the reason sample.hip's header gives.
-// A candidate that is not taken adds +0.f, which changes no bit: a float sum that starts at +0.f is never -0.f
-// under round-to-nearest (x + y is -0 only when both are, an exact cancellation gives +0), although the m v terms
-// are signed.  The term is SELECTED (take ? m v : 0.f), never multiplied by a mask: the m of a candidate that is
-// not taken is garbage of either sign.  The wave loops over its groups wave-uniformly; a lane's whole walk happens
+// A candidate that is not taken adds a selected +0.f, which changes no bit although the m v terms are signed
+// (walk_common.h).  The wave loops over its groups wave-uniformly; a lane's whole walk happens
 // inside its own group's iteration, so its order is the definition's.  A wave whose lanes fall into more than
 // kTracerMaxGroups groups walks the direct way, every lane its own 27 cells from global memory: the shared walk
 // serialises over groups, and 64 lone tracers would cost 64 shared walks.
-#include "sph_c_api.h"
-#include "sph_device.h"
+#include "walk_common.h"
 
 namespace {
 
@@ -39,61 +36,35 @@ static_assert(kTracerChunk % 4 == 0 && (kTracerBlockX & (kTracerBlockX - 1)) == 
 constexpr int kTracerMaxGroups = TRACER_MAX_GROUPS; // G: a wave with more groups than this walks the direct way
 constexpr int kNoGroup = 0x7fffffff;
 
-// the cell of a coordinate, (int)(p / h) like the cell hash, or -1 for a point outside the grid (section 10b's)
-__device__ __forceinline__ int tracer_cell(const DevParams &P, float p) {
-    if (!(p >= 0.f)) return -1;
-    const float q = p / P.h;
-    if (!(q < (float)P.D)) return -1;
-    return (int)q;
-}
-
 // one candidate, c = (x, y, z, .), v = (vx, vy, vz, .): the definition written down
 __device__ __forceinline__ void tracer_add(const DevParams &P, float px, float py, float pz, const float4 c, const float4 v,
                                            float &den, float &nx, float &ny, float &nz) {
     const float dx = px - c.x, dy = py - c.y, dz = pz - c.z;
-    const float d2 = (dx * dx + dy * dy) + dz * dz;
-    if (d2 > P.h2) return;
-    const float diff = P.h2 - d2;
-    const float m = SPH_MASS * (((P.dcoef * diff) * diff) * diff);
-    den += m;
-    nx += m * v.x;
-    ny += m * v.y;
-    nz += m * v.z;
+    const Poly6 K = poly6_mass(P, (dx * dx + dy * dy) + dz * dz);
+    if (!K.taken) return;
+    den += K.m;
+    nx += K.m * v.x;
+    ny += K.m * v.y;
+    nz += K.m * v.z;
 }
 
-// the same without a branch: a candidate that is not taken, or lies beyond h, adds +0 to all four sums
+// the same with selected terms: a candidate that is not taken, or lies beyond h, adds +0 to all four sums
 __device__ __forceinline__ void tracer_add(const DevParams &P, float px, float py, float pz, const float4 c, const float4 v,
                                            bool take, float &den, float &nx, float &ny, float &nz) {
     const float dx = px - c.x, dy = py - c.y, dz = pz - c.z;
-    const float d2 = (dx * dx + dy * dy) + dz * dz;
-    take = take && !(d2 > P.h2);
-    const float diff = P.h2 - d2;
-    const float m = SPH_MASS * (((P.dcoef * diff) * diff) * diff);
-    den += take ? m : 0.f;
-    nx += take ? m * v.x : 0.f;
-    ny += take ? m * v.y : 0.f;
-    nz += take ? m * v.z : 0.f;
+    const Poly6 K = poly6_mass(P, (dx * dx + dy * dy) + dz * dz);
+    take = take && K.taken;
+    den += take ? K.m : 0.f;
+    nx += take ? K.m * v.x : 0.f;
+    ny += take ? K.m * v.y : 0.f;
+    nz += take ? K.m * v.z : 0.f;
 }
 
 // the direct walk of one tracer inside the grid: 27 cells of global loads (the check path, and the waves of the
 // default path that hold too many groups)
 __device__ __forceinline__ void tracer_walk_direct(const DevParams &P, const TracerArgs &A, float px, float py, float pz, int cx,
                                                    int cy, int cz, float &den, float &nx, float &ny, float &nz) {
-    for (int dz = -1; dz < 2; ++dz) {
-        const int sz = cz + dz;
-        if (sz < 0 || sz >= P.D) continue;
-        for (int dy = -1; dy < 2; ++dy) {
-            const int sy = cy + dy;
-            if (sy < 0 || sy >= P.D) continue;
-            for (int dx = -1; dx < 2; ++dx) {
-                const int sx = cx + dx;
-                if (sx < 0 || sx >= P.D) continue;
-                const int2 run = A.cellRange[(sz * P.D + sy) * P.D + sx];
-                for (int j = max(run.x, 0); j < min(run.y, A.n); ++j)
-                    tracer_add(P, px, py, pz, A.pos[(size_t)j * A.stride], A.vel[(size_t)j * A.stride], den, nx, ny, nz);
-            }
-        }
-    }
+    for_each_candidate_27(P, A.S, cx, cy, cz, [&](int j) WALK_LAMBDA { tracer_add(P, px, py, pz, A.S.position(j), A.S.velocity(j), den, nx, ny, nz); });
 }
 
 // velocity, move and the two stores of tracer idx; p holds its position words as they were loaded
@@ -113,9 +84,9 @@ __global__ __launch_bounds__(256) void k_tracer_plain(DevParams P, TracerArgs A)
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= A.m) return;
     const float4 p = A.posDen[i];
-    const int cx = tracer_cell(P, p.x), cy = tracer_cell(P, p.y), cz = tracer_cell(P, p.z);
+    const int cx = point_cell(P, p.x), cy = point_cell(P, p.y), cz = point_cell(P, p.z);
     float den = 0.f, nx = 0.f, ny = 0.f, nz = 0.f;
-    if (A.n > 0 && cx >= 0 && cy >= 0 && cz >= 0) tracer_walk_direct(P, A, p.x, p.y, p.z, cx, cy, cz, den, nx, ny, nz);
+    if (A.S.n > 0 && cx >= 0 && cy >= 0 && cz >= 0) tracer_walk_direct(P, A, p.x, p.y, p.z, cx, cy, cz, den, nx, ny, nz);
     tracer_finish(A, (uint32_t)i, p, den, nx, ny, nz);
 }
 
@@ -124,7 +95,7 @@ __global__ __launch_bounds__(256) void k_tracer_keys(DevParams P, TracerArgs A) 
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= A.m) return;
     const float4 p = A.posDen[i];
-    const int cx = tracer_cell(P, p.x), cy = tracer_cell(P, p.y), cz = tracer_cell(P, p.z);
+    const int cx = point_cell(P, p.x), cy = point_cell(P, p.y), cz = point_cell(P, p.z);
     const bool inside = cx >= 0 && cy >= 0 && cz >= 0;
     A.keys[i] = inside ? (uint32_t)((cz * P.D + cy) * P.D + cx) : (uint32_t)P.numCells;
     A.vals[i] = (uint32_t)i;
@@ -139,7 +110,7 @@ __global__ __launch_bounds__(64) void k_tracer_walk(DevParams P, TracerArgs A) {
     const bool valid = idx < (uint32_t)A.m; // (the sort's values are a permutation of [0, m): never false for i < m)
     if (!valid) idx = 0;
     const float4 p = valid ? A.posDen[idx] : make_float4(0.f, 0.f, 0.f, 0.f);
-    const int cx = tracer_cell(P, p.x), cy = tracer_cell(P, p.y), cz = tracer_cell(P, p.z);
+    const int cx = point_cell(P, p.x), cy = point_cell(P, p.y), cz = point_cell(P, p.z);
     const bool inside = valid && cx >= 0 && cy >= 0 && cz >= 0;
     const int gkey = inside ? (cz * P.D + cy) * P.D + (cx & ~(kTracerBlockX - 1)) : kNoGroup;
     // The groups of this wave.  The lanes are sorted by cell key, the group key is monotone in it: a group begins
@@ -171,42 +142,20 @@ __global__ __launch_bounds__(64) void k_tracer_walk(DevParams P, TracerArgs A) {
                 for (int dy = -1; dy < 2; ++dy) {
                     const int sy = gy + dy;
                     if (sy < 0 || sy >= P.D) continue;
-                    // this lane's window of the stream: the rows of cells cx - 1 .. cx + 1 of this (y, z) row, one
-                    // contiguous run (empty cells hold {0, 0} and add nothing); empty for a lane of another group
-                    int ws = 0x7fffffff, we = 0;
-                    if (act) {
-                        const int2 *cells = A.cellRange + (sz * P.D + sy) * P.D;
-                        for (int sx = max(cx - 1, 0); sx <= min(cx + 1, P.D - 1); ++sx) {
-                            const int2 run = cells[sx];
-                            if (run.y > run.x) {
-                                ws = min(ws, run.x);
-                                we = max(we, run.y);
-                            }
-                        }
-                    }
-                    // the stretch the wave stages: from the first window's start to the last one's end
-                    const int s0 = max(__builtin_amdgcn_readfirstlane(wave_min_i32(ws)), 0);
-                    const int s1 = min(__builtin_amdgcn_readfirstlane(wave_max_i32(we)), A.n);
+                    int ws, we, s0, s1; // this lane's window (empty for a lane of another group), the wave's stretch
+                    lane_window(P, A.S, sy, sz, cx, act, ws, we);
+                    wave_hull(ws, we, A.S.n, s0, s1);
                     for (int base = s0; base < s1; base += kTracerChunk) {
                         const int cnt = min(kTracerChunk, s1 - base);
                         __syncthreads(); // the previous chunk has been read
                         // 32 bytes per candidate: (x, y, z, ., vx, vy, vz, .); with the interleaved records
                         // (vel = pos + 1, stride 2) a plain copy
                         for (int t = lane; t < 2 * cnt; t += 64)
-                            cand[t] = ((t & 1) ? A.vel : A.pos)[(size_t)(base + (t >> 1)) * A.stride];
+                            cand[t] = ((t & 1) ? A.S.vel : A.S.pos)[(size_t)(base + (t >> 1)) * A.S.stride];
                         __syncthreads();
-                        // every lane reads every candidate (one LDS address per read: a broadcast) and takes those
-                        // of its own window, in stream order.  (Slots past cnt hold stale rows: they lie outside
-                        // every [lo, hi).)
-                        const int lo = max(ws - base, 0), hi = min(we - base, cnt);
-                        for (int k = 0; k < cnt; k += 4) {
-                            float4 c[4], v[4];
-#pragma unroll
-                            for (int u = 0; u < 4; ++u) c[u] = cand[2 * (k + u)], v[u] = cand[2 * (k + u) + 1];
-#pragma unroll
-                            for (int u = 0; u < 4; ++u)
-                                tracer_add(P, p.x, p.y, p.z, c[u], v[u], k + u >= lo && k + u < hi, den, nx, ny, nz);
-                        }
+                        take_staged<2>(cand, cnt, ws - base, we - base, [&](const float4(&c)[2], bool mine) WALK_LAMBDA {
+                            tracer_add(P, p.x, p.y, p.z, c[0], c[1], mine, den, nx, ny, nz);
+                        });
                     }
                 }
             }
@@ -219,7 +168,7 @@ __global__ __launch_bounds__(64) void k_tracer_walk(DevParams P, TracerArgs A) {
 
 void sph_launch_tracers(const DevParams &P, TracerArgs A, bool plain, const SortWorkspace &ws, int keyBits, hipStream_t s) {
     if (A.m <= 0) return;
-    if (plain || A.n <= 0) { // (no particle: every sum is empty, no grid to read)
+    if (plain || A.S.n <= 0) { // (no particle: every sum is empty, no grid to read)
         k_tracer_plain<<<(A.m + 255) / 256, 256, 0, s>>>(P, A);
         return;
     }

@@ -44,6 +44,24 @@ def _fp(a):
     return a.ctypes.data_as(C.POINTER(C.c_float)) if a is not None else None
 
 
+def _lattice(o, shape, origin, spacing):
+    """struct_size, nx / ny / nz, origin and spacing of a lattice struct (SphSampleLattice, SphSurfaceOptions) from
+    `shape` = (nz, ny, nx), origin as (x, y, z) and spacing as (x, y, z) or one number; returns (nz, ny, nx) as ints."""
+    nz, ny, nx = (int(d) for d in shape)
+    o.struct_size = C.sizeof(type(o))
+    o.nx, o.ny, o.nz = nx, ny, nz
+    o.origin[:] = [float(v) for v in origin]
+    o.spacing[:] = [float(v) for v in (spacing if np.ndim(spacing) else (spacing,) * 3)]
+    return nz, ny, nx
+
+
+def _rows(p, n, cols, dtype):
+    """An array of its own of the n x cols values behind the C pointer p (cols = None: n values); n == 0 (p may be
+    null): the empty array of that shape."""
+    shape = (n,) if cols is None else (n, cols)
+    return np.array(np.ctypeslib.as_array(p, shape=shape), copy=True) if n else np.zeros(shape, dtype)
+
+
 class Simulator:
     def __init__(self, settings, sweep="list", flags=0, device=-1, capacity=0, math="strict", key_order="flattened"):
         self.settings = settings
@@ -234,12 +252,8 @@ class Simulator:
         """`field` ("density", "speed", "pressure") of the current state at the lattice points
         origin + (ix, iy, iz) * spacing -- origin and spacing as (x, y, z), spacing also as one number --
         as an np.float32 array of its own of `shape` = (nz, ny, nx).  Points outside the grid give 0."""
-        nz, ny, nx = (int(d) for d in shape)
         lat = _lib.SphSampleLattice()
-        lat.struct_size = C.sizeof(_lib.SphSampleLattice)
-        lat.nx, lat.ny, lat.nz = nx, ny, nz
-        lat.origin[:] = [float(o) for o in origin]
-        lat.spacing[:] = [float(s) for s in (spacing if np.ndim(spacing) else (spacing,) * 3)]
+        nz, ny, nx = _lattice(lat, shape, origin, spacing)
         lat.field = _lib.FIELDS[field] if isinstance(field, str) else int(field)
         self._check(self._L.sph_sample_field(self._h, C.byref(lat)), "sph_sample_field")
         p = self._L.sph_sample_host(self._h, None, None, None)
@@ -260,21 +274,15 @@ class Simulator:
         `shape` = (nz, ny, nx) as for sample_field, by marching tetrahedra on the device: {"vertices": float32
         (V, 3), "triangles": uint32 (T, 3)}, arrays of their own.  Normals (a, b, c -> (b - a) x (c - a)) point out
         of the fluid; the mesh is closed when the lattice's outer shell lies outside it."""
-        nz, ny, nx = (int(d) for d in shape)
         o = _lib.SphSurfaceOptions()
-        o.struct_size = C.sizeof(_lib.SphSurfaceOptions)
-        o.nx, o.ny, o.nz = nx, ny, nz
-        o.origin[:] = [float(v) for v in origin]
-        o.spacing[:] = [float(s) for s in (spacing if np.ndim(spacing) else (spacing,) * 3)]
+        _lattice(o, shape, origin, spacing)
         o.iso = float(iso)
         self._check(self._L.sph_extract_surface(self._h, C.byref(o)), "sph_extract_surface")
         vp, tp = C.POINTER(C.c_float)(), C.POINTER(C.c_uint32)()
         nv, nt = C.c_int64(0), C.c_int64(0)
         self._check(self._L.sph_surface_host(self._h, C.byref(vp), C.byref(nv), C.byref(tp), C.byref(nt)),
                     "sph_surface_host")
-        verts = np.array(np.ctypeslib.as_array(vp, shape=(nv.value, 3)), copy=True) if nv.value else np.zeros((0, 3), np.float32)
-        tris = np.array(np.ctypeslib.as_array(tp, shape=(nt.value, 3)), copy=True) if nt.value else np.zeros((0, 3), np.uint32)
-        return {"vertices": verts, "triangles": tris}
+        return {"vertices": _rows(vp, nv.value, 3, np.float32), "triangles": _rows(tp, nt.value, 3, np.uint32)}
 
     def surface_time(self, reset=False):
         """(sample_seconds, extract_seconds, calls): GPU time of the surface's sampling kernel and of its
@@ -330,11 +338,8 @@ class Simulator:
         set: the positions after the last advect, the density sum and the velocity it sampled before the move."""
         pd, u, m = C.POINTER(C.c_float)(), C.POINTER(C.c_float)(), C.c_int(0)
         self._check(self._L.sph_tracers_host(self._h, C.byref(pd), C.byref(u), C.byref(m)), "sph_tracers_host")
-        if m.value == 0:
-            return dict(pos=np.zeros((0, 3), np.float32), den=np.zeros(0, np.float32), vel=np.zeros((0, 3), np.float32))
-        pd = np.ctypeslib.as_array(pd, shape=(m.value, 4))
-        u = np.ctypeslib.as_array(u, shape=(m.value, 4))
-        return dict(pos=np.array(pd[:, :3], copy=True), den=np.array(pd[:, 3], copy=True), vel=np.array(u[:, :3], copy=True))
+        pd, u = _rows(pd, m.value, 4, np.float32), _rows(u, m.value, 4, np.float32)
+        return dict(pos=np.ascontiguousarray(pd[:, :3]), den=np.ascontiguousarray(pd[:, 3]), vel=np.ascontiguousarray(u[:, :3]))
 
     def tracer_stats(self, reset=False):
         """dict(calls, waves_shared, waves_direct, groups, seconds): sums since create or the last reset; `seconds`
@@ -353,14 +358,10 @@ class Simulator:
         self._check(self._L.sph_derive(self._h), "sph_derive")
         wd, gr, nb, n = C.POINTER(C.c_float)(), C.POINTER(C.c_float)(), C.POINTER(C.c_uint32)(), C.c_int(0)
         self._check(self._L.sph_derived_host(self._h, C.byref(wd), C.byref(gr), C.byref(nb), C.byref(n)), "sph_derived_host")
-        if n.value == 0:
-            z3, z1 = np.zeros((0, 3), np.float32), np.zeros(0, np.float32)
-            return dict(vorticity=z3, divergence=z1, grad_rho=z3.copy(), rho=z1.copy(), neighbours=np.zeros(0, np.uint32))
-        wd = np.ctypeslib.as_array(wd, shape=(n.value, 4))
-        gr = np.ctypeslib.as_array(gr, shape=(n.value, 4))
-        nb = np.ctypeslib.as_array(nb, shape=(n.value,))
-        return dict(vorticity=np.array(wd[:, :3], copy=True), divergence=np.array(wd[:, 3], copy=True),
-                    grad_rho=np.array(gr[:, :3], copy=True), rho=np.array(gr[:, 3], copy=True), neighbours=np.array(nb, copy=True))
+        wd, gr = _rows(wd, n.value, 4, np.float32), _rows(gr, n.value, 4, np.float32)
+        return dict(vorticity=np.ascontiguousarray(wd[:, :3]), divergence=np.ascontiguousarray(wd[:, 3]),
+                    grad_rho=np.ascontiguousarray(gr[:, :3]), rho=np.ascontiguousarray(gr[:, 3]),
+                    neighbours=_rows(nb, n.value, None, np.uint32))
 
     def derive_stats(self, reset=False):
         """dict(calls, runs_staged, runs_direct, seconds): sums since create or the last reset; `seconds` is the GPU
@@ -380,10 +381,7 @@ class Simulator:
         self._check(self._L.sph_label_bodies(self._h, C.byref(opt)), "sph_label_bodies")
         lab, tab, n, k, big = C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint32)(), C.c_int(0), C.c_int(0), C.c_uint32(0)
         self._check(self._L.sph_bodies_host(self._h, C.byref(lab), C.byref(n), C.byref(tab), C.byref(k), C.byref(big)), "sph_bodies_host")
-        if n.value == 0:
-            return dict(labels=np.zeros(0, np.uint32), table=np.zeros((0, 8), np.uint32), num_bodies=0, largest=0)
-        return dict(labels=np.array(np.ctypeslib.as_array(lab, shape=(n.value,)), copy=True),
-                    table=np.array(np.ctypeslib.as_array(tab, shape=(k.value, 8)), copy=True),
+        return dict(labels=_rows(lab, n.value, None, np.uint32), table=_rows(tab, k.value, 8, np.uint32),
                     num_bodies=k.value, largest=big.value)
 
     def body_stats(self, reset=False):
