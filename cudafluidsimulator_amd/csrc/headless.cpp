@@ -31,8 +31,14 @@ static int env_field(const char *var, const char *instead) {
     return -1;
 }
 
-// SPH_FREE_SHADE: the field that colours the frames; unset: the reference's flat blue
-static int shade_field() { return env_field("SPH_FREE_SHADE", "writing flat frames"); }
+// SPH_FREE_SHADE: the field that colours the frames, or `column` (kShadeColumn) for column-density frames; unset:
+// the reference's flat blue
+static const int kShadeColumn = 100;
+static int shade_field() {
+    const char *e = getenv("SPH_FREE_SHADE");
+    if (e && !strcmp(e, "column")) return kShadeColumn;
+    return env_field("SPH_FREE_SHADE", "nor column: writing flat frames");
+}
 
 // <dir>/<pattern with the frame number f> opened for writing bytes, or NULL after a complaint on stderr
 static FILE *open_out(const char *dir, const char *pattern, int f) {
@@ -77,7 +83,9 @@ static bool write_ply(const char *dir, const char *pattern, int f, long long cou
 // SPH_FREE_FRAMES_DIR=<dir>: what the window would have shown after frame f, as <dir>/frame_%04d.ppm (binary P6)
 static bool write_frame(Simulator *simulator, const char *dir, int f, int field) {
     int w = 0, h = 0;
-    const unsigned char *rgb = field < 0 ? simulator->renderFrame(&w, &h) : simulator->renderField(field, &w, &h);
+    const unsigned char *rgb = field < 0                ? simulator->renderFrame(&w, &h)
+                               : field == kShadeColumn ? simulator->renderColumn(&w, &h)
+                                                       : simulator->renderField(field, &w, &h);
     return rgb && write_ppm(dir, "frame_%04d.ppm", f, w, h, rgb);
 }
 

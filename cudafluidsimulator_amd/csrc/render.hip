@@ -9,6 +9,8 @@
 // atomics) and sends ONE global atomic per touched pixel and buffer.  A workgroup whose rectangle
 // does not fit the tile (unsorted state right after an upload, very large images) issues the plain
 // per-hit global atomics instead.  Minimum and sum commute, so every path gives the same buffers.
+// The column frame (section 10h, further down) is the same scheme over footprints that vary with depth, with a
+// 64-bit integer sum per pixel.
 #include "sph_c_api.h"
 #include "sph_device.h"
 
@@ -258,16 +260,21 @@ __device__ __forceinline__ uint32_t field_ramp(uint32_t q) {
     return 0xFFu | ((255u - 4u * (q - 192u)) << 8);
 }
 
+// the quantiser of the field and column frames: q = 0..255 of s on the scale lo..hi
+__device__ __forceinline__ uint32_t field_quantise(float s, float lo, float hi) {
+    uint32_t q = 0u;
+    if (hi != lo) {
+        const float u = ((s - lo) / (hi - lo)) * 256.f;
+        if (u == u) q = (uint32_t)(int)fminf(fmaxf(floorf(u), 0.f), 255.f); // (NaN: q = 0)
+    }
+    return q;
+}
+
 __device__ __forceinline__ uint32_t field_rgb(unsigned long long m, uint32_t c, uint32_t e, float lo, float hi) {
     const uint32_t d = (uint32_t)(m >> 32);
     if (e != 0xFFFFFFFFu && e <= d) return 0xFFFFFFu; // GL_LESS, lines drawn first
     if (c == 0u) return 0u;
-    uint32_t q = 0u;
-    if (hi != lo) {
-        const float u = ((__uint_as_float((uint32_t)m) - lo) / (hi - lo)) * 256.f;
-        if (u == u) q = (uint32_t)(int)fminf(fmaxf(floorf(u), 0.f), 255.f); // (NaN: q = 0)
-    }
-    return field_ramp(q);
+    return field_ramp(field_quantise(__uint_as_float((uint32_t)m), lo, hi));
 }
 
 // four pixels = 12 bytes = three dwords per thread (rgb is padded to a multiple of four pixels); colour(p) = 0xBBGGRR of pixel p
@@ -302,6 +309,220 @@ __global__ __launch_bounds__(256) void k_field_compose(const unsigned long long 
     });
 }
 
+// ---- the column frame: per pixel the sum over ALL particles of a 64-bit integer term ----
+// Through the centre of pixel (c, r) runs the ray (ax(c), ay(r), -1) from the eye; a particle within h of it adds the
+// line integral of its poly6 kernel along the ray, MASS coeff (32/35) a^7, as the integer (uint64)(term 2^32).  Sums of
+// integers commute: the tile, its fallback and the check path give the same words, whatever the order of the rows.
+//
+// Work split: one lane walks the whole footprint of its particle (9 to ~200 pixel tests).  The footprint's size is a
+// function of the particle's depth w (and, weakly, of its angle off the axis); in the cell-sorted stream the 64 rows
+// of a wave come from one cell or its neighbours in x, so their w differ by about h and their footprints by a pixel:
+// the lanes' trip counts agree without splitting particles by footprint row, which would cost each piece the
+// per-particle set-up again.  Id-ordered state (right after an upload, SPH_SWEEP_LINKED) diverges; it also misses the
+// tile, and is not the case the frame is built for.
+//
+// ax and ay are read from a table built once per image size (sph_launch_column_rays) with the operations of the
+// definition; inv, one IEEE divide, is recomputed per test.
+
+struct ColumnParams {
+    float h, h2, dcoef;
+    const float *rays; // ax of column c at [c], ay of row r at [width + r]
+};
+
+__global__ __launch_bounds__(256) void k_column_rays(RenderParams R, float *__restrict__ rays) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < R.width) rays[i] = 2.f * ((((float)i + 0.5f) / (0.5f * R.Wf)) - 1.f);
+    else if (i < R.width + R.height) rays[i] = 2.f * ((((float)(R.height - 1 - (i - R.width)) + 0.5f) / (0.5f * R.Hf)) - 1.f);
+}
+
+__global__ __launch_bounds__(256) void k_column_clear(unsigned long long *__restrict__ column, int npix,
+                                                      unsigned long long *__restrict__ maxWord) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < npix) column[i] = 0ull;
+    if (i == 0) *maxWord = 0ull;
+}
+
+// the term of a pair with a2 = h h - b2 > 0
+__device__ __forceinline__ unsigned long long column_term(float a2, float dcoef) {
+    const float c = (SPH_MASS * (((dcoef * a2) * a2) * a2)) * ((32.f / 35.f) * sqrtf(a2));
+    if (c >= 1048576.f) return 1ull << 52;
+    if (!(c > 0.f)) return 0ull; // NaN, and a negative coefficient
+    return (unsigned long long)(c * 4294967296.f);
+}
+
+// The pixels a particle can reach, clipped to the viewport (empty: c1 < c0).  On a ray b >= |e| / s, which bounds the
+// footprint by 0.25 W h s_p / (w - h) columns and 0.25 H h s_p / (w - h) rows around the particle's own pixel (DESIGN.md
+// section 10h); rounded up, plus one for the fp32 evaluation here.  A particle at or behind the eye's h (w <= h) may
+// reach every pixel; a non-finite one reaches none (its b2 is NaN or infinite for every ray).
+struct Footprint {
+    float X, Y, w;
+    int c0, c1, r0, r1;
+};
+__device__ __forceinline__ Footprint column_footprint(const float4 p, const RenderParams &R, float h) {
+    Footprint f;
+    f.X = p.x - 5.f;
+    f.Y = p.y - 5.f;
+    f.w = 15.f - p.z;
+    f.c0 = f.r0 = 0;
+    f.c1 = f.r1 = -1;
+    if (!(fabsf(f.X) < INFINITY && fabsf(f.Y) < INFINITY && fabsf(f.w) < INFINITY)) return f;
+    f.c1 = R.width - 1;
+    f.r1 = R.height - 1;
+    const float d = f.w - h;
+    if (d > 0.f) {
+        const Pixel q = project(p.x, p.y, p.z, R); // (clamped to +-65536)
+        const float u = f.X / f.w, v = f.Y / f.w;
+        const float k = (h * sqrtf((1.f + u * u) + v * v)) / d;
+        // (fminf drops a NaN: the whole viewport then)
+        const int hx = (int)fminf(ceilf((0.25f * R.Wf) * k) + 1.f, 131072.f);
+        const int hy = (int)fminf(ceilf((0.25f * R.Hf) * k) + 1.f, 131072.f);
+        f.c0 = max(q.px - hx, 0);
+        f.c1 = min(q.px + hx, R.width - 1);
+        f.r0 = max(q.py - hy, 0);
+        f.r1 = min(q.py + hy, R.height - 1);
+    }
+    if (f.r1 < f.r0) f.c1 = f.c0 - 1; // one test for "empty"
+    return f;
+}
+
+// every pixel of the footprint whose ray passes within h: sink(column, row, term)
+template <class Sink>
+__device__ __forceinline__ void column_hits(const Footprint &f, const RenderParams &R, const ColumnParams &C, Sink sink) {
+    for (int r = f.r0; r <= f.r1; ++r) {
+        const float ay = C.rays[R.width + r];
+        const float ey = f.Y - ay * f.w;
+        for (int c = f.c0; c <= f.c1; ++c) {
+            const float ax = C.rays[c];
+            const float inv = 1.f / ((1.f + ax * ax) + ay * ay);
+            const float ex = f.X - ax * f.w;
+            const float t = ex * ax + ey * ay;
+            const float b2 = (ex * ex + ey * ey) - (t * t) * inv;
+            const float a2 = C.h2 - b2;
+            if (a2 > 0.f) { // (a NaN is not)
+                const unsigned long long q = column_term(a2, C.dcoef);
+                if (q) sink(c, r, q);
+            }
+        }
+    }
+}
+
+// the check path (SPH_RENDER_PLAIN=1): one thread per particle, one global atomic per contributing pixel
+__global__ __launch_bounds__(256) void k_column_plain(const float4 *__restrict__ pos4, int n, RenderParams R, ColumnParams C,
+                                                      unsigned long long *__restrict__ column) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const Footprint f = column_footprint(pos4[i], R, C.h);
+    column_hits(f, R, C, [&](int c, int r, unsigned long long q) { atomicAdd(&column[r * R.width + c], q); });
+}
+
+// k_splat_tile's scheme over the hull of the workgroup's FOOTPRINTS: LDS atomics into a 64 KB tile of 64-bit sums,
+// then one global atomic per touched pixel; a hull that does not fit the tile: per-hit global atomics
+__global__ __launch_bounds__(kSplatThreads) void k_column_tile(const float4 *__restrict__ pos4, int n, RenderParams R, ColumnParams C,
+                                                               unsigned long long *__restrict__ column) {
+    __shared__ unsigned long long tile[kTilePixels];
+    __shared__ int box[4]; // min column, min row, max column, max row over the workgroup's footprints
+    const int t = threadIdx.x;
+    const int base = blockIdx.x * kSplatBlock;
+    if (t < 2) box[t] = 0x7fffffff;
+    else if (t < 4) box[t] = -0x7fffffff;
+
+    Footprint f[kSplatPerThread];
+    int lox = 0x7fffffff, loy = 0x7fffffff, hix = -0x7fffffff, hiy = -0x7fffffff;
+#pragma unroll
+    for (int k = 0; k < kSplatPerThread; ++k) {
+        const int i = base + k * kSplatThreads + t;
+        f[k].c0 = f[k].r0 = 0;
+        f[k].c1 = f[k].r1 = -1;
+        if (i < n) f[k] = column_footprint(pos4[i], R, C.h);
+        if (f[k].c1 >= f[k].c0) {
+            lox = min(lox, f[k].c0);
+            hix = max(hix, f[k].c1);
+            loy = min(loy, f[k].r0);
+            hiy = max(hiy, f[k].r1);
+        }
+    }
+    lox = wave_min_i32(lox);
+    loy = wave_min_i32(loy);
+    hix = wave_max_i32(hix);
+    hiy = wave_max_i32(hiy);
+    __syncthreads();
+    if ((t & 63) == 0) {
+        atomicMin(&box[0], lox);
+        atomicMin(&box[1], loy);
+        atomicMax(&box[2], hix);
+        atomicMax(&box[3], hiy);
+    }
+    __syncthreads();
+    if (box[2] < box[0]) return; // nothing of this workgroup is on screen (uniform)
+    const int x0 = box[0], y0 = box[1];
+    const int bw = box[2] - x0 + 1, bh = box[3] - y0 + 1;
+    const long long area = (long long)bw * bh;
+
+    if (area > kTilePixels) { // (uniform)
+#pragma unroll
+        for (int k = 0; k < kSplatPerThread; ++k)
+            column_hits(f[k], R, C, [&](int c, int r, unsigned long long q) { atomicAdd(&column[r * R.width + c], q); });
+        return;
+    }
+
+    const int area32 = (int)area;
+    for (int e = t; e < area32; e += kSplatThreads) tile[e] = 0ull;
+    __syncthreads();
+    // (every footprint lies inside the hull [x0, x0 + bw) x [y0, y0 + bh) by construction)
+#pragma unroll
+    for (int k = 0; k < kSplatPerThread; ++k)
+        column_hits(f[k], R, C, [&](int c, int r, unsigned long long q) { atomicAdd(&tile[(r - y0) * bw + (c - x0)], q); });
+    __syncthreads();
+    for (int e = t; e < area32; e += kSplatThreads) {
+        const unsigned long long v = tile[e];
+        if (v == 0ull) continue;
+        const int ey = e / bw;
+        atomicAdd(&column[(y0 + ey) * R.width + x0 + (e - ey * bw)], v);
+    }
+}
+
+// automatic range: the largest column word (the value is monotonic in the word); wave64 shuffles, one LDS step
+// across the four waves, then at most one atomic per workgroup
+__global__ __launch_bounds__(256) void k_column_max(const unsigned long long *__restrict__ column, int npix,
+                                                    unsigned long long *__restrict__ maxWord) {
+    __shared__ unsigned long long whi[4];
+    unsigned long long hi = 0ull;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < npix; i += gridDim.x * 256) hi = max(hi, column[i]);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) hi = max(hi, (unsigned long long)__shfl_xor(hi, off));
+    if ((threadIdx.x & 63) == 0) whi[threadIdx.x >> 6] = hi;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        hi = max(max(whi[0], whi[1]), max(whi[2], whi[3]));
+        if (*maxWord < hi) atomicMax(maxWord, hi); // (it only rises: a stale load that already is past ours settles it)
+    }
+}
+
+// one round-to-nearest-even conversion of the 64-bit word, then an exact scaling by 2^-32
+__device__ __forceinline__ float column_value(unsigned long long sum) { return (float)sum * 2.3283064365386963e-10f; }
+
+// maxWord: the reduced maximum of an automatic range (then lo = +0, hi = its value), or null (lo, hi: the options');
+// leaves the bits of the range it used in range[0..1]
+__global__ __launch_bounds__(256) void k_column_compose(const unsigned long long *__restrict__ column, const uint32_t *__restrict__ edge,
+                                                        const unsigned long long *__restrict__ maxWord, float lo, float hi, int npix,
+                                                        uint32_t *__restrict__ range, uint32_t *__restrict__ rgb) {
+    if (maxWord) {
+        lo = 0.f;
+        hi = column_value(*maxWord);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        range[0] = __float_as_uint(lo);
+        range[1] = __float_as_uint(hi);
+    }
+    compose_quad(npix, rgb, [&](int p) -> uint32_t {
+        if (edge[p] != 0xFFFFFFFFu) return 0xFFFFFFu; // the fluid is translucent: no depth test
+        const unsigned long long sum = column[p];
+        if (sum == 0ull) return 0u;
+        const uint32_t q = field_quantise(column_value(sum), lo, hi);
+        return (223u - ((7u * q) >> 3)) | ((239u - ((3u * q) >> 2)) << 8) | ((255u - (q >> 1)) << 16);
+    });
+}
+
 template <class Pay>
 void launch_splat(const RenderParams &R, const float4 *pos4, int n, bool plain, Pay pay, uint32_t *count, hipStream_t s) {
     if (n <= 0) return;
@@ -324,6 +545,25 @@ void sph_launch_render(const RenderParams &R, const float4 *pos4, int n, bool pl
     launch_splat(R, pos4, n, plain, FlatPayload{depth}, count, s);
     const int quads = (npix + 3) / 4;
     k_render_compose<<<(quads + 255) / 256, 256, 0, s>>>(depth, count, edge, npix, R.shade, rgb);
+}
+
+void sph_launch_column_rays(const RenderParams &R, float *rays, hipStream_t s) {
+    k_column_rays<<<(R.width + R.height + 255) / 256, 256, 0, s>>>(R, rays);
+}
+
+void sph_launch_render_column(const RenderParams &R, const float4 *pos4, int n, bool plain, float h, float h2, float dcoef,
+                              bool autoRange, float lo, float hi, const float *rays, unsigned long long *column,
+                              unsigned long long *maxWord, const uint32_t *edge, uint32_t *range, uint32_t *rgb, hipStream_t s) {
+    const int npix = R.width * R.height;
+    const ColumnParams C{h, h2, dcoef, rays};
+    k_column_clear<<<(npix + 255) / 256, 256, 0, s>>>(column, npix, maxWord);
+    if (n > 0) {
+        if (plain) k_column_plain<<<(n + 255) / 256, 256, 0, s>>>(pos4, n, R, C, column);
+        else k_column_tile<<<(n + kSplatBlock - 1) / kSplatBlock, kSplatThreads, 0, s>>>(pos4, n, R, C, column);
+    }
+    if (autoRange) k_column_max<<<min((npix + 255) / 256, 1024), 256, 0, s>>>(column, npix, maxWord);
+    const int quads = (npix + 3) / 4;
+    k_column_compose<<<(quads + 255) / 256, 256, 0, s>>>(column, edge, autoRange ? maxWord : nullptr, lo, hi, npix, range, rgb);
 }
 
 void sph_launch_render_field(const RenderParams &R, const float4 *pos4, const float4 *vel4, int n, bool plain, int field,

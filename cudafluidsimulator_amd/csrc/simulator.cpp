@@ -149,6 +149,18 @@ const unsigned char *Simulator::renderField(int field, int *width, int *height) 
     return f;
 }
 
+const unsigned char *Simulator::renderColumn(int *width, int *height) {
+    if (multi) {
+        fprintf(stderr, "sph: renderColumn: frames of a multi-GPU run (SPH_GPUS > 1) are not rendered\n");
+        return NULL;
+    }
+    if (!impl) return NULL;
+    check(impl, sph_render_column(impl, NULL), "sph_render_column");
+    const unsigned char *f = sph_frame_host(impl, width, height);
+    if (!f) check(impl, SPH_EHIP, "sph_frame_host");
+    return f;
+}
+
 const float *Simulator::sampleField(int field, const float origin[3], const float spacing[3], int nx, int ny, int nz) {
     if (multi) {
         fprintf(stderr, "sph: sampleField: a multi-GPU run (SPH_GPUS > 1) is not sampled\n");

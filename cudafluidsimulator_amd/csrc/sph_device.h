@@ -238,6 +238,15 @@ void sph_launch_render_field(const RenderParams &R, const float4 *pos4, const fl
                             bool autoRange, float lo, float hi, unsigned long long *packed, uint32_t *depth, uint32_t *count,
                             const uint32_t *edge, uint32_t *range, uint32_t *rgb, hipStream_t s);
 
+// The column frame.  rays: the pixel-centre rays of a width x height image, ax of column c
+// at [c], ay of row r at [width + r] (built once per image size, like the edge layer).
+void sph_launch_column_rays(const RenderParams &R, float *rays, hipStream_t s);
+// clear + splat of pos4[0, n) into `column` (one 64-bit sum per pixel) + (autoRange: the largest word into *maxWord)
+// + compose into rgb, which also leaves the bits of the range used in range[0..1].  h2, dcoef: the handle's settings.
+void sph_launch_render_column(const RenderParams &R, const float4 *pos4, int n, bool plain, float h, float h2, float dcoef,
+                              bool autoRange, float lo, float hi, const float *rays, unsigned long long *column,
+                              unsigned long long *maxWord, const uint32_t *edge, uint32_t *range, uint32_t *rgb, hipStream_t s);
+
 // The bits of the field frame's scalar of a row, from the (vx, vy, vz, rho) sph_download_state
 // reads: what the field frame colours by and the diagnostics reduce.  fp32, every operation rounded on its own.
 __device__ __forceinline__ uint32_t field_bits(const float4 v, int field) {

@@ -40,7 +40,7 @@ using sph_owned::PinnedBuf;
 //   SPH_STEP_TRACE        0        create  non-zero: sph_destroy prints where the host spent its timed steps, every timed
 //                                          step its GPU timeline, sph_create the SDMA engine it picked
 //   SPH_READBACK_SDMA     1        create  0: timed steps read back through the HIP runtime's copy, not an SDMA engine
-//   SPH_RENDER_PLAIN      0        call    non-zero: sph_render_frame / sph_render_field take the check path
+//   SPH_RENDER_PLAIN      0        call    non-zero: sph_render_frame / _field / _column take the check path
 //   SPH_SAMPLE_PLAIN      0        call    non-zero: sph_sample_field takes the one-thread-per-point check path
 //   SPH_DIAG_PLAIN        0        call    non-zero: sph_diagnose / sph_slab_diagnose take the check path
 //   SPH_SURFACE_PLAIN     0        call    non-zero: sph_extract_surface takes the check path, for its sample and its extraction
@@ -100,6 +100,9 @@ struct Pass {
     double seconds = 0; // from HIP events (PairEvent ring)
     long long calls = 0;
 };
+
+// What the last render drew (sph_frame.hip): decides which buffers hold a result and who may read them
+enum class FrameKind { Flat, Field, Column };
 
 // A few 64-bit counters a pass's kernels add to, on the device, with the pinned block they are read through.
 struct CounterBlock {
@@ -234,10 +237,14 @@ struct sph_handle {
                                      // the buffers hold a rendered frame of the size in rp; seconds: clear + splat + compose
     // The field frame (sph_render_field) adds the packed (depth bits << 32 | value bits) minimum per pixel and
     // the range of the colour scale: two words on the device, copied to pinned memory with the frame.
+    // The column frame (sph_render_column) keeps its 64-bit sum per pixel in the same buffer and sends its range the
+    // same way; it adds the word of the largest column and the table of the pixel-centre rays (per image size).
     sph_host::DeviceBuf<unsigned long long> rPacked;
     sph_host::DeviceBuf<uint32_t> rRange;
     sph_host::PinnedBuf<uint32_t> rangeHost;
-    bool fieldFrame = false;         // the last render was a field frame
+    sph_host::DeviceBuf<unsigned long long> rColumnMax;
+    sph_host::DeviceBuf<float> rRays;
+    sph_host::FrameKind frameKind = sph_host::FrameKind::Flat; // of the last render
 
     // ---- sph_sample.hip ----
     // The field sample (sample.hip): one float per lattice point on the device and in pinned memory, both grown

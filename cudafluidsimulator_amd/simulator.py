@@ -240,6 +240,33 @@ class Simulator:
         self._check(self._L.sph_field_range(self._h, C.byref(lo), C.byref(hi)), "sph_field_range")
         return np.float32(lo.value), np.float32(hi.value)
 
+    # -- the column frame: how much fluid lies behind each pixel (sph_render_column) --
+    def render_column(self, lo=0.0, hi=0.0, width=0, height=0):
+        """Queue one column-density frame of the current state over the scale lo..hi (both 0: from 0 to the
+        frame's largest column, reduced on the device); does not block.  frame_host() serves its RGB."""
+        o = _lib.SphColumnFrameOptions()
+        o.struct_size = C.sizeof(_lib.SphColumnFrameOptions)
+        o.width, o.height = int(width), int(height)
+        o.value_lo, o.value_hi = float(lo), float(hi)
+        self._check(self._L.sph_render_column(self._h, C.byref(o)), "sph_render_column")
+
+    def column_buffer(self):
+        """(H, W) uint64: the column word of each pixel of the last column frame (value = word / 2**32, 0 where
+        no particle reaches the pixel's ray)."""
+        w, h = C.c_int(0), C.c_int(0)
+        if not self._L.sph_frame_host(self._h, C.byref(w), C.byref(h)):
+            raise SphError("sph_frame_host failed: " + self._L.sph_last_error(self._h).decode())
+        out = np.zeros((h.value, w.value), np.uint64)
+        self._check(self._L.sph_download_column_buffer(self._h, out.ctypes.data_as(C.POINTER(C.c_uint64))),
+                    "sph_download_column_buffer")
+        return out
+
+    def column_range(self):
+        """(lo, hi) as np.float32: the colour scale the last column frame used; blocks until it is known."""
+        lo, hi = C.c_float(0), C.c_float(0)
+        self._check(self._L.sph_column_range(self._h, C.byref(lo), C.byref(hi)), "sph_column_range")
+        return np.float32(lo.value), np.float32(hi.value)
+
     def render_time(self, reset=False):
         """(seconds, frames): GPU time of clear + splat + compose summed over `frames` renders."""
         sec, fr = C.c_double(0), C.c_int64(0)

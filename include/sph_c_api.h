@@ -398,6 +398,39 @@ int sph_download_field_buffer(sph_handle *h, uint32_t *value_bits);
  * SPH_ESTATE if the last render was not a field frame. */
 int sph_field_range(sph_handle *h, float *lo, float *hi);
 
+/* ---- the column-density frame: how much fluid lies behind each pixel ----
+ * Additive to version 3: test for SPH_HAS_COLUMN_FRAME.  Defined to the bit in DESIGN.md section 10h ("The column
+ * frame"); all fp32, every operation rounded on its own.  The camera is sph_render_frame's.  Through the centre of
+ * every pixel runs a ray from the eye; a particle whose squared distance b2 to that ray is below h h adds
+ * c = MASS coeff (32/35) a^7, a2 = h h - b2: the line integral of its poly6 kernel along the ray, in closed form.  The
+ * term is the unsigned 64-bit integer (uint64)(c 2^32), 2^52 where c >= 2^20, 0 where c is NaN or negative; a pixel's
+ * column word is the sum of the terms of ALL particles modulo 2^64, so it depends on the set of rows only.  Value of a
+ * pixel: (float)word 2^-32.  Colour: the field frame's quantiser over value_lo .. value_hi, then an integer ramp from a
+ * thin film (223, 239, 255) to deep water (0, 48, 128); word 0: black; white wherever the box-edge layer has a sample
+ * (the fluid is translucent: no depth test).  The image is point-sampled: a particle whose footprint holds no pixel
+ * centre adds nothing. */
+#define SPH_HAS_COLUMN_FRAME 1
+typedef struct SphColumnFrameOptions {
+    int32_t struct_size;   /* = sizeof(SphColumnFrameOptions) */
+    int32_t width, height; /* 0 = 800 x 600; at most 4096 x 4096 */
+    float value_lo;        /* the colour scale runs from value_lo to value_hi; both 0: from 0 to the largest */
+    float value_hi;        /* column of this frame, reduced on the device */
+} SphColumnFrameOptions;
+/* sph_render_frame's queueing, streams and state rules (SPH_ESTATE before any state and for
+ * SPH_FLAG_EXTERNAL_STATE handles; works with SPH_FLAG_NO_READBACK, every sweep and both key orders; needs no grid
+ * and builds none; SPH_RENDER_PLAIN=1 selects the check path, one global atomic per particle and pixel).
+ * opt == NULL: 800 x 600, automatic range.  A bad size, a non-finite value_lo / value_hi, value_hi < value_lo:
+ * SPH_EINVAL.  Does not block.  sph_frame_host serves the RGB and sph_get_render_time counts the frame;
+ * sph_download_frame_buffers (a column frame writes no depth or count), sph_download_field_buffer and sph_field_range
+ * return SPH_ESTATE after it.  A flat or field frame rendered afterwards is what it would have been without it. */
+int sph_render_column(sph_handle *h, const SphColumnFrameOptions *opt);
+/* The column words behind the last column frame, width x height, row 0 first (value = word 2^-32, 0 = no particle
+ * reaches the ray).  SPH_ESTATE if the last render was not a column frame. */
+int sph_download_column_buffer(sph_handle *h, uint64_t *column_words);
+/* The range the last column frame used (the options', or 0 and the value of its largest word).  Blocks until it is
+ * on the host.  SPH_ESTATE if the last render was not a column frame. */
+int sph_column_range(sph_handle *h, float *lo, float *hi);
+
 /* ---- the field sample: SPH-interpolated density, speed or pressure on a regular lattice ----
  * Additive to version 3: test for SPH_HAS_FIELD_SAMPLE.  Defined to the bit in DESIGN.md section 10b ("The field
  * sample"); all fp32, every operation rounded on its own, in both math modes.  Point (ix, iy, iz) lies at
