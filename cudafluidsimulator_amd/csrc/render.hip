@@ -1,6 +1,6 @@
-// The visualiser's frame (display.cpp:35-90), drawn on the device: clear, splat, compose and the
-// one-off box-edge layer.  The image is defined exactly in DESIGN.md section 10; every operation
-// below is fp32 and rounded on its own (-ffp-contract=off), in the order that section gives.
+// The visualiser's frames (display.cpp:35-90), drawn on the device: clear, splat, compose and the one-off box-edge
+// layer.  The images are defined exactly in DESIGN.md sections 10, 10a and 10h; every operation below is fp32 and
+// rounded on its own (-ffp-contract=off), in the order those sections give.
 //
 // The splat is a scatter with heavy contention: at 800 x 600 every particle covers 9 pixels of a
 // 400 x 300 region, ~300 hits per pixel at n = 4 M and thousands on the rows the floor pile projects
@@ -9,8 +9,8 @@
 // atomics) and sends ONE global atomic per touched pixel and buffer.  A workgroup whose rectangle
 // does not fit the tile (unsorted state right after an upload, very large images) issues the plain
 // per-hit global atomics instead.  Minimum and sum commute, so every path gives the same buffers.
-// The column frame (section 10h, further down) is the same scheme over footprints that vary with depth, with a
-// 64-bit integer sum per pixel.
+// That scheme is written once (k_frame_tile, k_frame_plain) over a frame policy: SplatFrame, the squares of the flat
+// and field frames, and ColumnFrame (section 10h), footprints that vary with depth and a 64-bit integer sum per pixel.
 #include "sph_c_api.h"
 #include "sph_device.h"
 
@@ -19,7 +19,7 @@ namespace {
 constexpr int kSplatThreads = 256;
 constexpr int kSplatPerThread = 4;
 constexpr int kSplatBlock = kSplatThreads * kSplatPerThread; // particles per workgroup
-constexpr int kTilePixels = 8192;                            // a count and a minimum each: 64 KB (flat) or 96 KB (field) of LDS
+constexpr int kTilePixels = 8192;                            // 64 KB of LDS (flat, column) or 96 KB (field)
 
 struct Pixel {
     int px, py;
@@ -41,7 +41,7 @@ __device__ __forceinline__ Pixel project(float x, float y, float z, const Render
     return p;
 }
 
-// ---- the splat, once for two payloads ----
+// ---- the splat of the flat and field frames, once for two payloads ----
 // The flat frame keeps the minimum of the depth bits per pixel.  The field frame ("The field
 // frame") keeps the minimum of (bits(w) << 32) | bits(s), s >= +0 the scalar of the particle's vel4 row (xyz =
 // velocity, w = density): the high word IS the depth buffer of the flat frame, the low word the value of the nearest
@@ -56,7 +56,6 @@ __device__ __forceinline__ unsigned long long field_word(uint32_t wbits, uint32_
 struct FlatPayload {
     using Word = uint32_t;
     static constexpr Word kEmpty = 0xFFFFFFFFu;
-    static constexpr bool kRange = false;
     Word *least; // depth
     __device__ __forceinline__ Word word(uint32_t wbits, int) const { return wbits; }
 };
@@ -64,25 +63,31 @@ struct FlatPayload {
 struct FieldPayload {
     using Word = unsigned long long;
     static constexpr Word kEmpty = 0xFFFFFFFFFFFFFFFFull;
-    static constexpr bool kRange = true;
     Word *least; // packed
     const float4 *vel4;
     int field;
     __device__ __forceinline__ Word word(uint32_t wbits, int i) const { return field_word(wbits, field_bits(vel4[i], field)); }
 };
 
-// range[0] / range[1] (field frame only): the bits of lo / hi compose will read -- the fixed range, or the identities of the reduction
-template <class Pay>
-__global__ __launch_bounds__(256) void k_render_clear(typename Pay::Word *__restrict__ least, uint32_t *__restrict__ count, int npix,
-                                                      uint32_t *__restrict__ range, uint32_t lo, uint32_t hi) {
+// One clear for the three frames.  Per pixel: `least` (flat: the depth words) and `wide` (field: the packed words,
+// column: the sums) are set to `empty`, `count` to 0, each where given.  range[0] / range[1] (field): the bits of lo / hi
+// compose will read -- the fixed range, or the identities of the reduction; *maxWord (column): 0
+__global__ __launch_bounds__(256) void k_frame_clear(uint32_t *__restrict__ least, unsigned long long *__restrict__ wide,
+                                                     unsigned long long empty, uint32_t *__restrict__ count, int npix,
+                                                     uint32_t *__restrict__ range, uint32_t lo, uint32_t hi,
+                                                     unsigned long long *__restrict__ maxWord) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < npix) {
-        least[i] = Pay::kEmpty;
-        count[i] = 0u;
+        if (least) least[i] = (uint32_t)empty;
+        if (wide) wide[i] = empty;
+        if (count) count[i] = 0u;
     }
-    if (Pay::kRange && i == 0) {
-        range[0] = lo;
-        range[1] = hi;
+    if (i == 0) {
+        if (range) {
+            range[0] = lo;
+            range[1] = hi;
+        }
+        if (maxWord) *maxWord = 0ull;
     }
 }
 
@@ -101,52 +106,105 @@ __device__ __forceinline__ void splat_hits(const RenderParams &R, int px, int py
         }
 }
 
-// the check path (SPH_RENDER_PLAIN=1): one thread per particle, one atomic per hit and buffer
+// A frame policy is what k_frame_tile / k_frame_plain need of a frame: the item of a row (one that covers nothing for
+// a row off screen), its pixel box, the hit loop of an item into a target -- the global buffers (0, 0, width), or the
+// workgroup's tile over the rectangle that starts at (x0, y0) and is `pitch` wide --, clear / touched / flush for one
+// tile entry, and the check path's row.  kMargin: the hull of the boxes still has to be widened by the radius and clipped.
 template <class Pay>
-__global__ __launch_bounds__(256) void k_splat_plain(const float4 *__restrict__ pos4, int n, RenderParams R, Pay pay,
-                                                     uint32_t *__restrict__ count) {
+struct SplatFrame {
+    using Word = typename Pay::Word;
+    static constexpr int kNowhere = -0x40000000; // px of no particle, or of one whose square misses the viewport: covers nothing
+    static constexpr bool kMargin = true;        // the boxes are the particles' centres
+    struct Item {
+        int px, py;
+        Word word;
+    };
+    struct Target {
+        uint32_t *count;
+        Word *least;
+    };
+    struct Tile {
+        Word least[kTilePixels];
+        uint32_t count[kTilePixels];
+        __device__ __forceinline__ Target target() { return {count, least}; }
+    };
+    Pay pay;
+    uint32_t *count;
+
+    __device__ __forceinline__ Target global() const { return {count, pay.least}; }
+    __device__ __forceinline__ Item none() const { return {kNowhere, kNowhere, Pay::kEmpty}; }
+    __device__ __forceinline__ Item item(const float4 p, int i, const RenderParams &R) const {
+        const Pixel q = project(p.x, p.y, p.z, R);
+        const int r = R.radius;
+        Item it = none();
+        // a centre whose square misses the viewport draws nothing and must not stretch the rectangle
+        if (q.px + r >= 0 && q.px - r < R.width && q.py + r >= 0 && q.py - r < R.height) it = {q.px, q.py, pay.word(q.wbits, i)};
+        return it;
+    }
+    __device__ __forceinline__ bool box(const Item &q, int &x0, int &y0, int &x1, int &y1) const {
+        x0 = x1 = q.px;
+        y0 = y1 = q.py;
+        return q.px != kNowhere;
+    }
+    __device__ __forceinline__ void hits(const Item &q, const RenderParams &R, Target T, int x0, int y0, int pitch) const {
+        if (q.px != kNowhere) splat_hits(R, q.px, q.py, q.word, T.count, T.least, x0, y0, pitch);
+    }
+    // the check path's row: no test against the viewport beside the clipping of the hit loop itself
+    __device__ __forceinline__ void plain(const float4 p, int i, const RenderParams &R) const {
+        const Pixel q = project(p.x, p.y, p.z, R);
+        splat_hits(R, q.px, q.py, pay.word(q.wbits, i), count, pay.least, 0, 0, R.width);
+    }
+    __device__ __forceinline__ void clear(Target T, int e) const {
+        T.count[e] = 0u;
+        T.least[e] = Pay::kEmpty;
+    }
+    __device__ __forceinline__ bool touched(Target T, int e) const { return T.count[e] != 0u; }
+    __device__ __forceinline__ void flush(Target T, int e, int g) const {
+        atomicAdd(&count[g], T.count[e]);
+        // The word only ever decreases during the splat, so whatever value a plain (aligned, single) load returns,
+        // however stale, is >= the final one: if it is already <= ours, ours cannot change the result.
+        const Word m = T.least[e];
+        if (pay.least[g] > m) atomicMin(&pay.least[g], m);
+    }
+};
+
+// Both kernels take a policy's two members -- its parameters and its global buffer -- as kernel arguments of their own
+// and put the policy together again: the fields of one by-value argument are loaded where they are first used, which in
+// the tile kernel is behind the barriers (the column frame: +1 %).
+// The check path (SPH_RENDER_PLAIN=1): one thread per particle, one global atomic per hit and buffer
+template <class Frame, class Part, class Word>
+__global__ __launch_bounds__(256) void k_frame_plain(const float4 *__restrict__ pos4, int n, RenderParams R, Part part,
+                                                     Word *__restrict__ buffer) {
+    const Frame F{part, buffer};
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const float4 p = pos4[i];
-    const Pixel q = project(p.x, p.y, p.z, R);
-    splat_hits(R, q.px, q.py, pay.word(q.wbits, i), count, pay.least, 0, 0, R.width);
+    F.plain(pos4[i], i, R);
 }
 
-template <class Pay>
-__global__ __launch_bounds__(kSplatThreads) void k_splat_tile(const float4 *__restrict__ pos4, int n, RenderParams R, Pay pay,
-                                                              uint32_t *__restrict__ count) {
-    using Word = typename Pay::Word;
-    constexpr int kNowhere = -0x40000000; // px of no particle, or of one whose square misses the viewport: covers nothing
-    __shared__ Word tLeast[kTilePixels];
-    __shared__ uint32_t tCount[kTilePixels];
-    __shared__ int box[4]; // min x, min y, max x, max y over the workgroup's particle centres
+template <class Frame, class Part, class Word>
+__global__ __launch_bounds__(kSplatThreads) void k_frame_tile(const float4 *__restrict__ pos4, int n, RenderParams R, Part part,
+                                                              Word *__restrict__ buffer) {
+    const Frame F{part, buffer};
+    __shared__ typename Frame::Tile tile;
+    __shared__ int box[4]; // min x, min y, max x, max y over the boxes of the workgroup's items
     const int t = threadIdx.x;
     const int base = blockIdx.x * kSplatBlock;
-    const int r = R.radius;
     if (t < 2) box[t] = 0x7fffffff;
     else if (t < 4) box[t] = -0x7fffffff;
 
-    int qx[kSplatPerThread], qy[kSplatPerThread];
-    Word qw[kSplatPerThread];
+    typename Frame::Item q[kSplatPerThread];
     int lox = 0x7fffffff, loy = 0x7fffffff, hix = -0x7fffffff, hiy = -0x7fffffff;
 #pragma unroll
     for (int k = 0; k < kSplatPerThread; ++k) {
         const int i = base + k * kSplatThreads + t;
-        qx[k] = qy[k] = kNowhere;
-        qw[k] = Pay::kEmpty;
-        if (i < n) {
-            const float4 p = pos4[i];
-            const Pixel q = project(p.x, p.y, p.z, R);
-            // a centre whose square misses the viewport draws nothing and must not stretch the rectangle
-            if (q.px + r >= 0 && q.px - r < R.width && q.py + r >= 0 && q.py - r < R.height) {
-                qx[k] = q.px;
-                qy[k] = q.py;
-                qw[k] = pay.word(q.wbits, i);
-                lox = min(lox, q.px);
-                hix = max(hix, q.px);
-                loy = min(loy, q.py);
-                hiy = max(hiy, q.py);
-            }
+        q[k] = F.none();
+        if (i < n) q[k] = F.item(pos4[i], i, R);
+        int bx0, by0, bx1, by1;
+        if (F.box(q[k], bx0, by0, bx1, by1)) {
+            lox = min(lox, bx0);
+            hix = max(hix, bx1);
+            loy = min(loy, by0);
+            hiy = max(hiy, by1);
         }
     }
     lox = wave_min_i32(lox);
@@ -162,39 +220,32 @@ __global__ __launch_bounds__(kSplatThreads) void k_splat_tile(const float4 *__re
     }
     __syncthreads();
     if (box[2] < box[0]) return; // nothing of this workgroup is on screen (uniform)
-    const int x0 = max(box[0] - r, 0), y0 = max(box[1] - r, 0);
-    const int x1 = min(box[2] + r, R.width - 1), y1 = min(box[3] + r, R.height - 1);
+    int x0 = box[0], y0 = box[1], x1 = box[2], y1 = box[3];
+    if (Frame::kMargin) { // (a hull of footprints is clipped already)
+        x0 = max(x0 - R.radius, 0), y0 = max(y0 - R.radius, 0);
+        x1 = min(x1 + R.radius, R.width - 1), y1 = min(y1 + R.radius, R.height - 1);
+    }
     const int bw = x1 - x0 + 1, bh = y1 - y0 + 1;
     const long long area = (long long)bw * bh;
 
     if (area > kTilePixels) { // (uniform) the rectangle does not fit: per-hit global atomics
 #pragma unroll
-        for (int k = 0; k < kSplatPerThread; ++k)
-            if (qx[k] != kNowhere) splat_hits(R, qx[k], qy[k], qw[k], count, pay.least, 0, 0, R.width);
+        for (int k = 0; k < kSplatPerThread; ++k) F.hits(q[k], R, F.global(), 0, 0, R.width);
         return;
     }
 
-    const int tile = (int)area;
-    for (int e = t; e < tile; e += kSplatThreads) {
-        tCount[e] = 0u;
-        tLeast[e] = Pay::kEmpty;
-    }
+    const auto T = tile.target();
+    const int entries = (int)area;
+    for (int e = t; e < entries; e += kSplatThreads) F.clear(T, e);
     __syncthreads();
-    // (every pixel of a clipped square lies inside [x0, x1] x [y0, y1] by construction)
+    // (every hit of an item lies inside its box, widened by the margin: inside [x0, x1] x [y0, y1] by construction)
 #pragma unroll
-    for (int k = 0; k < kSplatPerThread; ++k)
-        if (qx[k] != kNowhere) splat_hits(R, qx[k], qy[k], qw[k], tCount, tLeast, x0, y0, bw);
+    for (int k = 0; k < kSplatPerThread; ++k) F.hits(q[k], R, T, x0, y0, bw);
     __syncthreads();
-    for (int e = t; e < tile; e += kSplatThreads) {
-        const uint32_t c = tCount[e];
-        if (c == 0u) continue;
+    for (int e = t; e < entries; e += kSplatThreads) {
+        if (!F.touched(T, e)) continue;
         const int ey = e / bw;
-        const int g = (y0 + ey) * R.width + x0 + (e - ey * bw);
-        atomicAdd(&count[g], c);
-        // The word only ever decreases during the splat, so whatever value a plain (aligned, single) load returns,
-        // however stale, is >= the final one: if it is already <= ours, ours cannot change the result.
-        const Word m = tLeast[e];
-        if (pay.least[g] > m) atomicMin(&pay.least[g], m);
+        F.flush(T, e, (y0 + ey) * R.width + x0 + (e - ey * bw));
     }
 }
 
@@ -224,31 +275,39 @@ __device__ __forceinline__ uint32_t pixel_rgb(uint32_t d, uint32_t c, uint32_t e
     return (32u * L) | ((32u * L) << 8) | 0xFF0000u;
 }
 
-// automatic range: minimum and maximum of the bit patterns of s over ALL n rows (s >= +0: bit order = value order);
-// wave64 shuffles, one LDS step across the four waves, then at most one atomic per workgroup and word
+// The range reductions.  block_fold: v over the workgroup -- wave64 shuffles, then one LDS step across the four waves --
+// for thread 0; one call per instantiation and kernel (nothing keeps a second call's writes to `part` behind this one's
+// reads).  settle: that value into *word with at most one atomic per workgroup: *word only moves one way while
+// the kernel runs, so a plain load that already is past ours, however stale, settles it.
+template <bool kMax, class T>
+__device__ __forceinline__ T block_fold(T v) {
+    __shared__ T part[4];
+    auto pick = [](T a, T b) { return kMax ? max(a, b) : min(a, b); };
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = pick(v, (T)__shfl_xor(v, off));
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return pick(pick(part[0], part[1]), pick(part[2], part[3]));
+}
+template <bool kMax, class T>
+__device__ __forceinline__ void settle(T *word, T v) {
+    if (kMax ? *word < v : *word > v) kMax ? atomicMax(word, v) : atomicMin(word, v);
+}
+
+// automatic range: minimum and maximum of the bit patterns of s over ALL n rows (s >= +0: bit order = value order)
 __global__ __launch_bounds__(256) void k_field_range(const float4 *__restrict__ vel4, int n, int field,
                                                      uint32_t *__restrict__ range) {
-    __shared__ uint32_t wlo[4], whi[4];
     uint32_t lo = 0xFFFFFFFFu, hi = 0u;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
         const uint32_t b = field_bits(vel4[i], field);
         lo = min(lo, b);
         hi = max(hi, b);
     }
-    // (the helpers compare signed values: flip the top bit around them)
-    lo = (uint32_t)wave_min_i32((int)(lo ^ 0x80000000u)) ^ 0x80000000u;
-    hi = (uint32_t)wave_max_i32((int)(hi ^ 0x80000000u)) ^ 0x80000000u;
-    if ((threadIdx.x & 63) == 0) {
-        wlo[threadIdx.x >> 6] = lo;
-        whi[threadIdx.x >> 6] = hi;
-    }
-    __syncthreads();
+    lo = block_fold<false>(lo);
+    hi = block_fold<true>(hi);
     if (threadIdx.x == 0) {
-        lo = min(min(wlo[0], wlo[1]), min(wlo[2], wlo[3]));
-        hi = max(max(whi[0], whi[1]), max(whi[2], whi[3]));
-        // (lo only falls and hi only rises: a stale load that already is past ours settles it)
-        if (range[0] > lo) atomicMin(&range[0], lo);
-        if (range[1] < hi) atomicMax(&range[1], hi);
+        settle<false>(&range[0], lo);
+        settle<true>(&range[1], hi);
     }
 }
 
@@ -335,13 +394,6 @@ __global__ __launch_bounds__(256) void k_column_rays(RenderParams R, float *__re
     else if (i < R.width + R.height) rays[i] = 2.f * ((((float)(R.height - 1 - (i - R.width)) + 0.5f) / (0.5f * R.Hf)) - 1.f);
 }
 
-__global__ __launch_bounds__(256) void k_column_clear(unsigned long long *__restrict__ column, int npix,
-                                                      unsigned long long *__restrict__ maxWord) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < npix) column[i] = 0ull;
-    if (i == 0) *maxWord = 0ull;
-}
-
 // the term of a pair with a2 = h h - b2 > 0
 __device__ __forceinline__ unsigned long long column_term(float a2, float dcoef) {
     const float c = (SPH_MASS * (((dcoef * a2) * a2) * a2)) * ((32.f / 35.f) * sqrtf(a2));
@@ -406,96 +458,45 @@ __device__ __forceinline__ void column_hits(const Footprint &f, const RenderPara
     }
 }
 
-// the check path (SPH_RENDER_PLAIN=1): one thread per particle, one global atomic per contributing pixel
-__global__ __launch_bounds__(256) void k_column_plain(const float4 *__restrict__ pos4, int n, RenderParams R, ColumnParams C,
-                                                      unsigned long long *__restrict__ column) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const Footprint f = column_footprint(pos4[i], R, C.h);
-    column_hits(f, R, C, [&](int c, int r, unsigned long long q) { atomicAdd(&column[r * R.width + c], q); });
-}
+struct ColumnFrame {
+    static constexpr bool kMargin = false; // the boxes are the footprints, clipped already
+    using Item = Footprint;
+    using Target = unsigned long long *;
+    struct Tile {
+        unsigned long long sum[kTilePixels];
+        __device__ __forceinline__ Target target() { return sum; }
+    };
+    ColumnParams C;
+    unsigned long long *column;
 
-// k_splat_tile's scheme over the hull of the workgroup's FOOTPRINTS: LDS atomics into a 64 KB tile of 64-bit sums,
-// then one global atomic per touched pixel; a hull that does not fit the tile: per-hit global atomics
-__global__ __launch_bounds__(kSplatThreads) void k_column_tile(const float4 *__restrict__ pos4, int n, RenderParams R, ColumnParams C,
-                                                               unsigned long long *__restrict__ column) {
-    __shared__ unsigned long long tile[kTilePixels];
-    __shared__ int box[4]; // min column, min row, max column, max row over the workgroup's footprints
-    const int t = threadIdx.x;
-    const int base = blockIdx.x * kSplatBlock;
-    if (t < 2) box[t] = 0x7fffffff;
-    else if (t < 4) box[t] = -0x7fffffff;
-
-    Footprint f[kSplatPerThread];
-    int lox = 0x7fffffff, loy = 0x7fffffff, hix = -0x7fffffff, hiy = -0x7fffffff;
-#pragma unroll
-    for (int k = 0; k < kSplatPerThread; ++k) {
-        const int i = base + k * kSplatThreads + t;
-        f[k].c0 = f[k].r0 = 0;
-        f[k].c1 = f[k].r1 = -1;
-        if (i < n) f[k] = column_footprint(pos4[i], R, C.h);
-        if (f[k].c1 >= f[k].c0) {
-            lox = min(lox, f[k].c0);
-            hix = max(hix, f[k].c1);
-            loy = min(loy, f[k].r0);
-            hiy = max(hiy, f[k].r1);
-        }
+    __device__ __forceinline__ Target global() const { return column; }
+    __device__ __forceinline__ Item none() const {
+        Footprint f;
+        f.c0 = f.r0 = 0;
+        f.c1 = f.r1 = -1;
+        return f;
     }
-    lox = wave_min_i32(lox);
-    loy = wave_min_i32(loy);
-    hix = wave_max_i32(hix);
-    hiy = wave_max_i32(hiy);
-    __syncthreads();
-    if ((t & 63) == 0) {
-        atomicMin(&box[0], lox);
-        atomicMin(&box[1], loy);
-        atomicMax(&box[2], hix);
-        atomicMax(&box[3], hiy);
+    __device__ __forceinline__ Item item(const float4 p, int, const RenderParams &R) const { return column_footprint(p, R, C.h); }
+    __device__ __forceinline__ bool box(const Item &f, int &x0, int &y0, int &x1, int &y1) const {
+        x0 = f.c0, y0 = f.r0, x1 = f.c1, y1 = f.r1;
+        return f.c1 >= f.c0;
     }
-    __syncthreads();
-    if (box[2] < box[0]) return; // nothing of this workgroup is on screen (uniform)
-    const int x0 = box[0], y0 = box[1];
-    const int bw = box[2] - x0 + 1, bh = box[3] - y0 + 1;
-    const long long area = (long long)bw * bh;
-
-    if (area > kTilePixels) { // (uniform)
-#pragma unroll
-        for (int k = 0; k < kSplatPerThread; ++k)
-            column_hits(f[k], R, C, [&](int c, int r, unsigned long long q) { atomicAdd(&column[r * R.width + c], q); });
-        return;
+    __device__ __forceinline__ void hits(const Item &f, const RenderParams &R, Target T, int x0, int y0, int pitch) const {
+        column_hits(f, R, C, [&](int c, int r, unsigned long long q) { atomicAdd(&T[(r - y0) * pitch + (c - x0)], q); });
     }
+    __device__ __forceinline__ void plain(const float4 p, int i, const RenderParams &R) const { hits(item(p, i, R), R, column, 0, 0, R.width); }
+    __device__ __forceinline__ void clear(Target T, int e) const { T[e] = 0ull; }
+    __device__ __forceinline__ bool touched(Target T, int e) const { return T[e] != 0ull; }
+    __device__ __forceinline__ void flush(Target T, int e, int g) const { atomicAdd(&column[g], T[e]); }
+};
 
-    const int area32 = (int)area;
-    for (int e = t; e < area32; e += kSplatThreads) tile[e] = 0ull;
-    __syncthreads();
-    // (every footprint lies inside the hull [x0, x0 + bw) x [y0, y0 + bh) by construction)
-#pragma unroll
-    for (int k = 0; k < kSplatPerThread; ++k)
-        column_hits(f[k], R, C, [&](int c, int r, unsigned long long q) { atomicAdd(&tile[(r - y0) * bw + (c - x0)], q); });
-    __syncthreads();
-    for (int e = t; e < area32; e += kSplatThreads) {
-        const unsigned long long v = tile[e];
-        if (v == 0ull) continue;
-        const int ey = e / bw;
-        atomicAdd(&column[(y0 + ey) * R.width + x0 + (e - ey * bw)], v);
-    }
-}
-
-// automatic range: the largest column word (the value is monotonic in the word); wave64 shuffles, one LDS step
-// across the four waves, then at most one atomic per workgroup
+// automatic range: the largest column word (the value is monotonic in the word)
 __global__ __launch_bounds__(256) void k_column_max(const unsigned long long *__restrict__ column, int npix,
                                                     unsigned long long *__restrict__ maxWord) {
-    __shared__ unsigned long long whi[4];
     unsigned long long hi = 0ull;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < npix; i += gridDim.x * 256) hi = max(hi, column[i]);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) hi = max(hi, (unsigned long long)__shfl_xor(hi, off));
-    if ((threadIdx.x & 63) == 0) whi[threadIdx.x >> 6] = hi;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        hi = max(max(whi[0], whi[1]), max(whi[2], whi[3]));
-        if (*maxWord < hi) atomicMax(maxWord, hi); // (it only rises: a stale load that already is past ours settles it)
-    }
+    hi = block_fold<true>(hi);
+    if (threadIdx.x == 0) settle<true>(maxWord, hi);
 }
 
 // one round-to-nearest-even conversion of the 64-bit word, then an exact scaling by 2^-32
@@ -523,12 +524,15 @@ __global__ __launch_bounds__(256) void k_column_compose(const unsigned long long
     });
 }
 
-template <class Pay>
-void launch_splat(const RenderParams &R, const float4 *pos4, int n, bool plain, Pay pay, uint32_t *count, hipStream_t s) {
+template <class Frame>
+void launch_splat(const RenderParams &R, const float4 *pos4, int n, bool plain, Frame F, hipStream_t s) {
     if (n <= 0) return;
-    if (plain) k_splat_plain<<<(n + 255) / 256, 256, 0, s>>>(pos4, n, R, pay, count);
-    else k_splat_tile<<<(n + kSplatBlock - 1) / kSplatBlock, kSplatThreads, 0, s>>>(pos4, n, R, pay, count);
+    const auto [part, buffer] = F;
+    if (plain) k_frame_plain<Frame><<<(n + 255) / 256, 256, 0, s>>>(pos4, n, R, part, buffer);
+    else k_frame_tile<Frame><<<(n + kSplatBlock - 1) / kSplatBlock, kSplatThreads, 0, s>>>(pos4, n, R, part, buffer);
 }
+
+int blocks_of(int items) { return (items + 255) / 256; }
 
 } // namespace
 
@@ -538,44 +542,35 @@ void sph_launch_render_edges(const RenderParams &R, uint32_t *edge, hipStream_t 
     k_render_edges<<<(12 * 4096) / 256, 256, 0, s>>>(R, edge);
 }
 
-void sph_launch_render(const RenderParams &R, const float4 *pos4, int n, bool plain, uint32_t *depth, uint32_t *count,
-                       const uint32_t *edge, uint32_t *rgb, hipStream_t s) {
-    const int npix = R.width * R.height;
-    k_render_clear<FlatPayload><<<(npix + 255) / 256, 256, 0, s>>>(depth, count, npix, nullptr, 0u, 0u);
-    launch_splat(R, pos4, n, plain, FlatPayload{depth}, count, s);
-    const int quads = (npix + 3) / 4;
-    k_render_compose<<<(quads + 255) / 256, 256, 0, s>>>(depth, count, edge, npix, R.shade, rgb);
-}
-
 void sph_launch_column_rays(const RenderParams &R, float *rays, hipStream_t s) {
-    k_column_rays<<<(R.width + R.height + 255) / 256, 256, 0, s>>>(R, rays);
+    k_column_rays<<<blocks_of(R.width + R.height), 256, 0, s>>>(R, rays);
 }
 
-void sph_launch_render_column(const RenderParams &R, const float4 *pos4, int n, bool plain, float h, float h2, float dcoef,
-                              bool autoRange, float lo, float hi, const float *rays, unsigned long long *column,
-                              unsigned long long *maxWord, const uint32_t *edge, uint32_t *range, uint32_t *rgb, hipStream_t s) {
+void sph_launch_render(const RenderParams &R, const FrameView &V, const float4 *pos4, int n, bool plain, hipStream_t s) {
     const int npix = R.width * R.height;
-    const ColumnParams C{h, h2, dcoef, rays};
-    k_column_clear<<<(npix + 255) / 256, 256, 0, s>>>(column, npix, maxWord);
-    if (n > 0) {
-        if (plain) k_column_plain<<<(n + 255) / 256, 256, 0, s>>>(pos4, n, R, C, column);
-        else k_column_tile<<<(n + kSplatBlock - 1) / kSplatBlock, kSplatThreads, 0, s>>>(pos4, n, R, C, column);
-    }
-    if (autoRange) k_column_max<<<min((npix + 255) / 256, 1024), 256, 0, s>>>(column, npix, maxWord);
-    const int quads = (npix + 3) / 4;
-    k_column_compose<<<(quads + 255) / 256, 256, 0, s>>>(column, edge, autoRange ? maxWord : nullptr, lo, hi, npix, range, rgb);
+    k_frame_clear<<<blocks_of(npix), 256, 0, s>>>(V.depth, nullptr, FlatPayload::kEmpty, V.count, npix, nullptr, 0u, 0u, nullptr);
+    launch_splat(R, pos4, n, plain, SplatFrame<FlatPayload>{{V.depth}, V.count}, s);
+    k_render_compose<<<blocks_of((npix + 3) / 4), 256, 0, s>>>(V.depth, V.count, V.edge, npix, R.shade, V.rgb);
 }
 
-void sph_launch_render_field(const RenderParams &R, const float4 *pos4, const float4 *vel4, int n, bool plain, int field,
-                            bool autoRange, float lo, float hi, unsigned long long *packed, uint32_t *depth, uint32_t *count,
-                            const uint32_t *edge, uint32_t *range, uint32_t *rgb, hipStream_t s) {
+void sph_launch_render_field(const RenderParams &R, const FrameView &V, const float4 *pos4, const float4 *vel4, int n, bool plain,
+                             int field, bool autoRange, float lo, float hi, hipStream_t s) {
     const int npix = R.width * R.height;
     const bool reduce = autoRange && n > 0;
-    k_render_clear<FieldPayload><<<(npix + 255) / 256, 256, 0, s>>>(packed, count, npix, range,
-                                                                   reduce ? 0xFFFFFFFFu : __builtin_bit_cast(uint32_t, lo),
-                                                                   reduce ? 0u : __builtin_bit_cast(uint32_t, hi));
-    if (reduce) k_field_range<<<min((n + 255) / 256, 1024), 256, 0, s>>>(vel4, n, field, range);
-    launch_splat(R, pos4, n, plain, FieldPayload{packed, vel4, field}, count, s);
-    const int quads = (npix + 3) / 4;
-    k_field_compose<<<(quads + 255) / 256, 256, 0, s>>>(packed, count, edge, range, npix, depth, rgb);
+    k_frame_clear<<<blocks_of(npix), 256, 0, s>>>(nullptr, V.packed, FieldPayload::kEmpty, V.count, npix, V.range,
+                                                  reduce ? 0xFFFFFFFFu : __builtin_bit_cast(uint32_t, lo),
+                                                  reduce ? 0u : __builtin_bit_cast(uint32_t, hi), nullptr);
+    if (reduce) k_field_range<<<min(blocks_of(n), 1024), 256, 0, s>>>(vel4, n, field, V.range);
+    launch_splat(R, pos4, n, plain, SplatFrame<FieldPayload>{{V.packed, vel4, field}, V.count}, s);
+    k_field_compose<<<blocks_of((npix + 3) / 4), 256, 0, s>>>(V.packed, V.count, V.edge, V.range, npix, V.depth, V.rgb);
+}
+
+void sph_launch_render_column(const RenderParams &R, const FrameView &V, const float4 *pos4, int n, bool plain, float h, float h2,
+                              float dcoef, bool autoRange, float lo, float hi, hipStream_t s) {
+    const int npix = R.width * R.height;
+    k_frame_clear<<<blocks_of(npix), 256, 0, s>>>(nullptr, V.packed, 0ull, nullptr, npix, nullptr, 0u, 0u, V.maxWord);
+    launch_splat(R, pos4, n, plain, ColumnFrame{{h, h2, dcoef, V.rays}, V.packed}, s);
+    if (autoRange) k_column_max<<<min(blocks_of(npix), 1024), 256, 0, s>>>(V.packed, npix, V.maxWord);
+    k_column_compose<<<blocks_of((npix + 3) / 4), 256, 0, s>>>(V.packed, V.edge, autoRange ? V.maxWord : nullptr, lo, hi, npix,
+                                                             V.range, V.rgb);
 }

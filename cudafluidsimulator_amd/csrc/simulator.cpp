@@ -122,43 +122,34 @@ void Simulator::simulateAndTime(Times *times) {
     check(impl, sph_step(impl, reinterpret_cast<SphTimes *>(times)), "sph_step");
 }
 
-const unsigned char *Simulator::renderFrame(int *width, int *height) {
+// what the three render* methods share: `render` queues the frame on the single-domain handle; the frame in pinned memory
+template <class Render>
+static const unsigned char *rendered(const char *method, bool multi, sph_handle *impl, int *width, int *height, const char *call,
+                                     Render render) {
     if (multi) {
-        fprintf(stderr, "sph: renderFrame: frames of a multi-GPU run (SPH_GPUS > 1) are not rendered\n");
+        fprintf(stderr, "sph: %s: frames of a multi-GPU run (SPH_GPUS > 1) are not rendered\n", method);
         return NULL;
     }
     if (!impl) return NULL;
-    check(impl, sph_render_frame(impl, NULL), "sph_render_frame");
+    check(impl, render(), call);
     const unsigned char *f = sph_frame_host(impl, width, height);
     if (!f) check(impl, SPH_EHIP, "sph_frame_host");
     return f;
+}
+
+const unsigned char *Simulator::renderFrame(int *width, int *height) {
+    return rendered("renderFrame", multi, impl, width, height, "sph_render_frame", [&] { return sph_render_frame(impl, NULL); });
 }
 
 const unsigned char *Simulator::renderField(int field, int *width, int *height) {
-    if (multi) {
-        fprintf(stderr, "sph: renderField: frames of a multi-GPU run (SPH_GPUS > 1) are not rendered\n");
-        return NULL;
-    }
-    if (!impl) return NULL;
     SphFieldFrameOptions o{};
     o.struct_size = (int32_t)sizeof o;
     o.field = field;
-    check(impl, sph_render_field(impl, &o), "sph_render_field");
-    const unsigned char *f = sph_frame_host(impl, width, height);
-    if (!f) check(impl, SPH_EHIP, "sph_frame_host");
-    return f;
+    return rendered("renderField", multi, impl, width, height, "sph_render_field", [&] { return sph_render_field(impl, &o); });
 }
 
 const unsigned char *Simulator::renderColumn(int *width, int *height) {
-    if (multi) {
-        fprintf(stderr, "sph: renderColumn: frames of a multi-GPU run (SPH_GPUS > 1) are not rendered\n");
-        return NULL;
-    }
-    if (!impl) return NULL;
-    check(impl, sph_render_column(impl, NULL), "sph_render_column");
-    const unsigned char *f = sph_frame_host(impl, width, height);
-    if (!f) check(impl, SPH_EHIP, "sph_frame_host");
-    return f;
+    return rendered("renderColumn", multi, impl, width, height, "sph_render_column", [&] { return sph_render_column(impl, NULL); });
 }
 
 const float *Simulator::sampleField(int field, const float origin[3], const float spacing[3], int nx, int ny, int nz) {

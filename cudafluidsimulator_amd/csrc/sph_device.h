@@ -227,25 +227,29 @@ struct RenderParams {
 };
 // the static layer: 12 box edges x 4096 samples, minimum depth bits per pixel (clears `edge` first)
 void sph_launch_render_edges(const RenderParams &R, uint32_t *edge, hipStream_t s);
-// clear + splat of pos4[0, n) + compose into rgb (3 bytes per pixel, padded to a multiple of 4 pixels);
-// plain = the one-atomic-per-hit check path
-void sph_launch_render(const RenderParams &R, const float4 *pos4, int n, bool plain, uint32_t *depth, uint32_t *count,
-                       const uint32_t *edge, uint32_t *rgb, hipStream_t s);
-// The field frame: clear + (autoRange: min / max of the field over vel4[0, n) into range[0..1], else the bits of
-// lo / hi) + splat of (pos4, vel4)[0, n) into `packed` (depth bits << 32 | value bits) and `count` + compose into
-// rgb, which also leaves the depth words in `depth`.  field = SPH_FIELD_*.
-void sph_launch_render_field(const RenderParams &R, const float4 *pos4, const float4 *vel4, int n, bool plain, int field,
-                            bool autoRange, float lo, float hi, unsigned long long *packed, uint32_t *depth, uint32_t *count,
-                            const uint32_t *edge, uint32_t *range, uint32_t *rgb, hipStream_t s);
-
-// The column frame.  rays: the pixel-centre rays of a width x height image, ax of column c
-// at [c], ay of row r at [width + r] (built once per image size, like the edge layer).
+// The frame's device buffers, as the three launchers below take them: filled by frame_view() (sph_frame.hip) and by
+// nobody else; null while no frame that needs the buffer was asked for
+struct FrameView {
+    uint32_t *depth, *count;     // per pixel, of the flat and field frames
+    const uint32_t *edge;        // the static layer
+    uint32_t *rgb;               // 3 bytes per pixel, padded to a multiple of 4 pixels
+    unsigned long long *packed;  // per pixel: the field frame's (depth bits << 32 | value bits), the column frame's sum
+    uint32_t *range;             // the bits of lo and hi of the colour scale
+    unsigned long long *maxWord; // the largest column word
+    const float *rays;           // sph_launch_column_rays' table
+};
+// The pixel-centre rays of a width x height image: ax of column c at [c], ay of row r at
+// [width + r] (built once per image size, like the edge layer).
 void sph_launch_column_rays(const RenderParams &R, float *rays, hipStream_t s);
-// clear + splat of pos4[0, n) into `column` (one 64-bit sum per pixel) + (autoRange: the largest word into *maxWord)
-// + compose into rgb, which also leaves the bits of the range used in range[0..1].  h2, dcoef: the handle's settings.
-void sph_launch_render_column(const RenderParams &R, const float4 *pos4, int n, bool plain, float h, float h2, float dcoef,
-                              bool autoRange, float lo, float hi, const float *rays, unsigned long long *column,
-                              unsigned long long *maxWord, const uint32_t *edge, uint32_t *range, uint32_t *rgb, hipStream_t s);
+// Each: clear + splat of pos4[0, n) + compose into V.rgb; plain = the one-atomic-per-hit check path.  Field frame:
+// autoRange: min / max of the field (SPH_FIELD_*) over vel4[0, n) into V.range, else the bits of lo / hi; its compose
+// also leaves the depth words in V.depth.  Column frame: h, h2, dcoef: the handle's settings; autoRange: from 0 to the
+// largest column (V.maxWord), else lo / hi; its compose leaves the bits of the range used in V.range.
+void sph_launch_render(const RenderParams &R, const FrameView &V, const float4 *pos4, int n, bool plain, hipStream_t s);
+void sph_launch_render_field(const RenderParams &R, const FrameView &V, const float4 *pos4, const float4 *vel4, int n, bool plain,
+                             int field, bool autoRange, float lo, float hi, hipStream_t s);
+void sph_launch_render_column(const RenderParams &R, const FrameView &V, const float4 *pos4, int n, bool plain, float h, float h2,
+                              float dcoef, bool autoRange, float lo, float hi, hipStream_t s);
 
 // The bits of the field frame's scalar of a row, from the (vx, vy, vz, rho) sph_download_state
 // reads: what the field frame colours by and the diagnostics reduce.  fp32, every operation rounded on its own.

@@ -104,6 +104,25 @@ struct Pass {
 // What the last render drew (sph_frame.hip): decides which buffers hold a result and who may read them
 enum class FrameKind { Flat, Field, Column };
 
+// The visualiser's frame (sph_frame.hip; kernels: render.hip).  The first render of an image size allocates the
+// per-pixel depth bits, hit count and static box-edge layer and the RGB8 frame, on the device and in pinned memory.
+// The first field or column frame of that size adds `packed` -- the field frame's (depth bits << 32 | value bits)
+// minimum per pixel, the column frame's 64-bit sum -- and the two words of the colour scale's range, which leave for
+// pinned memory with the frame; the first column frame the word of the largest column and the table of the
+// pixel-centre rays.
+struct FrameState {
+    RenderParams rp{}; // size / point radius / shade of the last render (width 0: none yet)
+    DeviceBuf<uint32_t> depth, count, edge, rgb;
+    PinnedBuf<uint8_t> host;
+    Pass pass; // out: the frame (and range) on its way to host / rangeHost; valid: a frame of the size in rp is held
+    DeviceBuf<unsigned long long> packed;
+    DeviceBuf<uint32_t> range;
+    PinnedBuf<uint32_t> rangeHost;
+    DeviceBuf<unsigned long long> maxWord;
+    DeviceBuf<float> rays;
+    FrameKind kind = FrameKind::Flat; // of the last render
+};
+
 // A few 64-bit counters a pass's kernels add to, on the device, with the pinned block they are read through.
 struct CounterBlock {
     explicit CounterBlock(int words) : count(words) {}
@@ -228,23 +247,7 @@ struct sph_handle {
     sph_host::DeviceBuf<int> partTiles; // slab partition: class counts per 1024-particle tile
 
     // ---- sph_frame.hip ----
-    // The visualiser's frame (render.hip), allocated by the first sph_render_frame: per-pixel depth bits,
-    // hit count and the static box-edge layer on the device, the RGB8 frame on the device and in pinned memory.
-    RenderParams rp{};               // size / point radius / shade of the last render (width 0: none yet)
-    sph_host::DeviceBuf<uint32_t> rDepth, rCount, rEdge, rRgb;
-    sph_host::PinnedBuf<uint8_t> frameHost;
-    sph_host::Pass frame;            // out: the frame (a field frame: and its range) on its way to frameHost / rangeHost; valid:
-                                     // the buffers hold a rendered frame of the size in rp; seconds: clear + splat + compose
-    // The field frame (sph_render_field) adds the packed (depth bits << 32 | value bits) minimum per pixel and
-    // the range of the colour scale: two words on the device, copied to pinned memory with the frame.
-    // The column frame (sph_render_column) keeps its 64-bit sum per pixel in the same buffer and sends its range the
-    // same way; it adds the word of the largest column and the table of the pixel-centre rays (per image size).
-    sph_host::DeviceBuf<unsigned long long> rPacked;
-    sph_host::DeviceBuf<uint32_t> rRange;
-    sph_host::PinnedBuf<uint32_t> rangeHost;
-    sph_host::DeviceBuf<unsigned long long> rColumnMax;
-    sph_host::DeviceBuf<float> rRays;
-    sph_host::FrameKind frameKind = sph_host::FrameKind::Flat; // of the last render
+    sph_host::FrameState frame;
 
     // ---- sph_sample.hip ----
     // The field sample (sample.hip): one float per lattice point on the device and in pinned memory, both grown

@@ -184,14 +184,24 @@ class Simulator:
         o.shade = _lib.SHADES[shade] if isinstance(shade, str) else int(shade)
         self._check(self._L.sph_render_frame(self._h, C.byref(o)), "sph_render_frame")
 
-    def frame_host(self):
-        """(H, W, 3) uint8 view of the last rendered frame, row 0 = top of the window; blocks until
-        it has landed, valid until the next render."""
+    def _frame_size(self):
+        """(pointer, H, W) of the last rendered frame in pinned memory; blocks until it has landed."""
         w, h = C.c_int(0), C.c_int(0)
         p = self._L.sph_frame_host(self._h, C.byref(w), C.byref(h))
         if not p:
             raise SphError("sph_frame_host failed: " + self._L.sph_last_error(self._h).decode())
-        return np.ctypeslib.as_array(p, shape=(h.value, w.value, 3))
+        return p, h.value, w.value
+
+    def _frame_range(self, call, name):
+        lo, hi = C.c_float(0), C.c_float(0)
+        self._check(call(self._h, C.byref(lo), C.byref(hi)), name)
+        return np.float32(lo.value), np.float32(hi.value)
+
+    def frame_host(self):
+        """(H, W, 3) uint8 view of the last rendered frame, row 0 = top of the window; blocks until
+        it has landed, valid until the next render."""
+        p, h, w = self._frame_size()
+        return np.ctypeslib.as_array(p, shape=(h, w, 3))
 
     def render(self, width=0, height=0, point_size=0, shade="flat"):
         """The frame display.cpp would draw (defaults: 800 x 600, points of size 3, flat blue) as an
@@ -202,10 +212,8 @@ class Simulator:
     def frame_buffers(self):
         """depth bits, covering-particle count and box-edge depth bits of the last frame: three
         (H, W) uint32 arrays."""
-        w, h = C.c_int(0), C.c_int(0)
-        if not self._L.sph_frame_host(self._h, C.byref(w), C.byref(h)):
-            raise SphError("sph_frame_host failed: " + self._L.sph_last_error(self._h).decode())
-        out = [np.zeros((h.value, w.value), np.uint32) for _ in range(3)]
+        h, w = self._frame_size()[1:]
+        out = [np.zeros((h, w), np.uint32) for _ in range(3)]
         u32p = C.POINTER(C.c_uint32)
         self._check(self._L.sph_download_frame_buffers(self._h, *[a.ctypes.data_as(u32p) for a in out]),
                     "sph_download_frame_buffers")
@@ -226,19 +234,15 @@ class Simulator:
     def field_buffer(self):
         """(H, W) uint32: the bits of the field value of the particle that colours each pixel of the
         last field frame, 0xFFFFFFFF where none covers it."""
-        w, h = C.c_int(0), C.c_int(0)
-        if not self._L.sph_frame_host(self._h, C.byref(w), C.byref(h)):
-            raise SphError("sph_frame_host failed: " + self._L.sph_last_error(self._h).decode())
-        out = np.zeros((h.value, w.value), np.uint32)
+        h, w = self._frame_size()[1:]
+        out = np.zeros((h, w), np.uint32)
         self._check(self._L.sph_download_field_buffer(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32))),
                     "sph_download_field_buffer")
         return out
 
     def field_range(self):
         """(lo, hi) as np.float32: the colour scale the last field frame used; blocks until it is known."""
-        lo, hi = C.c_float(0), C.c_float(0)
-        self._check(self._L.sph_field_range(self._h, C.byref(lo), C.byref(hi)), "sph_field_range")
-        return np.float32(lo.value), np.float32(hi.value)
+        return self._frame_range(self._L.sph_field_range, "sph_field_range")
 
     # -- the column frame: how much fluid lies behind each pixel (sph_render_column) --
     def render_column(self, lo=0.0, hi=0.0, width=0, height=0):
@@ -253,19 +257,15 @@ class Simulator:
     def column_buffer(self):
         """(H, W) uint64: the column word of each pixel of the last column frame (value = word / 2**32, 0 where
         no particle reaches the pixel's ray)."""
-        w, h = C.c_int(0), C.c_int(0)
-        if not self._L.sph_frame_host(self._h, C.byref(w), C.byref(h)):
-            raise SphError("sph_frame_host failed: " + self._L.sph_last_error(self._h).decode())
-        out = np.zeros((h.value, w.value), np.uint64)
+        h, w = self._frame_size()[1:]
+        out = np.zeros((h, w), np.uint64)
         self._check(self._L.sph_download_column_buffer(self._h, out.ctypes.data_as(C.POINTER(C.c_uint64))),
                     "sph_download_column_buffer")
         return out
 
     def column_range(self):
         """(lo, hi) as np.float32: the colour scale the last column frame used; blocks until it is known."""
-        lo, hi = C.c_float(0), C.c_float(0)
-        self._check(self._L.sph_column_range(self._h, C.byref(lo), C.byref(hi)), "sph_column_range")
-        return np.float32(lo.value), np.float32(hi.value)
+        return self._frame_range(self._L.sph_column_range, "sph_column_range")
 
     def render_time(self, reset=False):
         """(seconds, frames): GPU time of clear + splat + compose summed over `frames` renders."""
