@@ -26,6 +26,7 @@ EXPORTED_SYMBOLS = [
     "sph_render_frame", "sph_frame_host", "sph_download_frame_buffers", "sph_get_render_time", "sph_api_version",
     "sph_render_field", "sph_download_field_buffer", "sph_field_range",
     "sph_render_column", "sph_download_column_buffer", "sph_column_range",
+    "sph_render_liquid", "sph_download_liquid_buffers",
     "sph_sample_field", "sph_sample_host", "sph_get_sample_time",
     "sph_extract_surface", "sph_surface_host", "sph_get_surface_time",
     "sph_diagnose", "sph_diagnostics_host", "sph_diagnostics_values", "sph_diagnostics_add",
@@ -41,6 +42,7 @@ SPH_HAS_FIELD_FRAME = 1
 SPH_FIELD_SPEED, SPH_FIELD_DENSITY, SPH_FIELD_PRESSURE = 0, 1, 2
 FIELDS = {"speed": SPH_FIELD_SPEED, "density": SPH_FIELD_DENSITY, "pressure": SPH_FIELD_PRESSURE}
 SPH_HAS_COLUMN_FRAME = 1
+SPH_HAS_LIQUID_FRAME = 1
 SPH_HAS_FIELD_SAMPLE = 1
 SPH_HAS_SURFACE = 1
 SPH_HAS_DIAGNOSTICS = 1
@@ -91,6 +93,12 @@ class SphFieldFrameOptions(C.Structure):
 class SphColumnFrameOptions(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
                 ("value_lo", C.c_float), ("value_hi", C.c_float)]
+
+
+class SphLiquidFrameOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("radius", C.c_float), ("smooth_iterations", C.c_int32), ("smooth_radius", C.c_int32),
+                ("smooth_depth", C.c_float), ("light", C.c_float * 3), ("thickness_scale", C.c_float)]
 
 
 class SphSampleLattice(C.Structure):
@@ -262,6 +270,8 @@ def load_library():
     L.sph_render_column.argtypes = [hp, C.POINTER(SphColumnFrameOptions)]
     L.sph_download_column_buffer.argtypes = [hp, C.POINTER(C.c_uint64)]
     L.sph_column_range.argtypes = [hp, fp, fp]
+    L.sph_render_liquid.argtypes = [hp, C.POINTER(SphLiquidFrameOptions)]
+    L.sph_download_liquid_buffers.argtypes = [hp, u32p, u32p, fp, C.POINTER(C.c_uint64)]
     L.sph_sample_field.argtypes = [hp, C.POINTER(SphSampleLattice)]
     L.sph_sample_host.argtypes = [hp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.sph_sample_host.restype = fp

@@ -31,13 +31,14 @@ static int env_field(const char *var, const char *instead) {
     return -1;
 }
 
-// SPH_FREE_SHADE: the field that colours the frames, or `column` (kShadeColumn) for column-density frames; unset:
-// the reference's flat blue
-static const int kShadeColumn = 100;
+// SPH_FREE_SHADE: the field that colours the frames, `column` (kShadeColumn) for column-density frames or `liquid`
+// (kShadeLiquid) for the shaded water surface; unset: the reference's flat blue
+static const int kShadeColumn = 100, kShadeLiquid = 101;
 static int shade_field() {
     const char *e = getenv("SPH_FREE_SHADE");
     if (e && !strcmp(e, "column")) return kShadeColumn;
-    return env_field("SPH_FREE_SHADE", "nor column: writing flat frames");
+    if (e && !strcmp(e, "liquid")) return kShadeLiquid;
+    return env_field("SPH_FREE_SHADE", "nor column or liquid: writing flat frames");
 }
 
 // <dir>/<pattern with the frame number f> opened for writing bytes, or NULL after a complaint on stderr
@@ -85,6 +86,7 @@ static bool write_frame(Simulator *simulator, const char *dir, int f, int field)
     int w = 0, h = 0;
     const unsigned char *rgb = field < 0                ? simulator->renderFrame(&w, &h)
                                : field == kShadeColumn ? simulator->renderColumn(&w, &h)
+                               : field == kShadeLiquid ? simulator->renderLiquid(&w, &h)
                                                        : simulator->renderField(field, &w, &h);
     return rgb && write_ppm(dir, "frame_%04d.ppm", f, w, h, rgb);
 }

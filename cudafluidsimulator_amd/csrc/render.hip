@@ -10,7 +10,8 @@
 // does not fit the tile (unsorted state right after an upload, very large images) issues the plain
 // per-hit global atomics instead.  Minimum and sum commute, so every path gives the same buffers.
 // That scheme is written once (k_frame_tile, k_frame_plain) over a frame policy: SplatFrame, the squares of the flat
-// and field frames, and ColumnFrame (section 10h), footprints that vary with depth and a 64-bit integer sum per pixel.
+// and field frames, ColumnFrame (section 10h), footprints that vary with depth and a 64-bit integer sum per pixel, and
+// SphereFrame (section 10i), the same footprints with the minimum of a ray-sphere entry depth per pixel.
 #include "sph_c_api.h"
 #include "sph_device.h"
 
@@ -524,6 +525,212 @@ __global__ __launch_bounds__(256) void k_column_compose(const unsigned long long
     });
 }
 
+// ---- the liquid frame: front surface, smoothing, normals, a lit picture ----
+// Every particle is a sphere of radius r <= h.  On the ray of a pixel the sphere is entered at depth
+// wf = (w + t inv) - sqrtf(a2 inv), a2 = r r - b2 > 0: closest approach minus half the chord, from the quantities of
+// the column frame's test.  The front buffer keeps the minimum of the bits of wf >= 1 (the near plane) per pixel: a
+// minimum of positive floats' bits, so tile, fallback and check path agree like the flat frame's.
+
+struct SphereParams {
+    float r, r2;
+    const float *rays; // k_column_rays' table
+};
+
+struct SphereFrame {
+    static constexpr bool kMargin = false; // the boxes are the footprints, clipped already
+    static constexpr uint32_t kEmpty = 0xFFFFFFFFu;
+    using Item = Footprint;
+    using Target = uint32_t *;
+    struct Tile {
+        uint32_t least[kTilePixels];
+        __device__ __forceinline__ Target target() { return least; }
+    };
+    SphereParams S;
+    uint32_t *front;
+
+    __device__ __forceinline__ Target global() const { return front; }
+    __device__ __forceinline__ Item none() const {
+        Footprint f;
+        f.c0 = f.r0 = 0;
+        f.c1 = f.r1 = -1;
+        return f;
+    }
+    // (a2 > 0 needs b < r: the column frame's bound with r in the place of h)
+    __device__ __forceinline__ Item item(const float4 p, int, const RenderParams &R) const { return column_footprint(p, R, S.r); }
+    __device__ __forceinline__ bool box(const Item &f, int &x0, int &y0, int &x1, int &y1) const {
+        x0 = f.c0, y0 = f.r0, x1 = f.c1, y1 = f.r1;
+        return f.c1 >= f.c0;
+    }
+    // (column_hits' loop with t and inv kept for the depth; written out here so that the column frame's own kernels
+    // compile from the lines they always did)
+    __device__ __forceinline__ void hits(const Item &f, const RenderParams &R, Target T, int x0, int y0, int pitch) const {
+        for (int r = f.r0; r <= f.r1; ++r) {
+            const float ay = S.rays[R.width + r];
+            const float ey = f.Y - ay * f.w;
+            for (int c = f.c0; c <= f.c1; ++c) {
+                const float ax = S.rays[c];
+                const float inv = 1.f / ((1.f + ax * ax) + ay * ay);
+                const float ex = f.X - ax * f.w;
+                const float t = ex * ax + ey * ay;
+                const float b2 = (ex * ex + ey * ey) - (t * t) * inv;
+                const float a2 = S.r2 - b2;
+                if (a2 > 0.f) { // (a NaN is not)
+                    const float wf = (f.w + t * inv) - sqrtf(a2 * inv);
+                    if (wf >= 1.f) atomicMin(&T[(r - y0) * pitch + (c - x0)], __float_as_uint(wf)); // (a NaN is not)
+                }
+            }
+        }
+    }
+    __device__ __forceinline__ void plain(const float4 p, int i, const RenderParams &R) const { hits(item(p, i, R), R, front, 0, 0, R.width); }
+    __device__ __forceinline__ void clear(Target T, int e) const { T[e] = kEmpty; }
+    __device__ __forceinline__ bool touched(Target T, int e) const { return T[e] != kEmpty; }
+    __device__ __forceinline__ void flush(Target T, int e, int g) const {
+        const uint32_t m = T[e]; // (the flat frame's rule: a plain load that already shows a nearer word settles it)
+        if (front[g] > m) atomicMin(&front[g], m);
+    }
+};
+
+// One smoothing iteration: out = the bilateral filter of `in` (both: the bits of a depth per pixel, 0xFFFFFFFF =
+// empty).  A workgroup owns kSmoothW x kSmoothH output pixels, one wave per row, and stages them with a halo of k
+// into LDS once; pixels of the halo outside the viewport are staged as empty.  Every read of the window then has the
+// 64 lanes of a wave on 64 consecutive dwords of one LDS row: lanes l and l + 32 share a bank, which is free, and no
+// two lanes of a 32-lane half do, whatever the pitch 64 + 2k.
+constexpr int kSmoothW = 64, kSmoothH = 4, kSmoothMaxRadius = 7;
+constexpr uint32_t kNoDepth = 0xFFFFFFFFu;
+
+__global__ __launch_bounds__(kSmoothW * kSmoothH) void k_liquid_smooth(const uint32_t *__restrict__ in, uint32_t *__restrict__ out,
+                                                                      int width, int height, int k, float delta) {
+    __shared__ uint32_t win[(kSmoothW + 2 * kSmoothMaxRadius) * (kSmoothH + 2 * kSmoothMaxRadius)];
+    const int t = threadIdx.x;
+    const int x0 = blockIdx.x * kSmoothW, y0 = blockIdx.y * kSmoothH;
+    const int lw = kSmoothW + 2 * k, lh = kSmoothH + 2 * k;
+    for (int e = t; e < lw * lh; e += kSmoothW * kSmoothH) {
+        const int ly = e / lw, lx = e - ly * lw;
+        const int gx = x0 - k + lx, gy = y0 - k + ly;
+        win[e] = (gx >= 0 && gx < width && gy >= 0 && gy < height) ? in[(size_t)gy * width + gx] : kNoDepth;
+    }
+    __syncthreads();
+    const int lx = t & (kSmoothW - 1), ly = t / kSmoothW;
+    const int x = x0 + lx, y = y0 + ly;
+    if (x >= width || y >= height) return;
+    const uint32_t *centre = &win[(ly + k) * lw + (lx + k)];
+    const uint32_t zb = *centre;
+    uint32_t result = zb;
+    if (zb != kNoDepth) {
+        const float zp = __uint_as_float(zb);
+        const float norm = (float)(2 * k * k + 1);
+        float num = 0.f, den = 1.f;
+        for (int dy = -k; dy <= k; ++dy)
+            for (int dx = -k; dx <= k; ++dx) {
+                const uint32_t qb = centre[dy * lw + dx];
+                if (qb == kNoDepth || (dx == 0 && dy == 0)) continue;
+                const float d = __uint_as_float(qb) - zp;
+                const float u = d / delta;
+                const float g = 1.f - u * u;
+                if (g > 0.f) { // (a NaN is not)
+                    const float s = 1.f - (float)(dx * dx + dy * dy) / norm;
+                    const float wgt = (s * s) * (g * g);
+                    num = num + wgt * d;
+                    den = den + wgt;
+                }
+            }
+        result = __float_as_uint(zp + num / den);
+    }
+    out[(size_t)y * width + x] = result;
+}
+
+struct LiquidShade {
+    float light[3];  // as given (compose normalises it)
+    float thickness; // s_ref, used where maxWord is null
+};
+
+struct Vec3 {
+    float x, y, z;
+};
+__device__ __forceinline__ float dot3(Vec3 a, Vec3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+__device__ __forceinline__ Vec3 over_length(Vec3 a) {
+    const float len = sqrtf(dot3(a, a));
+    return {a.x / len, a.y / len, a.z / len};
+}
+__device__ __forceinline__ float at_least_zero(float v) { return v > 0.f ? v : 0.f; } // (a NaN: 0)
+
+// the tangent along one screen axis at a pixel with view-space point P: `ahead` / `behind` are the neighbours' points
+// in the forward and backward direction (valid: inside the viewport and non-empty)
+__device__ __forceinline__ Vec3 liquid_tangent(Vec3 P, bool fwdOk, Vec3 ahead, bool backOk, Vec3 behind, Vec3 none) {
+    const Vec3 fwd = {ahead.x - P.x, ahead.y - P.y, ahead.z - P.z};
+    const Vec3 back = {P.x - behind.x, P.y - behind.y, P.z - behind.z};
+    if (fwdOk && backOk) return fabsf(back.z) < fabsf(fwd.z) ? back : fwd; // (forward on a tie)
+    if (fwdOk) return fwd;
+    if (backOk) return back;
+    return none;
+}
+
+// The lit picture.  depth: the raw front words (the edge test), z: the final smoothed plane, column: the column words;
+// maxWord: the reduced largest word of an automatic thickness scale, or null (then S.thickness).  Also leaves the
+// unit normal of every pixel in `normals` (w = 0; all zero where the pixel is empty).
+__global__ __launch_bounds__(256) void k_liquid_compose(const uint32_t *__restrict__ depth, const uint32_t *__restrict__ z,
+                                                        const unsigned long long *__restrict__ column,
+                                                        const uint32_t *__restrict__ edge, const float *__restrict__ rays,
+                                                        const unsigned long long *__restrict__ maxWord, LiquidShade S, int width,
+                                                        int height, float4 *__restrict__ normals, uint32_t *__restrict__ rgb) {
+    const float sref = maxWord ? column_value(*maxWord) : S.thickness;
+    const Vec3 L = over_length({S.light[0], S.light[1], S.light[2]});
+    auto point = [&](int c, int r, bool &ok) -> Vec3 {
+        ok = c >= 0 && c < width && r >= 0 && r < height;
+        uint32_t b = kNoDepth;
+        if (ok) b = z[(size_t)r * width + c];
+        ok = b != kNoDepth;
+        if (!ok) return {0.f, 0.f, 0.f};
+        const float d = __uint_as_float(b);
+        return {rays[c] * d, rays[width + r] * d, -d};
+    };
+    compose_quad(width * height, rgb, [&](int p) -> uint32_t {
+        const int r = p / width, c = p - r * width;
+        bool here, e, w, n, s;
+        const Vec3 P = point(c, r, here);
+        const uint32_t eb = edge[p];
+        if (!here) {
+            normals[p] = make_float4(0.f, 0.f, 0.f, 0.f);
+            return eb != 0xFFFFFFFFu ? 0xFFFFFFu : 0u;
+        }
+        const Vec3 Pe = point(c + 1, r, e), Pw = point(c - 1, r, w), Pn = point(c, r - 1, n), Ps = point(c, r + 1, s);
+        const Vec3 Tx = liquid_tangent(P, e, Pe, w, Pw, {1.f, 0.f, 0.f});
+        const Vec3 Ty = liquid_tangent(P, n, Pn, s, Ps, {0.f, 1.f, 0.f});
+        Vec3 N = {Tx.y * Ty.z - Tx.z * Ty.y, Tx.z * Ty.x - Tx.x * Ty.z, Tx.x * Ty.y - Tx.y * Ty.x};
+        const float len2 = dot3(N, N);
+        if (len2 > 0.f) { // (a NaN is not)
+            const float len = sqrtf(len2);
+            N = {N.x / len, N.y / len, N.z / len};
+        } else N = {0.f, 0.f, 1.f};
+        normals[p] = make_float4(N.x, N.y, N.z, 0.f);
+        if (eb != 0xFFFFFFFFu && eb <= depth[p]) return 0xFFFFFFu; // GL_LESS, lines drawn first
+
+        const float ax = rays[c], ay = rays[width + r];
+        const float vlen = sqrtf((1.f + ax * ax) + ay * ay);
+        const Vec3 V = {-ax / vlen, -ay / vlen, 1.f / vlen};
+        const Vec3 Hh = over_length({L.x + V.x, L.y + V.y, L.z + V.z});
+        const float nl = at_least_zero(dot3(N, L));
+        float spec = at_least_zero(dot3(N, Hh));
+#pragma unroll
+        for (int k = 0; k < 6; ++k) spec = spec * spec;
+        const float f = 1.f - at_least_zero(dot3(N, V));
+        const float fres = 0.02f + 0.98f * (((f * f) * (f * f)) * f);
+        const float tau = sref == 0.f ? 0.f : column_value(column[p]) / sref;
+        const float lit = 0.25f + 0.75f * nl;
+        const float kappa[3] = {6.f, 2.f, 0.75f}, sky[3] = {0.75f, 0.85f, 1.f};
+        uint32_t out = 0u;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            const float T = 1.f / (1.f + kappa[ch] * tau);
+            float col = ((1.f - fres) * (T * lit) + fres * sky[ch]) + spec;
+            col = at_least_zero(col);
+            col = col < 1.f ? col : 1.f;
+            out |= (uint32_t)(col * 255.f + 0.5f) << (8 * ch);
+        }
+        return out;
+    });
+}
+
 template <class Frame>
 void launch_splat(const RenderParams &R, const float4 *pos4, int n, bool plain, Frame F, hipStream_t s) {
     if (n <= 0) return;
@@ -573,4 +780,27 @@ void sph_launch_render_column(const RenderParams &R, const FrameView &V, const f
     if (autoRange) k_column_max<<<min(blocks_of(npix), 1024), 256, 0, s>>>(V.packed, npix, V.maxWord);
     k_column_compose<<<blocks_of((npix + 3) / 4), 256, 0, s>>>(V.packed, V.edge, autoRange ? V.maxWord : nullptr, lo, hi, npix,
                                                              V.range, V.rgb);
+}
+
+const uint32_t *sph_launch_render_liquid(const RenderParams &R, const FrameView &V, const float4 *pos4, int n, bool plain,
+                                         const LiquidParams &Q, hipStream_t s) {
+    const int npix = R.width * R.height;
+    k_frame_clear<<<blocks_of(npix), 256, 0, s>>>(V.depth, nullptr, SphereFrame::kEmpty, nullptr, npix, nullptr, 0u, 0u, nullptr);
+    k_frame_clear<<<blocks_of(npix), 256, 0, s>>>(nullptr, V.packed, 0ull, nullptr, npix, nullptr, 0u, 0u, V.maxWord);
+    launch_splat(R, pos4, n, plain, SphereFrame{{Q.radius, Q.radius * Q.radius, V.rays}, V.depth}, s);
+    launch_splat(R, pos4, n, plain, ColumnFrame{{Q.h, Q.h2, Q.dcoef, V.rays}, V.packed}, s); // sph_launch_render_column's
+    if (Q.autoThickness) k_column_max<<<min(blocks_of(npix), 1024), 256, 0, s>>>(V.packed, npix, V.maxWord);
+    const uint32_t *z = V.depth;
+    if (Q.smoothRadius > 0) {
+        const dim3 grid((R.width + kSmoothW - 1) / kSmoothW, (R.height + kSmoothH - 1) / kSmoothH);
+        for (int it = 0; it < Q.smoothIterations; ++it) {
+            uint32_t *out = (it & 1) ? V.smooth[1] : V.smooth[0];
+            k_liquid_smooth<<<grid, kSmoothW * kSmoothH, 0, s>>>(z, out, R.width, R.height, Q.smoothRadius, Q.smoothDepth);
+            z = out;
+        }
+    }
+    const LiquidShade S{{Q.light[0], Q.light[1], Q.light[2]}, Q.thickness};
+    k_liquid_compose<<<blocks_of((npix + 3) / 4), 256, 0, s>>>(V.depth, z, V.packed, V.edge, V.rays, Q.autoThickness ? V.maxWord : nullptr, S,
+                                                             R.width, R.height, V.normals, V.rgb);
+    return z;
 }

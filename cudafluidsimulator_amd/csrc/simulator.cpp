@@ -152,6 +152,10 @@ const unsigned char *Simulator::renderColumn(int *width, int *height) {
     return rendered("renderColumn", multi, impl, width, height, "sph_render_column", [&] { return sph_render_column(impl, NULL); });
 }
 
+const unsigned char *Simulator::renderLiquid(int *width, int *height) {
+    return rendered("renderLiquid", multi, impl, width, height, "sph_render_liquid", [&] { return sph_render_liquid(impl, NULL); });
+}
+
 const float *Simulator::sampleField(int field, const float origin[3], const float spacing[3], int nx, int ny, int nz) {
     if (multi) {
         fprintf(stderr, "sph: sampleField: a multi-GPU run (SPH_GPUS > 1) is not sampled\n");

@@ -227,7 +227,7 @@ struct RenderParams {
 };
 // the static layer: 12 box edges x 4096 samples, minimum depth bits per pixel (clears `edge` first)
 void sph_launch_render_edges(const RenderParams &R, uint32_t *edge, hipStream_t s);
-// The frame's device buffers, as the three launchers below take them: filled by frame_view() (sph_frame.hip) and by
+// The frame's device buffers, as the four launchers below take them: filled by frame_view() (sph_frame.hip) and by
 // nobody else; null while no frame that needs the buffer was asked for
 struct FrameView {
     uint32_t *depth, *count;     // per pixel, of the flat and field frames
@@ -237,6 +237,8 @@ struct FrameView {
     uint32_t *range;             // the bits of lo and hi of the colour scale
     unsigned long long *maxWord; // the largest column word
     const float *rays;           // sph_launch_column_rays' table
+    uint32_t *smooth[2];         // the liquid frame's ping-pong planes of smoothed depth bits
+    float4 *normals;             // ... and its normals
 };
 // The pixel-centre rays of a width x height image: ax of column c at [c], ay of row r at
 // [width + r] (built once per image size, like the edge layer).
@@ -250,6 +252,21 @@ void sph_launch_render_field(const RenderParams &R, const FrameView &V, const fl
                              int field, bool autoRange, float lo, float hi, hipStream_t s);
 void sph_launch_render_column(const RenderParams &R, const FrameView &V, const float4 *pos4, int n, bool plain, float h, float h2,
                               float dcoef, bool autoRange, float lo, float hi, hipStream_t s);
+// The liquid frame, the options with every default resolved: clears, the sphere splat into
+// V.depth, sph_launch_render_column's splat (and maximum, where the thickness scale is automatic) into V.packed, the
+// smoothing iterations, compose into V.normals and V.rgb.  Returns the plane that holds the final smoothed depth:
+// V.depth where nothing was smoothed, else one of V.smooth.
+struct LiquidParams {
+    float radius;              // of the spheres, <= h
+    float h, h2, dcoef;        // the handle's settings (the column words)
+    int smoothIterations, smoothRadius;
+    float smoothDepth;
+    float light[3];            // not normalised
+    bool autoThickness;
+    float thickness;           // the scale where not automatic
+};
+const uint32_t *sph_launch_render_liquid(const RenderParams &R, const FrameView &V, const float4 *pos4, int n, bool plain,
+                                         const LiquidParams &Q, hipStream_t s);
 
 // The bits of the field frame's scalar of a row, from the (vx, vy, vz, rho) sph_download_state
 // reads: what the field frame colours by and the diagnostics reduce.  fp32, every operation rounded on its own.

@@ -1,4 +1,5 @@
-// The visualiser's frame: sph_render_frame / sph_render_field / sph_render_column and what reads their results
+// The visualiser's frame: sph_render_frame / sph_render_field / sph_render_column / sph_render_liquid and what reads
+// their results
 // (kernels: render.hip).
 #include "sph_handle.h"
 
@@ -19,6 +20,10 @@ int render_resize(sph_handle *h, int width, int height) {
     if (rc) return rc;
     f.packed.reset(); // (sized by the image: the next field or column frame allocates it again)
     f.rays.reset();
+    f.smooth[0].reset();
+    f.smooth[1].reset();
+    f.normals.reset();
+    f.smoothed = nullptr;
     f.kind = FrameKind::Flat;
     f.rp.width = f.rp.height = 0;
     const size_t npix = (size_t)width * (size_t)height;
@@ -43,7 +48,7 @@ int render_resize(sph_handle *h, int width, int height) {
 // the frame's device buffers, as the launchers of render.hip take them
 FrameView frame_view(const sph_handle *h) {
     const FrameState &f = h->frame;
-    return {f.depth, f.count, f.edge, f.rgb, f.packed, f.range, f.maxWord, f.rays};
+    return {f.depth, f.count, f.edge, f.rgb, f.packed, f.range, f.maxWord, f.rays, {f.smooth[0], f.smooth[1]}, f.normals};
 }
 
 // the value range of the field and column options: a message or null
@@ -53,7 +58,7 @@ const char *bad_value_range(float lo, float hi) {
 }
 
 // The renderers up to their launch: the state checks, the caller's options into `o`, the option checks (pointSize: the
-// option in `o`, null for the column frame, which draws no points; `rest(o)`: the entry point's own, a message or null),
+// option in `o`, null for the column and liquid frames, which draw no points; `rest(o)`: the entry point's own, a message or null),
 // the buffers, the wait for the previous frame's copy.
 template <class Opt, class Rest>
 int frame_begin(sph_handle *h, const Opt *opt, const char *unset, Opt &o, const int32_t *pointSize, Rest rest, FrameKind kind) {
@@ -74,13 +79,19 @@ int frame_begin(sph_handle *h, const Opt *opt, const char *unset, Opt &o, const 
         if (!f.range) HIPCHK(h, f.range.alloc(2));
         if (!f.rangeHost) HIPCHK(h, f.rangeHost.alloc(2));
     }
-    if (kind == FrameKind::Column) {
+    if (kind == FrameKind::Column || kind == FrameKind::Liquid) {
         if (!f.maxWord) HIPCHK(h, f.maxWord.alloc(1));
         if (!f.rays) {
             HIPCHK(h, f.rays.alloc((size_t)width + height));
             sph_launch_column_rays(f.rp, f.rays, h->compute);
             HIPCHK(h, hipGetLastError());
         }
+    }
+    if (kind == FrameKind::Liquid) {
+        const size_t npix = (size_t)width * height;
+        for (auto &plane : f.smooth)
+            if (!plane) HIPCHK(h, plane.alloc(npix));
+        if (!f.normals) HIPCHK(h, f.normals.alloc(npix));
     }
     f.rp.radius = (points - 1) / 2;
     return outbound_fence(h, f.pass.out); // the previous frame's copy still reads the device frame the compose is about to rewrite
@@ -97,7 +108,7 @@ int frame_finish(sph_handle *h, FrameKind kind, Launch launch) {
     f.pass.valid = true;
     f.kind = kind;
     const OutboundCopy frame{f.host.get(), f.rgb.get(), (size_t)f.rp.width * f.rp.height * 3};
-    if (kind == FrameKind::Flat) return outbound_send(h, f.pass.out, {frame});
+    if (kind == FrameKind::Flat || kind == FrameKind::Liquid) return outbound_send(h, f.pass.out, {frame}); // (no colour scale to report)
     return outbound_send(h, f.pass.out, {frame, {f.rangeHost.get(), f.range.get(), 2 * sizeof(uint32_t)}});
 }
 
@@ -105,8 +116,9 @@ int frame_finish(sph_handle *h, FrameKind kind, Launch launch) {
 int last_frame_was(sph_handle *h, FrameKind kind) {
     SPH_ON_DEVICE(h);
     if (h->frame.pass.valid && h->frame.kind == kind) return SPH_OK;
-    return fail(h, SPH_ESTATE, kind == FrameKind::Field ? "the last render was not a field frame (sph_render_field)"
-                                                        : "the last render was not a column frame (sph_render_column)");
+    return fail(h, SPH_ESTATE, kind == FrameKind::Field    ? "the last render was not a field frame (sph_render_field)"
+                               : kind == FrameKind::Column ? "the last render was not a column frame (sph_render_column)"
+                                                           : "the last render was not a liquid frame (sph_render_liquid)");
 }
 
 // sph_field_range / sph_column_range
@@ -156,6 +168,7 @@ int sph_download_frame_buffers(sph_handle *h, uint32_t *depth_bits, uint32_t *co
     const FrameState &f = h->frame;
     if (!f.pass.valid) return fail(h, SPH_ESTATE, "sph_render_frame must come first");
     if (f.kind == FrameKind::Column) return fail(h, SPH_ESTATE, "the last render was a column frame: it writes no depth or count (sph_download_column_buffer)");
+    if (f.kind == FrameKind::Liquid) return fail(h, SPH_ESTATE, "the last render was a liquid frame: it writes no point depth or count (sph_download_liquid_buffers)");
     HIPCHK(h, hipStreamSynchronize(h->compute));
     const size_t bytes = (size_t)f.rp.width * f.rp.height * sizeof(uint32_t);
     if (depth_bits) HIPCHK(h, hipMemcpy(depth_bits, f.depth, bytes, hipMemcpyDeviceToHost));
@@ -218,5 +231,55 @@ int sph_download_column_buffer(sph_handle *h, uint64_t *column_words) {
 }
 
 int sph_column_range(sph_handle *h, float *lo, float *hi) { return frame_range(h, FrameKind::Column, lo, hi); }
+
+int sph_render_liquid(sph_handle *h, const SphLiquidFrameOptions *opt) {
+    if (!h) return SPH_EINVAL;
+    SphLiquidFrameOptions o{};
+    const float hh = h->P.h; // (read again behind frame_begin's state checks; a handle without state fails there)
+    auto rest = [hh](const SphLiquidFrameOptions &o) -> const char * {
+        if (!(o.radius == 0.f || (o.radius > 0.f && o.radius <= hh))) return "radius must be 0 (h) or 0 < radius <= h";
+        if (o.smooth_iterations < -1 || o.smooth_iterations > 8) return "smooth_iterations must be -1..8";
+        if (o.smooth_radius < -1 || o.smooth_radius > 7) return "smooth_radius must be -1..7";
+        if (!(o.smooth_depth >= 0.f) || !std::isfinite(o.smooth_depth)) return "smooth_depth must be finite and > 0 (0: 2 radius)";
+        for (float l : o.light)
+            if (!std::isfinite(l)) return "light must be finite";
+        if (!(o.thickness_scale >= 0.f) || !std::isfinite(o.thickness_scale)) return "thickness_scale must be finite and >= 0";
+        return nullptr;
+    };
+    if (int rc = frame_begin(h, opt, "SphLiquidFrameOptions.struct_size is not set", o, nullptr, rest, FrameKind::Liquid)) return rc;
+    LiquidParams Q{};
+    Q.radius = o.radius == 0.f ? h->P.h : o.radius;
+    Q.h = h->P.h, Q.h2 = h->P.h2, Q.dcoef = h->P.dcoef;
+    Q.smoothIterations = o.smooth_iterations == 0 ? 3 : o.smooth_iterations < 0 ? 0 : o.smooth_iterations;
+    Q.smoothRadius = o.smooth_radius == 0 ? 3 : o.smooth_radius < 0 ? 0 : o.smooth_radius;
+    Q.smoothDepth = o.smooth_depth == 0.f ? 2.f * Q.radius : o.smooth_depth;
+    const bool dark = o.light[0] == 0.f && o.light[1] == 0.f && o.light[2] == 0.f;
+    const float sun[3] = {-0.35f, 0.8f, 0.5f};
+    for (int k = 0; k < 3; ++k) Q.light[k] = dark ? sun[k] : o.light[k];
+    Q.autoThickness = o.thickness_scale == 0.f;
+    Q.thickness = o.thickness_scale;
+    // pos4[cur]: the rows sph_render_frame draws
+    return frame_finish(h, FrameKind::Liquid, [&] {
+        h->frame.smoothed = sph_launch_render_liquid(h->frame.rp, frame_view(h), h->pos4[h->cur], h->n, plain_path("SPH_RENDER_PLAIN"), Q, h->compute);
+    });
+}
+
+int sph_download_liquid_buffers(sph_handle *h, uint32_t *front_bits, uint32_t *smooth_depth_bits, float *normals_xyz,
+                                uint64_t *column_words) {
+    if (!h) return SPH_EINVAL;
+    if (int rc = last_frame_was(h, FrameKind::Liquid)) return rc;
+    const FrameState &f = h->frame;
+    HIPCHK(h, hipStreamSynchronize(h->compute));
+    const size_t npix = (size_t)f.rp.width * f.rp.height;
+    if (front_bits) HIPCHK(h, hipMemcpy(front_bits, f.depth, npix * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (smooth_depth_bits) HIPCHK(h, hipMemcpy(smooth_depth_bits, f.smoothed, npix * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (column_words) HIPCHK(h, hipMemcpy(column_words, f.packed, npix * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (normals_xyz) {
+        std::vector<float4> n4(npix);
+        HIPCHK(h, hipMemcpy(n4.data(), f.normals, npix * sizeof(float4), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < npix; ++i) normals_xyz[3 * i] = n4[i].x, normals_xyz[3 * i + 1] = n4[i].y, normals_xyz[3 * i + 2] = n4[i].z;
+    }
+    return SPH_OK;
+}
 
 } // extern "C"

@@ -102,14 +102,14 @@ struct Pass {
 };
 
 // What the last render drew (sph_frame.hip): decides which buffers hold a result and who may read them
-enum class FrameKind { Flat, Field, Column };
+enum class FrameKind { Flat, Field, Column, Liquid };
 
 // The visualiser's frame (sph_frame.hip; kernels: render.hip).  The first render of an image size allocates the
 // per-pixel depth bits, hit count and static box-edge layer and the RGB8 frame, on the device and in pinned memory.
 // The first field or column frame of that size adds `packed` -- the field frame's (depth bits << 32 | value bits)
 // minimum per pixel, the column frame's 64-bit sum -- and the two words of the colour scale's range, which leave for
 // pinned memory with the frame; the first column frame the word of the largest column and the table of the
-// pixel-centre rays.
+// pixel-centre rays; the first liquid frame two planes of smoothed depth and one of normals.
 struct FrameState {
     RenderParams rp{}; // size / point radius / shade of the last render (width 0: none yet)
     DeviceBuf<uint32_t> depth, count, edge, rgb;
@@ -120,6 +120,9 @@ struct FrameState {
     PinnedBuf<uint32_t> rangeHost;
     DeviceBuf<unsigned long long> maxWord;
     DeviceBuf<float> rays;
+    DeviceBuf<uint32_t> smooth[2];          // the liquid frame's ping-pong planes (first liquid frame of an image size)
+    DeviceBuf<float4> normals;              // ... and its normals
+    const uint32_t *smoothed = nullptr;     // the plane that holds the last liquid frame's final smoothed depth
     FrameKind kind = FrameKind::Flat; // of the last render
 };
 

@@ -267,6 +267,39 @@ class Simulator:
         """(lo, hi) as np.float32: the colour scale the last column frame used; blocks until it is known."""
         return self._frame_range(self._L.sph_column_range, "sph_column_range")
 
+    # -- the liquid frame: the fluid as a shaded water surface (sph_render_liquid) --
+    def render_liquid(self, radius=0.0, smooth_iterations=3, smooth_radius=3, smooth_depth=0.0, light=(0.0, 0.0, 0.0),
+                      thickness_scale=0.0, width=0, height=0):
+        """Queue one liquid frame of the current state; does not block.  frame_host() serves its RGB.  radius: of the
+        spheres (0: h); smooth_iterations (0..8) passes of a bilateral filter over (2 smooth_radius + 1)^2 pixels
+        (smooth_radius 0..7) that ignores neighbours further than smooth_depth (0: 2 radius) away in depth; light: the
+        direction towards the light in view space (all 0: the default); thickness_scale: the column value of optical
+        depth 1 (0: the frame's largest column, reduced on the device)."""
+        o = _lib.SphLiquidFrameOptions()
+        o.struct_size = C.sizeof(_lib.SphLiquidFrameOptions)
+        o.width, o.height = int(width), int(height)
+        o.radius = float(radius)
+        # (the C options keep 0 for "default": a count of 0 is spelled -1 there)
+        o.smooth_iterations = -1 if int(smooth_iterations) == 0 else int(smooth_iterations)
+        o.smooth_radius = -1 if int(smooth_radius) == 0 else int(smooth_radius)
+        o.smooth_depth = float(smooth_depth)
+        o.light[0], o.light[1], o.light[2] = (float(v) for v in light)
+        o.thickness_scale = float(thickness_scale)
+        self._check(self._L.sph_render_liquid(self._h, C.byref(o)), "sph_render_liquid")
+
+    def liquid_buffers(self):
+        """{"front", "smooth": (H, W) uint32, the bits of the front depth and of the smoothed depth, 0xFFFFFFFF where
+        the pixel is empty; "normals": (H, W, 3) float32; "column": (H, W) uint64} of the last liquid frame."""
+        h, w = self._frame_size()[1:]
+        out = dict(front=np.zeros((h, w), np.uint32), smooth=np.zeros((h, w), np.uint32),
+                   normals=np.zeros((h, w, 3), np.float32), column=np.zeros((h, w), np.uint64))
+        u32p = C.POINTER(C.c_uint32)
+        self._check(self._L.sph_download_liquid_buffers(
+            self._h, out["front"].ctypes.data_as(u32p), out["smooth"].ctypes.data_as(u32p),
+            out["normals"].ctypes.data_as(C.POINTER(C.c_float)), out["column"].ctypes.data_as(C.POINTER(C.c_uint64))),
+            "sph_download_liquid_buffers")
+        return out
+
     def render_time(self, reset=False):
         """(seconds, frames): GPU time of clear + splat + compose summed over `frames` renders."""
         sec, fr = C.c_double(0), C.c_int64(0)

@@ -98,6 +98,9 @@ class Simulator {
     // The column-density frame of the same camera: how much fluid lies behind each pixel, the colour scale from 0 to
     // the frame's largest column (sph_render_column in sph_c_api.h).
     const unsigned char *renderColumn(int *width, int *height);
+    // The liquid frame of the same camera: the fluid as a smoothed, lit water surface, every option at its default
+    // (sph_render_liquid in sph_c_api.h).
+    const unsigned char *renderLiquid(int *width, int *height);
     // The SPH-interpolated field on a regular lattice (sph_sample_field in sph_c_api.h): nx x ny x nz floats, point
     // (ix, iy, iz) = origin + i * spacing per axis at index (iz ny + iy) nx + ix.  Owned by the simulator, valid
     // until the next call.  NULL (with a message on stderr) with SPH_GPUS > 1 and where the library answers

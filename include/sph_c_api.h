@@ -431,6 +431,42 @@ int sph_download_column_buffer(sph_handle *h, uint64_t *column_words);
  * on the host.  SPH_ESTATE if the last render was not a column frame. */
 int sph_column_range(sph_handle *h, float *lo, float *hi);
 
+/* ---- the liquid frame: the fluid as a shaded water surface ----
+ * Additive to version 3: test for SPH_HAS_LIQUID_FRAME.  Defined to the bit in DESIGN.md section 10i ("The liquid
+ * frame"); all fp32, every operation rounded on its own, nothing but + - x / sqrtf, comparisons and selects.  The camera
+ * and the pixel rays are the column frame's.  Every particle is a sphere of `radius`; per pixel the library keeps the
+ * smallest depth at which the pixel's ray enters a sphere at or behind the near plane (the front buffer, the bits of
+ * wf, 0xFFFFFFFF where there is none) and the column frame's word.  The front buffer is smoothed `smooth_iterations`
+ * times by a bilateral filter over (2 smooth_radius + 1)^2 pixels that ignores neighbours further than
+ * smooth_depth away in depth, so silhouettes stay sharp; normals come from one-sided differences of the smoothed
+ * view-space points; the colour is a diffuse and a specular term, a Fresnel blend to a sky colour and a per-channel
+ * absorption by the column behind the pixel on the scale of thickness_scale.  RGB8, row 0 first: white where a box
+ * edge is not behind the (unsmoothed) front, else the water colour, else black. */
+#define SPH_HAS_LIQUID_FRAME 1
+typedef struct SphLiquidFrameOptions {
+    int32_t struct_size;       /* = sizeof(SphLiquidFrameOptions) */
+    int32_t width, height;     /* 0 = 800 x 600; at most 4096 x 4096 */
+    float radius;              /* of the spheres; 0 = h of the handle, else 0 < radius <= h */
+    int32_t smooth_iterations; /* 0 = 3; -1 = none; at most 8 */
+    int32_t smooth_radius;     /* k, in pixels; 0 = 3; -1 = a window of the pixel alone, which smooths nothing; at most 7 */
+    float smooth_depth;        /* neighbours this far away in depth or further add nothing; 0 = 2 radius; > 0, finite */
+    float light[3];            /* the direction towards the light in view space; all 0 = (-0.35, 0.8, 0.5); finite */
+    float thickness_scale;     /* the column value that counts as optical depth 1; 0 = the frame's largest column, */
+                               /* reduced on the device; >= 0, finite */
+} SphLiquidFrameOptions;
+/* sph_render_column's queueing, streams and state rules, SPH_RENDER_PLAIN=1 included.  opt == NULL: every default.
+ * A bad size, radius, count, smooth_depth, light or thickness_scale: SPH_EINVAL.  Does not block.  sph_frame_host
+ * serves the RGB and sph_get_render_time counts the frame; sph_download_frame_buffers, sph_download_field_buffer,
+ * sph_field_range, sph_download_column_buffer and sph_column_range return SPH_ESTATE after it.  A flat, field or column
+ * frame rendered afterwards is what it would have been without it. */
+int sph_render_liquid(sph_handle *h, const SphLiquidFrameOptions *opt);
+/* The buffers behind the last liquid frame, each width x height, row 0 first, each may be NULL: the front words, the
+ * bits of the smoothed depth (0xFFFFFFFF = empty in both), the unit normals as 3 floats per pixel (0, 0, 0 where
+ * empty) and the column words (those sph_render_column gives for the same state).  SPH_ESTATE if the last render was
+ * not a liquid frame. */
+int sph_download_liquid_buffers(sph_handle *h, uint32_t *front_bits, uint32_t *smooth_depth_bits, float *normals_xyz,
+                                uint64_t *column_words);
+
 /* ---- the field sample: SPH-interpolated density, speed or pressure on a regular lattice ----
  * Additive to version 3: test for SPH_HAS_FIELD_SAMPLE.  Defined to the bit in DESIGN.md section 10b ("The field
  * sample"); all fp32, every operation rounded on its own, in both math modes.  Point (ix, iy, iz) lies at
