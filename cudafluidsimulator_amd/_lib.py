@@ -34,6 +34,7 @@ EXPORTED_SYMBOLS = [
     "sph_tracers_set", "sph_tracers_advect", "sph_tracers_host", "sph_get_tracer_stats",
     "sph_derive", "sph_derived_host", "sph_get_derive_stats",
     "sph_label_bodies", "sph_bodies_host", "sph_get_body_stats",
+    "sph_neighbour_lists", "sph_neighbours_host", "sph_get_neighbour_stats",
 ]
 SPH_API_VERSION = 3
 SPH_SHADE_FLAT, SPH_SHADE_COUNT = 0, 1
@@ -50,6 +51,8 @@ SPH_HAS_TRACERS = 1
 MAX_TRACERS = 1 << 24
 SPH_HAS_DERIVED = 1
 SPH_HAS_BODIES = 1
+SPH_HAS_NEIGHBOURS = 1
+SPH_NEIGHBOURS_WALK_ORDER = 1
 BODY_TABLE = ("label", "count", "min_x", "min_y", "min_z", "max_x", "max_y", "max_z")   # words of a table row
 DIAG_SUMS = ("x", "y", "z", "vx", "vy", "vz", "rho", "prs", "v2")   # SPH_DIAG_SUM_*
 DIAG_EXTREMA = ("x", "y", "z", "speed", "rho", "prs")               # SPH_DIAG_EXT_*
@@ -193,6 +196,16 @@ class SphBodyStats(C.Structure):
                 ("unions", C.c_uint64), ("rounds", C.c_uint64), ("gave_up", C.c_uint64), ("seconds", C.c_double)]
 
 
+class SphNeighbourOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("radius", C.c_float), ("flags", C.c_int32), ("pad_", C.c_int32),
+                ("max_entries", C.c_uint64)]
+
+
+class SphNeighbourStats(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("pad_", C.c_int32), ("calls", C.c_int64), ("entries", C.c_uint64),
+                ("longest", C.c_uint64), ("runs_staged", C.c_uint64), ("runs_direct", C.c_uint64), ("seconds", C.c_double)]
+
+
 class SphKernelTimes(C.Structure):
     _fields_ = [("hash", C.c_double), ("sort", C.c_double), ("gather", C.c_double),
                 ("density", C.c_double), ("force", C.c_double), ("readback", C.c_double),
@@ -296,5 +309,9 @@ def load_library():
     L.sph_bodies_host.argtypes = [hp, C.POINTER(u32p), C.POINTER(C.c_int), C.POINTER(u32p), C.POINTER(C.c_int),
                                   C.POINTER(C.c_uint32)]
     L.sph_get_body_stats.argtypes = [hp, C.POINTER(SphBodyStats), C.c_int]
+    L.sph_neighbour_lists.argtypes = [hp, C.POINTER(SphNeighbourOptions)]
+    L.sph_neighbours_host.argtypes = [hp, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(u32p), C.POINTER(C.c_int),
+                                      C.POINTER(C.c_uint64)]
+    L.sph_get_neighbour_stats.argtypes = [hp, C.POINTER(SphNeighbourStats), C.c_int]
     _lib = L
     return L

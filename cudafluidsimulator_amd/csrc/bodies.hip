@@ -54,13 +54,6 @@ __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
 __device__ __forceinline__ uint32_t order_key(uint32_t b) { return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u); }
 __device__ __forceinline__ uint32_t order_bits(uint32_t k) { return k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu); }
 
-// the link test: c is the candidate, pi the row
-__device__ __forceinline__ bool linked(const float4 pi, const float4 c, float r2) {
-    const float ex = c.x - pi.x, ey = c.y - pi.y, ez = c.z - pi.z;
-    const float d2 = (ex * ex + ey * ey) + ez * ez;
-    return d2 <= r2; // (false for a NaN)
-}
-
 __device__ __forceinline__ uint32_t trip_bound(int n) {
     const unsigned long long b = 2ull * (unsigned long long)n + 2ull;
     return b > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)b;

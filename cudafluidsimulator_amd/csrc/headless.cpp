@@ -225,6 +225,26 @@ static bool write_bodies(Simulator *simulator, const char *dir, int f, float lin
     return ok;
 }
 
+// SPH_FREE_NEIGHBOURS=<f>, f in (0, 1], the radius in units of h: beside each written frame every particle's
+// neighbours within that radius (sph_neighbour_lists) as <dir>/neighbours_%04d.bin: the 8 bytes `SPHNBR01`, uint32 n,
+// uint32 0, uint64 entries, the n + 1 uint64 offsets, the uint32 ids, all little-endian; and one line on stderr,
+// `neighbours <frame> <entries> <longest>`.  A refused result has printed the library's message: no file, no more tries.
+static bool write_neighbours(Simulator *simulator, const char *dir, int f, float radius) {
+    const uint32_t head[2] = {(uint32_t)simulator->settings->numParticles, 0u};
+    const uint64_t *offsets = NULL;
+    const uint32_t *ids = NULL;
+    uint64_t entries = 0, longest = 0;
+    if (!simulator->neighbourLists(radius, &offsets, &ids, &entries)) return false;
+    for (uint32_t i = 0; i < head[0]; ++i) longest = offsets[i + 1] - offsets[i] > longest ? offsets[i + 1] - offsets[i] : longest;
+    FILE *out = open_out(dir, "neighbours_%04d.bin", f);
+    if (!out) return false;
+    bool ok = write_bytes(out, "SPHNBR01", 8) && write_bytes(out, head, 8) && write_bytes(out, &entries, 8);
+    ok = ok && write_bytes(out, offsets, ((size_t)head[0] + 1) * 8) && write_bytes(out, ids, (size_t)entries * 4);
+    ok = (fclose(out) == 0) && ok;
+    if (ok) fprintf(stderr, "neighbours %d %llu %llu\n", f, (unsigned long long)entries, (unsigned long long)longest);
+    return ok;
+}
+
 // SPH_FREE_STATS=1: for each written frame one JSON line of run diagnostics (Simulator::diagnostics) in
 // <dir>/stats.jsonl; doubles as %.17g, which reads back to the same double
 static bool write_stats(Simulator *simulator, FILE *out, int f) {
@@ -285,6 +305,16 @@ void startVisualization(Simulator *simulator) {
         else
             bodyLink = v * simulator->settings->h;
     }
+    float neighbourRadius = 0.f; // 0: no neighbour files
+    if (framesDir && getenv("SPH_FREE_NEIGHBOURS")) {
+        const char *e = getenv("SPH_FREE_NEIGHBOURS");
+        char *end = NULL;
+        const float v = strtof(e, &end);
+        if (end == e || *end || !std::isfinite(v) || !(v > 0.f) || v > 1.f)
+            fprintf(stderr, "sph: SPH_FREE_NEIGHBOURS=%s is not a radius in (0, 1] (units of h) -- writing no neighbour files\n", e);
+        else
+            neighbourRadius = v * simulator->settings->h;
+    }
     FILE *stats = NULL;
     if (framesDir && getenv("SPH_FREE_STATS") && atoi(getenv("SPH_FREE_STATS")) != 0) {
         const std::string path = std::string(framesDir) + "/stats.jsonl";
@@ -301,6 +331,8 @@ void startVisualization(Simulator *simulator) {
         if (framesDir && tracers > 0 && f % every == 0 && !write_tracers(simulator, framesDir, f)) tracers = 0;
         if (framesDir && particles && f % every == 0 && !write_particles(simulator, framesDir, f)) particles = false;
         if (framesDir && bodyLink > 0.f && f % every == 0 && !write_bodies(simulator, framesDir, f, bodyLink)) bodyLink = 0.f;
+        if (framesDir && neighbourRadius > 0.f && f % every == 0 && !write_neighbours(simulator, framesDir, f, neighbourRadius))
+            neighbourRadius = 0.f;
         if (framesDir && f % every == 0 && !write_frame(simulator, framesDir, f, field)) framesDir = NULL;
         if (framesDir && slice >= 0 && f % every == 0 && !write_slice(simulator, framesDir, f, slice)) slice = -1;
         if (framesDir && surfaceIso > 0.f && f % every == 0 && !write_surface(simulator, framesDir, f, surfaceIso)) surfaceIso = 0.f;

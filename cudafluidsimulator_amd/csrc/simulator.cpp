@@ -269,6 +269,26 @@ bool Simulator::labelBodies(float link, const uint32_t **labels, const uint32_t 
     return true;
 }
 
+bool Simulator::neighbourLists(float radius, const uint64_t **offsets, const uint32_t **neighbours, uint64_t *entries) {
+    if (multi) {
+        fprintf(stderr, "sph: neighbourLists: a multi-GPU run (SPH_GPUS > 1) lists no neighbours\n");
+        return false;
+    }
+    if (!impl) return false;
+    SphNeighbourOptions o = {};
+    o.struct_size = (int32_t)sizeof o;
+    o.radius = radius;
+    const int rc = sph_neighbour_lists(impl, &o);
+    if (rc == SPH_ESTATE || rc == SPH_EINVAL || rc == SPH_ENOMEM) { // (SPH_SWEEP=linked, a radius longer than h, more ids than
+                                                                    // max_entries, ...): no lists, nothing broken
+        fprintf(stderr, "sph: neighbourLists: %s\n", sph_last_error(impl));
+        return false;
+    }
+    check(impl, rc, "sph_neighbour_lists");
+    check(impl, sph_neighbours_host(impl, offsets, neighbours, NULL, entries), "sph_neighbours_host");
+    return true;
+}
+
 bool Simulator::getVelocity(float *vel_xyz) {
     if (multi || !impl || !vel_xyz) return false;
     check(impl, sph_download_state(impl, NULL, vel_xyz, NULL, NULL), "sph_download_state");

@@ -369,6 +369,27 @@ void sph_launch_bodies_plain_end(const BodyArgs &A, hipStream_t s);
 // both paths: the table of numBodies rows, labels in id order, counters->largest
 void sph_launch_bodies_table(const BodyArgs &A, int numBodies, hipStream_t s);
 
+// ---- neighbour lists: every particle's neighbours within a radius, as CSR (neighbours.hip) ----
+struct NeighbourArgs {
+    StreamView S;            // the rows and their candidates, n > 0 (the velocities are not read)
+    float r2;                // radius squared, rounded once
+    uint32_t *counts;        // [n] particle-id order: the length of every list
+    uint64_t *offsets;       // [n + 1] particle-id order: the exclusive scan of counts, then the total
+    uint32_t *neighbours;    // [total] the lists (emit and sort launches only)
+    unsigned long long *blockSum; // [sph_neighbour_scan_blocks(n)] the scan's per-block sums, then offsets
+    unsigned long long *totals;   // [2] the total (left by the scan) and the longest list (left by the count): what the host waits for
+    unsigned long long *counters; // [2] runs_staged, runs_direct (default path; both walks add to them)
+};
+constexpr int kNeighbourCounters = 2;
+int sph_neighbour_scan_blocks(int n);
+// Four launches; plain = the check path (one thread per row, one thread per list).  count: clears totals, fills
+// counts and totals[1].  scan: offsets[0, n] and totals[0] from counts.  emit: the walk again, every taken candidate's
+// id to its list, in walk order.  sort: every list ascending, in place.
+void sph_launch_neighbour_count(const DevParams &P, const NeighbourArgs &A, bool plain, hipStream_t s);
+void sph_launch_neighbour_scan(const NeighbourArgs &A, hipStream_t s);
+void sph_launch_neighbour_emit(const DevParams &P, const NeighbourArgs &A, bool plain, hipStream_t s);
+void sph_launch_neighbour_sort(const NeighbourArgs &A, bool plain, hipStream_t s);
+
 // ---- the surface mesh (surface.hip; defined in DESIGN.md section 10d) ----
 struct SurfaceArgs {
     int nx, ny, nz;          // lattice points per axis, each >= 2; point (ix, iy, iz) has L = (iz ny + iy) nx + ix

@@ -24,7 +24,7 @@ using sph_owned::PinnedBuf;
 
 // The library's SPH_* environment knobs: this comment is the list.  None changes a result; all are for A/B runs,
 // studies and diagnosis.  "create": read once, by read_knobs() at the top of sph_create, into sph_handle::knobs.
-// "call": read by every call, through plain_path().  Numbers are parsed with atoi (an empty value is 0).
+// "call": read by every call, through plain_path() / call_knob().  Numbers are parsed with atoi (an empty value is 0).
 //   name                  default  read    what it does
 //   SPH_SLIM_DIV          (auto)   create  0: the pair body uses the full IEEE divide / square-root expansions even
 //                                          with the reference's constants (same bits); any other value: no effect
@@ -47,6 +47,9 @@ using sph_owned::PinnedBuf;
 //   SPH_TRACER_PLAIN      0        call    non-zero: sph_tracers_advect takes the one-thread-per-tracer check path
 //   SPH_DERIVE_PLAIN      0        call    non-zero: sph_derive takes the one-thread-per-row check path
 //   SPH_BODIES_PLAIN      0        call    non-zero: sph_label_bodies takes the check path (min-label propagation in rounds)
+//   SPH_NEIGHBOURS_PLAIN  0        call    non-zero: sph_neighbour_lists takes the check path (one thread per row, one per list)
+//   SPH_NEIGHBOURS_TIME_PHASE 0    call    1 count, 2 scan, 3 emit, 4 sort: SphNeighbourStats.seconds sums that phase alone
+//                                          (scripts/studies/neighbours.py); 0: all four
 //   SPH_MGPU_THREADS      0        (libsph_mgpu.so, its own object: sph_mgpu_create in mgpu_state.cpp) non-zero: one
 //                                          host thread per local slab
 // (The SPH_* variables the command-line front end reads -- SPH_SWEEP, SPH_GPUS, SPH_TRANSPORT, SPH_RECUT_EVERY,
@@ -63,10 +66,11 @@ struct Knobs {
     bool stepTrace = false;
     bool readbackSdma = true;
 };
-inline bool plain_path(const char *name) {
+inline int call_knob(const char *name) { // a "call" knob's number (unset: 0)
     const char *e = getenv(name);
-    return e && atoi(e) != 0;
+    return e ? atoi(e) : 0;
 }
+inline bool plain_path(const char *name) { return call_knob(name) != 0; }
 
 constexpr int kEventRing = 64;
 constexpr int kCounterWords = 16 + 256 * 16; // 16 spare words, then 256 shards x 16: [0] pair tests,
@@ -335,6 +339,26 @@ struct sph_handle {
     int bodyN = 0, bodyCount = 0;    // rows and bodies of the last sph_label_bodies
     sph_host::Pass body;             // out: the results on their way to the pinned buffers; seconds: every kernel of the call
     unsigned long long bodyLinks = 0, bodyUnions = 0, bodyRounds = 0, bodyGaveUp = 0; // sums over calls
+
+    // ---- sph_neighbours.hip ----
+    // Neighbour lists (neighbours.hip): the length of every list and the CSR offsets in id order, the scan's block sums,
+    // the lists themselves, the two words the call waits for (the total, the longest list), and the pinned copies of
+    // offsets and lists; the per-particle buffers and the lists grow on demand, each on its own.
+    sph_host::DeviceBuf<uint32_t> nbrCounts, nbrLists;
+    sph_host::DeviceBuf<uint64_t> nbrOffsets;
+    sph_host::DeviceBuf<unsigned long long> nbrBlockSum, nbrTotals;
+    sph_host::PinnedBuf<uint64_t> nbrOffsetsHost;
+    sph_host::PinnedBuf<uint32_t> nbrListsHost;
+    sph_host::PinnedBuf<unsigned long long> nbrTotalsHost;
+    sph_host::Event nbrCounted;      // the two words have landed
+    size_t nbrCap = 0;               // particles the per-particle buffers hold
+    uint64_t nbrEntryCap = 0;        // entries either list buffer holds
+    int nbrN = 0;                    // rows of the last sph_neighbour_lists
+    uint64_t nbrEntries = 0, nbrLongest = 0; // ... its total and its longest list
+    uint64_t nbrEntriesSum = 0;      // sum over calls
+    uint64_t nbrNoOffsets = 0;       // the offsets of a result without particles: {0}
+    sph_host::CounterBlock nbrCounters{kNeighbourCounters}; // runs_staged, runs_direct
+    sph_host::Pass nbr;              // out: offsets and lists on their way to the pinned buffers; seconds: count + scan + emit + sort
 };
 
 #define HIPCHK(h, call)                                                               \
@@ -380,7 +404,7 @@ int outbound_fence(sph_handle *h, Outbound &o);
 int outbound_send(sph_handle *h, Outbound &o, std::initializer_list<OutboundCopy> copies);
 hipError_t outbound_wait(const Outbound &o);
 // What the passes over the grid's sorted stream share (the field sample, the surface mesh, the tracers, the derived
-// fields, the bodies).  analysis_begin: the state checks, in this order -- a slab handle (`slab_hint` ends that message),
+// fields, the bodies, the neighbour lists).  analysis_begin: the state checks, in this order -- a slab handle (`slab_hint` ends that message),
 // no state yet, SPH_SWEEP_LINKED, SPH_KEY_MORTON, a phase-split step still open; `what` names the pass in the messages.
 // analysis_grid: a grid of the state the handle holds NOW.  Phase 1: it exists (sph_phase_grid, or built ahead by a
 // timed step).  Phase 0: the table of the last step is the pre-integration one; the next step's grid is built here,

@@ -452,6 +452,29 @@ class Simulator:
         self._check(self._L.sph_get_body_stats(self._h, C.byref(st), 1 if reset else 0), "sph_get_body_stats")
         return dict(calls=st.calls, links=st.links, unions=st.unions, rounds=st.rounds, gave_up=st.gave_up, seconds=st.seconds)
 
+    # -- neighbour lists: every particle's neighbours within a radius, as CSR (sph_neighbour_lists) --
+    def neighbour_lists(self, radius=0.0, walk_order=False, max_entries=0):
+        """{"offsets": (n + 1,) uint64, "neighbours": (entries,) uint32}: arrays of their own.  The neighbours of
+        particle id i -- the particles within `radius` of it (0: h; else 0 < radius <= h), itself excluded -- are
+        neighbours[offsets[i]:offsets[i + 1]], in ascending id order, or (walk_order) in the order in which the density
+        sweep's walk of its row meets them.  A result of more than `max_entries` ids (0: 1 << 28) is refused."""
+        opt = _lib.SphNeighbourOptions(C.sizeof(_lib.SphNeighbourOptions), radius,
+                                       _lib.SPH_NEIGHBOURS_WALK_ORDER if walk_order else 0, 0, int(max_entries))
+        self._check(self._L.sph_neighbour_lists(self._h, C.byref(opt)), "sph_neighbour_lists")
+        off, nb, n, entries = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint32)(), C.c_int(0), C.c_uint64(0)
+        self._check(self._L.sph_neighbours_host(self._h, C.byref(off), C.byref(nb), C.byref(n), C.byref(entries)), "sph_neighbours_host")
+        return dict(offsets=_rows(off, n.value + 1, None, np.uint64), neighbours=_rows(nb, entries.value, None, np.uint32))
+
+    def neighbour_stats(self, reset=False):
+        """dict(calls, entries, longest, runs_staged, runs_direct, seconds): sums since create or the last reset;
+        `entries` sums the lists' ids over the calls, `longest` is the longest list of the last call, the two run
+        counters are derive_stats()'s over the count and the emit walk, `seconds` the GPU time of count + scan + emit +
+        sort."""
+        st = _lib.SphNeighbourStats()
+        self._check(self._L.sph_get_neighbour_stats(self._h, C.byref(st), 1 if reset else 0), "sph_get_neighbour_stats")
+        return dict(calls=st.calls, entries=st.entries, longest=st.longest, runs_staged=st.runs_staged,
+                    runs_direct=st.runs_direct, seconds=st.seconds)
+
     def phase(self, name):
         self._check(getattr(self._L, "sph_phase_" + name)(self._h), "sph_phase_" + name)
 

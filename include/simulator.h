@@ -131,6 +131,12 @@ class Simulator {
     // body with the most particles.  Any out-pointer may be NULL.  false (with a message on stderr) with SPH_GPUS > 1
     // and where the library answers SPH_ESTATE or SPH_EINVAL.
     bool labelBodies(float link, const uint32_t **labels, const uint32_t **table, int *numBodies, uint32_t *largest);
+    // The neighbour lists of the current state (sph_neighbour_lists in sph_c_api.h) as CSR in particle-id order: the
+    // neighbours of particle i -- the particles within `radius` of it (0: h; else 0 < radius <= h), in ascending id
+    // order -- are neighbours[offsets[i]] .. neighbours[offsets[i + 1] - 1]; n + 1 offsets, *entries ids, owned by the
+    // simulator, valid until the next neighbourLists.  Any out-pointer may be NULL.  false (with a message on stderr)
+    // with SPH_GPUS > 1 and where the library answers an error (SPH_ENOMEM: more than 1 << 28 ids).
+    bool neighbourLists(float radius, const uint64_t **offsets, const uint32_t **neighbours, uint64_t *entries);
     // The velocities of the current state (sph_download_state), n x 3 floats in particle-id order, into the caller's
     // buffer.  false with SPH_GPUS > 1 and before setup().
     bool getVelocity(float *vel_xyz);

@@ -755,6 +755,56 @@ typedef struct SphBodyStats {
 /* Sums since create or since the last reset.  Blocks. */
 int sph_get_body_stats(sph_handle *h, SphBodyStats *out, int reset);
 
+/* ---- neighbour lists: every particle's neighbours within a radius, as CSR in particle-id order ----
+ * Additive to version 3: test for SPH_HAS_NEIGHBOURS.  Defined to the bit in DESIGN.md section 10j ("Neighbour
+ * lists"); all fp32, every operation rounded on its own, in both math modes.  With r2 = radius radius, particle j is a
+ * neighbour of i when i != j and d2 <= r2, e = p_j - p_i (the words sph_download_state returns),
+ * d2 = (ex ex + ey ey) + ez ez; a NaN d2 is no neighbour.  That is the bodies' link test: the relation is symmetric to
+ * the bit, coincident particles are neighbours of each other, a particle is never in its own list.  The result:
+ * offsets = n + 1 words, offsets[0] = 0, offsets[i + 1] - offsets[i] the number of neighbours of particle id i;
+ * neighbours = offsets[n] particle ids.  Inside a list the ids ascend -- the whole result is then a function of the
+ * positions alone, the same words for any sweep backend, stream layout, kernel path or launch shape -- or, with
+ * SPH_NEIGHBOURS_WALK_ORDER, stand in the order in which the density sweep's walk of the particle's row meets them (the
+ * 27 cells in dz, dy, dx nesting, each cell's rows in the order of the grid's sorted stream: defined through the grid
+ * sph_download_grid returns after the call); that mode skips the sort.  Out of scope: multi-GPU lists, radii above h
+ * (the 27-cell walk is the bound), per-entry distances (recompute them from the ids and the downloaded positions),
+ * device pointers to the result. */
+#define SPH_HAS_NEIGHBOURS 1
+enum { SPH_NEIGHBOURS_WALK_ORDER = 1 };
+typedef struct SphNeighbourOptions {
+    int32_t struct_size;   /* = sizeof(SphNeighbourOptions) */
+    float radius;          /* 0 = h, else finite with 0 < radius <= h */
+    int32_t flags;         /* SPH_NEIGHBOURS_* */
+    int32_t pad_;          /* 0 */
+    uint64_t max_entries;  /* the call refuses a result with more entries; 0 = 1 << 28 (1 GiB of ids) */
+} SphNeighbourOptions;
+/* Lists the neighbours in the state the handle holds NOW.  opt == NULL: every default.  State rules, grid handling
+ * and error codes are sph_label_bodies's: the grid is found (phase 1) or built ahead (phase 0), the next step consumes
+ * it and no result of any step changes; SPH_ESTATE before any state, inside an open phase-split step, for
+ * SPH_FLAG_EXTERNAL_STATE handles (lists cross slab boundaries), with SPH_SWEEP_LINKED and with SPH_KEY_MORTON;
+ * SPH_EINVAL for an unset struct_size, an unknown flag, a non-zero pad_ and for a radius that is not finite, negative
+ * or greater than h.  The call counts, scans, and waits on the host once, for the total and the longest count.  A
+ * total above max_entries: SPH_ENOMEM, the message names both numbers, nothing is allocated for the refused result
+ * and the handle holds no neighbour result (the stats show what was counted).  Otherwise the buffers grow on demand,
+ * the emit, the sort and the copies are queued and the call returns.  No particles: SPH_OK, n = 0, offsets = {0}.
+ * SPH_NEIGHBOURS_PLAIN=1 in the environment selects the check path (one thread per row, every candidate loaded from
+ * global memory, the sort one thread per list; identical words). */
+int sph_neighbour_lists(sph_handle *h, const SphNeighbourOptions *opt);
+/* The results of the last sph_neighbour_lists, owned by the handle, valid until the next one.  Blocks until the copies
+ * have landed.  Any out-pointer may be NULL; *neighbours may be NULL where entries == 0.  SPH_ESTATE before the first
+ * sph_neighbour_lists and after one that was refused. */
+int sph_neighbours_host(sph_handle *h, const uint64_t **offsets, const uint32_t **neighbours, int *n, uint64_t *entries);
+typedef struct SphNeighbourStats {
+    int32_t struct_size, pad_;  /* sizeof(SphNeighbourStats), 0: both written by the call */
+    int64_t calls;              /* calls that ran a kernel (either path) */
+    uint64_t entries;           /* sum of offsets[n] over those calls; a refused call adds what it counted */
+    uint64_t longest;           /* the longest list of the last call */
+    uint64_t runs_staged, runs_direct; /* as SphDeriveStats, summed over the count and the emit walk; check path: 0 */
+    double seconds;             /* GPU time of count + scan + emit + sort (HIP events on the compute stream) */
+} SphNeighbourStats;
+/* Sums since create or since the last reset (a reset clears `longest` too).  Blocks. */
+int sph_get_neighbour_stats(sph_handle *h, SphNeighbourStats *out, int reset);
+
 const char *sph_build_info(void);
 
 #ifdef __cplusplus
