@@ -19,40 +19,19 @@
 // and takes the minimum over itself and its linked neighbours, all 27 cells from global memory, one launch per
 // round, until a round changes nothing.
 //
-// Both paths then share mark + scan (which particle ids are labels, and how many labels lie below each) and the
-// table launches.  Candidates are read from global memory on both paths (no LDS staging; section 10g says why).
+// Both paths then share mark + scan (which particle ids are labels, and how many labels lie below each: the scan of
+// scan_common.h) and the table launches.  Candidates are read from global memory on both paths (no LDS staging;
+// section 10g says why).
+#include "scan_common.h"
 #include "walk_common.h"
 
 namespace {
 
-constexpr int kBodyScanTile = 2048; // particle ids per block of the scan: 256 threads x 8
 constexpr uint32_t kNoId = 0xFFFFFFFFu;
 
 // a load that is served by the device's coherent level, never by this CU's L1 (the forest and the check path's
 // labels change under the launch that reads them)
 __device__ __forceinline__ uint32_t load_shared(uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = min(v, (uint32_t)__shfl_xor(v, off));
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = max(v, (uint32_t)__shfl_xor(v, off));
-    return v;
-}
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_xor(v, off);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-// the diagnostics' ordering key of a float's bits (section 10c) and its inverse
-__device__ __forceinline__ uint32_t order_key(uint32_t b) { return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u); }
-__device__ __forceinline__ uint32_t order_bits(uint32_t k) { return k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu); }
 
 __device__ __forceinline__ uint32_t trip_bound(int n) {
     const unsigned long long b = 2ull * (unsigned long long)n + 2ull;
@@ -217,72 +196,6 @@ __global__ __launch_bounds__(256) void k_body_mark(BodyArgs A, bool plain) {
     if (lab == id && id < (uint32_t)A.S.n) A.flag[id] = 1;
 }
 
-// ---- exclusive scan of flag[0, n) into rank: block sums, their offsets (one block), ranks ----
-__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t &total) {
-    __shared__ uint32_t waveSum[4];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint32_t incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t t = __shfl_up(incl, off);
-        if (lane >= off) incl += t;
-    }
-    if (lane == 63) waveSum[w] = incl;
-    __syncthreads();
-    uint32_t base = 0;
-    total = 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        base += q < w ? waveSum[q] : 0u;
-        total += waveSum[q];
-    }
-    __syncthreads(); // waveSum may be written again by the next call
-    return base + incl - v;
-}
-
-__device__ __forceinline__ uint32_t scan_slice(const BodyArgs &A, uint32_t (&f)[8]) {
-    const int first = blockIdx.x * kBodyScanTile + threadIdx.x * 8;
-    uint32_t sum = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        f[k] = first + k < A.S.n ? A.flag[first + k] : 0u;
-        sum += f[k];
-    }
-    return sum;
-}
-
-__global__ __launch_bounds__(256) void k_body_scan_sums(BodyArgs A) {
-    uint32_t f[8], total;
-    const uint32_t mine = scan_slice(A, f);
-    (void)block_exclusive_scan(mine, total);
-    if (threadIdx.x == 0) A.blockSum[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(256) void k_body_scan_offsets(BodyArgs A, int blocks) {
-    uint32_t carry = 0;
-    for (int k = 0; k < blocks; k += 256) { // (uniform trip count: the barriers inside are reached by every thread)
-        const int b = k + threadIdx.x;
-        const uint32_t v = b < blocks ? A.blockSum[b] : 0u;
-        uint32_t total;
-        const uint32_t before = block_exclusive_scan(v, total);
-        if (b < blocks) A.blockSum[b] = carry + before;
-        carry += total;
-    }
-    if (threadIdx.x == 0) A.counters->numBodies = carry;
-}
-
-__global__ __launch_bounds__(256) void k_body_scan_ranks(BodyArgs A) {
-    uint32_t f[8], total;
-    const uint32_t mine = scan_slice(A, f);
-    uint32_t before = A.blockSum[blockIdx.x] + block_exclusive_scan(mine, total);
-    const int first = blockIdx.x * kBodyScanTile + threadIdx.x * 8;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        if (first + k < A.S.n) A.rank[first + k] = before;
-        before += f[k];
-    }
-}
-
 // ---- the check path's round ----
 __global__ __launch_bounds__(256) void k_body_plain_round(DevParams P, BodyArgs A, bool first) {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -292,13 +205,11 @@ __global__ __launch_bounds__(256) void k_body_plain_round(DevParams P, BodyArgs 
     clipped_runs(P, A.S, pi, valid, js, je);
     const uint32_t mine = valid ? load_shared(&A.rowLabel[i]) : 0u;
     uint32_t m = mine, links = 0;
-#pragma unroll
-    for (int r = 0; r < 9; ++r)
-        for (int j = js[r]; j < je[r]; ++j) {
-            if (j == i || !linked(pi, A.S.position(j), A.r2)) continue;
-            links += j < i ? 1u : 0u;
-            m = min(m, load_shared(&A.rowLabel[j]));
-        }
+    for_each_row_candidate(js, je, [&](int j) WALK_LAMBDA {
+        if (j == i || !linked(pi, A.S.position(j), A.r2)) return;
+        links += j < i ? 1u : 0u;
+        m = min(m, load_shared(&A.rowLabel[j]));
+    });
     const bool lower = valid && m < mine;
     if (lower) __hip_atomic_store(&A.rowLabel[i], m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // (its only writer)
     const unsigned long long any = __ballot(lower);
@@ -394,27 +305,24 @@ __global__ __launch_bounds__(256) void k_body_table_finish(BodyArgs A, int numBo
     if ((threadIdx.x & 63) == 0 && packed) atomicMax(&A.counters->largest, packed);
 }
 
-inline int blocks_of(int n) { return (n + 255) / 256; }
-inline int fold_blocks_of(int n) { return (n + 256 * kBodyFold - 1) / (256 * kBodyFold); }
+inline int fold_blocks_of(int n) { return blocks_of(n, 256 * kBodyFold); }
 
 void launch_mark_and_scan(const BodyArgs &A, bool plain, hipStream_t s) {
-    const int sb = sph_body_scan_blocks(A.S.n);
-    k_body_mark<<<blocks_of(A.S.n), 256, 0, s>>>(A, plain);
-    k_body_scan_sums<<<sb, 256, 0, s>>>(A);
-    k_body_scan_offsets<<<1, 256, 0, s>>>(A, sb);
-    k_body_scan_ranks<<<sb, 256, 0, s>>>(A);
+    k_body_mark<<<blocks_of(A.S.n, 256), 256, 0, s>>>(A, plain);
+    // rank = the exclusive scan of flag, numBodies = its total
+    launch_exclusive_scan<uint32_t>(A.flag, A.S.n, A.blockSum, A.rank, &A.counters->numBodies, nullptr, s);
 }
 
 } // namespace
 
-int sph_body_scan_blocks(int n) { return n > 0 ? (n + kBodyScanTile - 1) / kBodyScanTile : 0; }
+int sph_body_scan_blocks(int n) { return scan_blocks(n); }
 
 void sph_launch_bodies_unite(const DevParams &P, const BodyArgs &A, hipStream_t s) {
     if (A.S.n <= 0) return;
     (void)hipMemsetAsync(A.counters, 0, sizeof(BodyCounters), s);
-    k_body_clear<<<blocks_of(A.S.n), 256, 0, s>>>(A, false);
-    k_body_link<<<blocks_of(A.S.n), 256, 0, s>>>(P, A);
-    k_body_flatten<<<blocks_of(A.S.n), 256, 0, s>>>(A);
+    k_body_clear<<<blocks_of(A.S.n, 256), 256, 0, s>>>(A, false);
+    k_body_link<<<blocks_of(A.S.n, 256), 256, 0, s>>>(P, A);
+    k_body_flatten<<<blocks_of(A.S.n, 256), 256, 0, s>>>(A);
     k_body_root_id<<<fold_blocks_of(A.S.n), 256, 0, s>>>(A);
     launch_mark_and_scan(A, false, s);
 }
@@ -422,13 +330,13 @@ void sph_launch_bodies_unite(const DevParams &P, const BodyArgs &A, hipStream_t 
 void sph_launch_bodies_plain_begin(const BodyArgs &A, hipStream_t s) {
     if (A.S.n <= 0) return;
     (void)hipMemsetAsync(A.counters, 0, sizeof(BodyCounters), s);
-    k_body_clear<<<blocks_of(A.S.n), 256, 0, s>>>(A, true);
+    k_body_clear<<<blocks_of(A.S.n, 256), 256, 0, s>>>(A, true);
 }
 
 void sph_launch_bodies_plain_round(const DevParams &P, const BodyArgs &A, bool first, hipStream_t s) {
     if (A.S.n <= 0) return;
     (void)hipMemsetAsync(&A.counters->changed, 0, sizeof(uint32_t), s);
-    k_body_plain_round<<<blocks_of(A.S.n), 256, 0, s>>>(P, A, first);
+    k_body_plain_round<<<blocks_of(A.S.n, 256), 256, 0, s>>>(P, A, first);
 }
 
 void sph_launch_bodies_plain_end(const BodyArgs &A, hipStream_t s) {
@@ -438,7 +346,7 @@ void sph_launch_bodies_plain_end(const BodyArgs &A, hipStream_t s) {
 
 void sph_launch_bodies_table(const BodyArgs &A, int numBodies, hipStream_t s) {
     if (A.S.n <= 0 || numBodies <= 0) return;
-    k_body_table_init<<<blocks_of(A.S.n), 256, 0, s>>>(A, numBodies);
+    k_body_table_init<<<blocks_of(A.S.n, 256), 256, 0, s>>>(A, numBodies);
     k_body_table_fill<<<fold_blocks_of(A.S.n), 256, 0, s>>>(A, numBodies);
-    k_body_table_finish<<<blocks_of(numBodies), 256, 0, s>>>(A, numBodies);
+    k_body_table_finish<<<blocks_of(numBodies, 256), 256, 0, s>>>(A, numBodies);
 }

@@ -10,8 +10,9 @@
 // slice, four candidates per trip, with unconditional reads (an exhausted lane reads the slice's last record again)
 // and selected terms, which change no bit (walk_common.h).  A run whose union is longer than the slice (a wave that spans two rows of cells, a crowded
 // cell) is walked by every lane from global memory, in the same order with the same arithmetic, so both walks give
-// the same words.  One workgroup is one wave; its barriers are wave-uniform (u0, u1 and the trip count are made
-// uniform through readfirstlane); nothing spins and no workgroup talks to another.
+// the same words.  The walk itself is walk_common.h's walk_runs_staged, shared with neighbours.hip: one workgroup is one
+// wave; its barriers are wave-uniform (u0, u1 and the trip count are made uniform through readfirstlane); nothing spins
+// and no workgroup talks to another.
 #include "walk_common.h"
 
 namespace {
@@ -112,9 +113,7 @@ __global__ __launch_bounds__(256) void k_derive_plain(DevParams P, DeriveArgs A)
     int js[9], je[9];
     clipped_runs(P, A.S, pi, valid, js, je);
     DeriveAcc S;
-#pragma unroll
-    for (int r = 0; r < 9; ++r)
-        for (int j = js[r]; j < je[r]; ++j) derive_add(P, pi, vi, A.S.position(j), A.S.velocity(j), S);
+    for_each_row_candidate(js, je, [&](int j) WALK_LAMBDA { derive_add(P, pi, vi, A.S.position(j), A.S.velocity(j), S); });
     if (valid) derive_finish(A, pi, S);
 }
 
@@ -129,45 +128,9 @@ __global__ __launch_bounds__(64) void k_derive_wave(DevParams P, DeriveArgs A) {
     clipped_runs(P, A.S, pi, valid, js, je);
     DeriveAcc S;
     uint32_t staged = 0, direct = 0;
-    // one copy of the loop body (not nine): r is wave-uniform, picking this run's bounds is 16 conditional moves
-#pragma unroll 1
-    for (int r = 0; r < 9; ++r) {
-        int jsr = js[0], jer = je[0];
-#pragma unroll
-        for (int q = 1; q < 9; ++q) {
-            jsr = (r == q) ? js[q] : jsr;
-            jer = (r == q) ? je[q] : jer;
-        }
-        const bool nonempty = jer > jsr;
-        if (!__ballot(nonempty)) continue;
-        // the stretch of the stream the wave needs for this run: [u0, u1), the same in every lane
-        const int u0 = __builtin_amdgcn_readfirstlane(wave_min_i32(nonempty ? jsr : 0x7fffffff));
-        const int u1 = __builtin_amdgcn_readfirstlane(wave_max_i32(nonempty ? jer : 0));
-        const int len = u1 - u0;
-        if (len > kDeriveSlice) {
-            direct += 1;
-            for (int j = jsr; j < jer; ++j) derive_add(P, pi, vi, A.S.position(j), A.S.velocity(j), S);
-            continue;
-        }
-        staged += 1;
-        // 32 bytes per candidate; with the interleaved records (vel = pos + 1, stride 2) a plain copy
-        for (int t = lane; t < 2 * len; t += 64) slice[t] = ((t & 1) ? A.S.vel : A.S.pos)[(size_t)(u0 + (t >> 1)) * A.S.stride];
-        __syncthreads();
-        // this lane's range in slots of the slice, [a, b) within [0, len); every read is clamped to slot len - 1
-        const int a = nonempty ? jsr - u0 : 0, b = nonempty ? jer - u0 : 0;
-        const int trips = __builtin_amdgcn_readfirstlane(wave_max_i32(b - a));
-        for (int k = 0; k < trips; k += kDeriveTrip) {
-            float4 c[kDeriveTrip], v[kDeriveTrip];
-#pragma unroll
-            for (int u = 0; u < kDeriveTrip; ++u) {
-                const int slot = min(a + k + u, len - 1);
-                c[u] = slice[2 * slot], v[u] = slice[2 * slot + 1];
-            }
-#pragma unroll
-            for (int u = 0; u < kDeriveTrip; ++u) derive_add(P, pi, vi, c[u], v[u], a + k + u < b, S);
-        }
-        __syncthreads(); // the slice has been read: the next run may overwrite it
-    }
+    walk_runs_staged<2, kDeriveSlice, kDeriveTrip>(
+        A.S, js, je, slice, staged, direct, [&](int j) WALK_LAMBDA { derive_add(P, pi, vi, A.S.position(j), A.S.velocity(j), S); },
+        [&](const float4(&c)[2], bool mine) WALK_LAMBDA { derive_add(P, pi, vi, c[0], c[1], mine, S); });
     if (lane == 0) {
         if (staged) atomicAdd(&A.counters[0], (unsigned long long)staged);
         if (direct) atomicAdd(&A.counters[1], (unsigned long long)direct);

@@ -18,10 +18,6 @@ constexpr int kDiagThreads = 256;
 constexpr int kDiagWaves = kDiagThreads / SPH_WAVE;
 constexpr int kDiagMaxBlocks = 1024; // 4 workgroups per CU: every lane takes ceil(n / 2^18) rows beyond that
 
-// the ordering key of an fp32 bit pattern (-0 < +0; a NaN sorts where its bits put it) and its inverse
-__device__ __forceinline__ uint32_t diag_key(uint32_t b) { return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u); }
-__device__ __forceinline__ uint32_t diag_unkey(uint32_t k) { return (k >> 31) ? (k ^ 0x80000000u) : ~k; }
-
 // q(t): NaN -> 0, t >= 2^31 -> INT64_MAX, t < -2^31 -> INT64_MIN (each counted in sat), else (int64)floor(t 2^32).
 // The scaling is exact, and the floor of a double below 2^63 in magnitude converts exactly.
 __device__ __forceinline__ long long diag_q(double t, uint32_t &sat) {
@@ -70,19 +66,6 @@ __device__ __forceinline__ DiagRow diag_row(const float4 p, const float4 v, uint
     return r;
 }
 
-// wave64 butterflies over the 32-bit halves, as wave_sum_u32 / wave_min_i32 of sph_device.h
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, off);
-        const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), off);
-        v += ((unsigned long long)hi << 32) | lo;
-    }
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) { return (uint32_t)wave_min_i32((int)(v ^ 0x80000000u)) ^ 0x80000000u; }
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) { return (uint32_t)wave_max_i32((int)(v ^ 0x80000000u)) ^ 0x80000000u; }
-
 // the whole block: zero sums and bins, the identities of the extrema, the given range of the histogram
 __global__ __launch_bounds__(kDiagThreads) void k_diag_clear(DiagBlock *__restrict__ blk, uint32_t loBits, uint32_t hiBits) {
     const int t = threadIdx.x;
@@ -115,8 +98,8 @@ __global__ __launch_bounds__(kDiagThreads) void k_diag_plain(DiagArgs A, DiagBlo
         atomicAdd((unsigned long long *)&blk->hi[k], (unsigned long long)(r.q[k] >> 32));
     }
     for (int k = 0; k < SPH_DIAG_EXTREMA; ++k) {
-        atomicMin(&blk->minKey[k], diag_key(r.b[k]));
-        atomicMax(&blk->maxKey[k], diag_key(r.b[k]));
+        atomicMin(&blk->minKey[k], order_key(r.b[k]));
+        atomicMax(&blk->maxKey[k], order_key(r.b[k]));
     }
     if (sat) atomicAdd(&blk->saturated, (unsigned long long)sat);
 }
@@ -144,7 +127,7 @@ __global__ __launch_bounds__(kDiagThreads) void k_diag_reduce(DiagArgs A, DiagBl
         }
 #pragma unroll
         for (int k = 0; k < SPH_DIAG_EXTREMA; ++k) {
-            const uint32_t key = diag_key(r.b[k]);
+            const uint32_t key = order_key(r.b[k]);
             mn[k] = min(mn[k], key);
             mx[k] = max(mx[k], key);
         }
@@ -206,8 +189,8 @@ __device__ __forceinline__ int diag_ext_of(int field) {
 __device__ __forceinline__ void diag_range(const DiagArgs &A, const DiagBlock *blk, float &lo, float &hi) {
     if (A.autoRange) {
         const int e = diag_ext_of(A.histField);
-        lo = __uint_as_float(diag_unkey(blk->minKey[e]));
-        hi = __uint_as_float(diag_unkey(blk->maxKey[e]));
+        lo = __uint_as_float(order_bits(blk->minKey[e]));
+        hi = __uint_as_float(order_bits(blk->maxKey[e]));
     } else {
         lo = __uint_as_float(blk->range[0]);
         hi = __uint_as_float(blk->range[1]);

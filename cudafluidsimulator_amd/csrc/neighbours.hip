@@ -7,14 +7,14 @@
 //
 // Count and emit are one templated walk (nbr_take): row i walks what the density sweep walks, the nine runs of
 // load_runs (sweep_common.h) around sweep_cell of its own position, each in stream order.  The default path is
-// derived.hip's: one wave per 64 consecutive rows, for each of the nine runs the UNION of the lanes' ranges staged in
-// LDS -- here as 16-byte records (x, y, z, id) --, unconditional reads (an exhausted lane reads the slice's last record
-// again), a selected test, wave-uniform barriers; a run whose union is longer than the slice is walked by every lane
-// from global memory in the same order.  The count adds a selected 0 / 1; the emit stores the id under a mask
-// (integers: nothing to select) at neighbours[offsets[id] + k++], so a list is in the order of the walk.  The check
-// path (SPH_NEIGHBOURS_PLAIN=1) is one thread per row with every candidate from global memory.
+// derived.hip's, the staged walk of walk_common.h (walk_runs_staged): one wave per 64 consecutive rows, for each of the
+// nine runs the UNION of the lanes' ranges staged in LDS -- here as 16-byte records (x, y, z, id) --, a selected test;
+// a run whose union is longer than the slice is walked by every lane from global memory in the same order.  The
+// count adds a selected 0 / 1; the emit stores the id under a mask (integers: nothing to select) at
+// neighbours[offsets[id] + k++], so a list is in the order of the walk.  The check path (SPH_NEIGHBOURS_PLAIN=1) is
+// one thread per row with every candidate from global memory.
 //
-// The scan is an exclusive 64-bit scan of the n counts in id order: block sums, their offsets (one block), offsets.
+// The scan is scan_common.h's with 64-bit sums, over the n counts in id order.
 //
 // The sort puts every list in ascending order, in place.  Ids are distinct, so the rank of an id -- how many ids of
 // its list are smaller -- is its place.  Default path: one wave per kSortLists consecutive lists, which are one
@@ -26,6 +26,7 @@
 // on the order inside them, so this is the textbook merge-split network, and every chunk has been in a window by the
 // end (C >= 3).  The windows of a list are stored and staged again by the same one-wave workgroup, a barrier between.
 // Check path: one thread per list, heapsort in global memory.
+#include "scan_common.h"
 #include "walk_common.h"
 
 namespace {
@@ -59,10 +60,9 @@ namespace {
 #endif
 constexpr int kSortWide = NBR_SORT_WIDE;
 constexpr int kNbrSlice = NBR_SLICE;
-constexpr int kNbrTrip = 4; // candidates per trip of the staged walk, as derived.hip
+constexpr int kNbrTrip = 4; // candidates per trip of the staged walk, as derived.hip's
 constexpr int kSortSlice = NBR_SORT_SLICE;
 constexpr int kSortLists = NBR_SORT_LISTS;
-constexpr int kNbrScanTile = 2048; // particle ids per block of the scan: 256 threads x 8
 static_assert(kSortLists >= 1 && kSortLists <= 64 && kSortSlice >= 4 && kSortSlice % 2 == 0, "one lane per list of a batch");
 
 // One candidate c of the row (pi, id): taken when it is the lane's (mine), within the radius and another particle.
@@ -110,130 +110,26 @@ struct NbrRow {
 template <bool kEmit>
 __global__ __launch_bounds__(256) void k_nbr_plain(DevParams P, NeighbourArgs A) {
     NbrRow<kEmit> R(P, A, blockIdx.x * 256 + threadIdx.x);
-#pragma unroll
-    for (int r = 0; r < 9; ++r)
-        for (int j = R.js[r]; j < R.je[r]; ++j) nbr_take<kEmit>(R.pi, R.id, A.r2, A.S.position(j), true, R.out, R.room, R.k);
+    for_each_row_candidate(R.js, R.je, [&](int j) WALK_LAMBDA { nbr_take<kEmit>(R.pi, R.id, A.r2, A.S.position(j), true, R.out, R.room, R.k); });
     R.finish(A);
 }
 
-// One wave per 64 consecutive rows of the sorted stream (the structure of k_derive_wave).
+// One wave per 64 consecutive rows of the sorted stream.
 template <bool kEmit>
 __global__ __launch_bounds__(64) void k_nbr_wave(DevParams P, NeighbourArgs A) {
     __shared__ float4 slice[kNbrSlice];
     const int lane = threadIdx.x;
     NbrRow<kEmit> R(P, A, blockIdx.x * 64 + lane);
     uint32_t staged = 0, direct = 0;
-    // one copy of the loop body (not nine): r is wave-uniform, picking this run's bounds is 16 conditional moves
-#pragma unroll 1
-    for (int r = 0; r < 9; ++r) {
-        int jsr = R.js[0], jer = R.je[0];
-#pragma unroll
-        for (int q = 1; q < 9; ++q) {
-            jsr = (r == q) ? R.js[q] : jsr;
-            jer = (r == q) ? R.je[q] : jer;
-        }
-        const bool nonempty = jer > jsr;
-        if (!__ballot(nonempty)) continue;
-        // the stretch of the stream the wave needs for this run: [u0, u1), the same in every lane
-        const int u0 = __builtin_amdgcn_readfirstlane(wave_min_i32(nonempty ? jsr : 0x7fffffff));
-        const int u1 = __builtin_amdgcn_readfirstlane(wave_max_i32(nonempty ? jer : 0));
-        const int len = u1 - u0;
-        if (len > kNbrSlice) {
-            direct += 1;
-            for (int j = jsr; j < jer; ++j) nbr_take<kEmit>(R.pi, R.id, A.r2, A.S.position(j), true, R.out, R.room, R.k);
-            continue;
-        }
-        staged += 1;
-        for (int t = lane; t < len; t += 64) slice[t] = A.S.position(u0 + t);
-        __syncthreads();
-        // this lane's range in slots of the slice, [a, b) within [0, len); every read is clamped to slot len - 1
-        const int a = nonempty ? jsr - u0 : 0, b = nonempty ? jer - u0 : 0;
-        const int trips = __builtin_amdgcn_readfirstlane(wave_max_i32(b - a));
-        for (int k = 0; k < trips; k += kNbrTrip) {
-            float4 c[kNbrTrip];
-#pragma unroll
-            for (int u = 0; u < kNbrTrip; ++u) c[u] = slice[min(a + k + u, len - 1)];
-#pragma unroll
-            for (int u = 0; u < kNbrTrip; ++u) nbr_take<kEmit>(R.pi, R.id, A.r2, c[u], a + k + u < b, R.out, R.room, R.k);
-        }
-        __syncthreads(); // the slice has been read: the next run may overwrite it
-    }
+    walk_runs_staged<1, kNbrSlice, kNbrTrip>(
+        A.S, R.js, R.je, slice, staged, direct,
+        [&](int j) WALK_LAMBDA { nbr_take<kEmit>(R.pi, R.id, A.r2, A.S.position(j), true, R.out, R.room, R.k); },
+        [&](const float4(&c)[1], bool mine) WALK_LAMBDA { nbr_take<kEmit>(R.pi, R.id, A.r2, c[0], mine, R.out, R.room, R.k); });
     if (lane == 0) {
         if (staged) atomicAdd(&A.counters[0], (unsigned long long)staged);
         if (direct) atomicAdd(&A.counters[1], (unsigned long long)direct);
     }
     R.finish(A);
-}
-
-// ---- exclusive 64-bit scan of counts[0, n) into offsets[0, n], the total to totals[0] ----
-__device__ __forceinline__ unsigned long long block_exclusive_scan(unsigned long long v, unsigned long long &total) {
-    __shared__ unsigned long long waveSum[4];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    unsigned long long incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const unsigned long long t = __shfl_up(incl, off);
-        if (lane >= off) incl += t;
-    }
-    if (lane == 63) waveSum[w] = incl;
-    __syncthreads();
-    unsigned long long base = 0;
-    total = 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        base += q < w ? waveSum[q] : 0ull;
-        total += waveSum[q];
-    }
-    __syncthreads(); // waveSum may be written again by the next call
-    return base + incl - v;
-}
-
-__device__ __forceinline__ unsigned long long scan_slice(const NeighbourArgs &A, uint32_t (&c)[8]) {
-    const int first = blockIdx.x * kNbrScanTile + threadIdx.x * 8;
-    unsigned long long sum = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        c[k] = first + k < A.S.n ? A.counts[first + k] : 0u;
-        sum += c[k];
-    }
-    return sum;
-}
-
-__global__ __launch_bounds__(256) void k_nbr_scan_sums(NeighbourArgs A) {
-    uint32_t c[8];
-    unsigned long long total;
-    const unsigned long long mine = scan_slice(A, c);
-    (void)block_exclusive_scan(mine, total);
-    if (threadIdx.x == 0) A.blockSum[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(256) void k_nbr_scan_offsets(NeighbourArgs A, int blocks) {
-    unsigned long long carry = 0;
-    for (int k = 0; k < blocks; k += 256) { // (uniform trip count: the barriers inside are reached by every thread)
-        const int b = k + threadIdx.x;
-        const unsigned long long v = b < blocks ? A.blockSum[b] : 0ull;
-        unsigned long long total;
-        const unsigned long long before = block_exclusive_scan(v, total);
-        if (b < blocks) A.blockSum[b] = carry + before;
-        carry += total;
-    }
-    if (threadIdx.x == 0) {
-        A.totals[0] = carry;
-        A.offsets[A.S.n] = carry;
-    }
-}
-
-__global__ __launch_bounds__(256) void k_nbr_scan_final(NeighbourArgs A) {
-    uint32_t c[8];
-    unsigned long long total;
-    const unsigned long long mine = scan_slice(A, c);
-    unsigned long long before = A.blockSum[blockIdx.x] + block_exclusive_scan(mine, total);
-    const int first = blockIdx.x * kNbrScanTile + threadIdx.x * 8;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        if (first + k < A.S.n) A.offsets[first + k] = before;
-        before += c[k];
-    }
 }
 
 // ---- the sort ----
@@ -355,11 +251,9 @@ __global__ __launch_bounds__(256) void k_nbr_sort_plain(NeighbourArgs A) {
     }
 }
 
-inline int blocks_of(int n, int per) { return (n + per - 1) / per; }
-
 } // namespace
 
-int sph_neighbour_scan_blocks(int n) { return n > 0 ? blocks_of(n, kNbrScanTile) : 0; }
+int sph_neighbour_scan_blocks(int n) { return scan_blocks(n); }
 
 void sph_launch_neighbour_count(const DevParams &P, const NeighbourArgs &A, bool plain, hipStream_t s) {
     if (A.S.n <= 0) return;
@@ -370,10 +264,9 @@ void sph_launch_neighbour_count(const DevParams &P, const NeighbourArgs &A, bool
 
 void sph_launch_neighbour_scan(const NeighbourArgs &A, hipStream_t s) {
     if (A.S.n <= 0) return;
-    const int sb = sph_neighbour_scan_blocks(A.S.n);
-    k_nbr_scan_sums<<<sb, 256, 0, s>>>(A);
-    k_nbr_scan_offsets<<<1, 256, 0, s>>>(A, sb);
-    k_nbr_scan_final<<<sb, 256, 0, s>>>(A);
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "offsets are scanned as unsigned long long");
+    unsigned long long *offsets = reinterpret_cast<unsigned long long *>(A.offsets);
+    launch_exclusive_scan<unsigned long long>(A.counts, A.S.n, A.blockSum, offsets, &A.totals[0], offsets + A.S.n, s);
 }
 
 void sph_launch_neighbour_emit(const DevParams &P, const NeighbourArgs &A, bool plain, hipStream_t s) {

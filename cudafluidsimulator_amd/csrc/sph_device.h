@@ -75,6 +75,42 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
     return v;
 }
+__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = min(v, (uint32_t)__shfl_xor(v, off));
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = max(v, (uint32_t)__shfl_xor(v, off));
+    return v;
+}
+// (64-bit words travel as their 32-bit halves)
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, off);
+        const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), off);
+        v += ((unsigned long long)hi << 32) | lo;
+    }
+    return v;
+}
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long o = __shfl_xor(v, off);
+        v = o > v ? o : v;
+    }
+    return v;
+}
+
+// The ordering key of an fp32 bit pattern and its inverse: unsigned keys ascend as the floats do (-0 < +0; a NaN sorts
+// where its bits put it), so integer minima and maxima of keys are the floats' (DESIGN.md sections 10c, 10g)
+__device__ __forceinline__ uint32_t order_key(uint32_t b) { return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u); }
+__device__ __forceinline__ uint32_t order_bits(uint32_t k) { return k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu); }
+
+// blocks of `per` items that hold n of them
+inline int blocks_of(int n, int per) { return (n + per - 1) / per; }
 
 // Particle state lives in two float4 streams, both in cell-sorted order:
 //   pos4[i] = (x, y, z, bits(original particle id))

@@ -1,6 +1,9 @@
 // What the analysis passes' kernels share (sample.hip, tracers.hip, derived.hip, bodies.hip, neighbours.hip): the walks of a
 // StreamView (sph_device.h) around a point or a row.  sweep_common.h stays the step's; from it come only sweep_cell and
-// load_runs.  Every function is __forceinline__ and none holds a barrier: those stay in the kernels, in plain sight.
+// load_runs.  Every function is __forceinline__ and none holds a barrier -- those stay in the kernels, in plain sight --
+// but one: walk_runs_staged, the staged walk of a row's nine runs, whose two barriers and the wave-uniform conditions
+// around them (which runs are skipped, which walk from global memory, how many trips a run takes) are one unit that
+// its two kernels must not hold in two copies.
 //
 // Selected terms.  The wave-shared walks read and compute unconditionally and SELECT what they add: take ? term : 0.f,
 // never a product with a mask, because the term of a candidate that is not taken is garbage of either sign.  Adding the
@@ -80,6 +83,14 @@ __device__ __forceinline__ void for_each_candidate_27(const DevParams &P, const 
     }
 }
 
+// the direct walk of a row: f(j) for every row j of its nine clipped runs, each in stream order
+template <class F>
+__device__ __forceinline__ void for_each_row_candidate(const int (&js)[9], const int (&je)[9], F f) {
+#pragma unroll
+    for (int r = 0; r < 9; ++r)
+        for (int j = js[r]; j < je[r]; ++j) f(j);
+}
+
 // A lane's window [ws, we) of the stream in the row of cells (sy, sz): the cells cx - 1 .. cx + 1 are one contiguous
 // run (flattened keys: x is the fastest axis; empty cells hold {0, 0} and add nothing).  Empty -- ws > we -- for a
 // lane that is not active.
@@ -123,5 +134,69 @@ __device__ __forceinline__ void take_staged(const float4 *cand, int cnt, int lo,
             for (int w = 0; w < kRecord; ++w) c[u][w] = cand[kRecord * (k + u) + w];
 #pragma unroll
         for (int u = 0; u < 4; ++u) take(c[u], k + u >= lo && k + u < hi);
+    }
+}
+
+// The staged walk of 64 consecutive rows' nine runs by a one-wave workgroup (k_derive_wave, k_nbr_wave): lane l holds
+// the clipped runs js / je of its row.  For each of the nine runs the UNION [u0, u1) of the lanes' ranges is copied into
+// `slice` (LDS, kSlice records of kRecord float4: 1 = the position words, 2 = position and velocity) between two
+// barriers, and every lane walks its own range from there, kTrip candidates to a trip: take(record, mine), mine = the
+// slot is in the lane's range.  The reads are unconditional -- a lane whose range is exhausted reads the union's last
+// record again and stays in the trip -- so take() must select, not branch (the top of this file).  A run whose union is
+// longer than the slice is walked by every lane from global memory in the same order: directFn(j).  staged / direct
+// count the runs of either kind.  Everything that decides whether a barrier is reached -- the ballot, u0, u1, the trip
+// count -- is wave-uniform (readfirstlane), and a workgroup is one wave.
+// (The copy is picked by the record width here, not handed in: see take_staged.)
+template <int kRecord, int kSlice, int kTrip, class Direct, class Take>
+__device__ __forceinline__ void walk_runs_staged(const StreamView &S, const int (&js)[9], const int (&je)[9], float4 (&slice)[kRecord * kSlice],
+                                                 uint32_t &staged, uint32_t &direct, Direct directFn, Take take) {
+    static_assert(kRecord == 1 || kRecord == 2, "position words, or position and velocity");
+    const int lane = threadIdx.x;
+    // (32-byte records: a lane copies words t = lane, lane + 64, ... of a slice, all of its own parity: one stream,
+    // picked once -- picked per word inside the copy loop, the pointer came from the kernel's arguments by a load per trip)
+    [[maybe_unused]] const float4 *half = (lane & 1) ? S.vel : S.pos;
+    // one copy of the loop body (not nine): r is wave-uniform, picking this run's bounds is 16 conditional moves
+#pragma unroll 1
+    for (int r = 0; r < 9; ++r) {
+        int jsr = js[0], jer = je[0];
+#pragma unroll
+        for (int q = 1; q < 9; ++q) {
+            jsr = (r == q) ? js[q] : jsr;
+            jer = (r == q) ? je[q] : jer;
+        }
+        const bool nonempty = jer > jsr;
+        if (!__ballot(nonempty)) continue;
+        // the stretch of the stream the wave needs for this run: [u0, u1), the same in every lane
+        const int u0 = __builtin_amdgcn_readfirstlane(wave_min_i32(nonempty ? jsr : 0x7fffffff));
+        const int u1 = __builtin_amdgcn_readfirstlane(wave_max_i32(nonempty ? jer : 0));
+        const int len = u1 - u0;
+        if (len > kSlice) {
+            direct += 1;
+            for (int j = jsr; j < jer; ++j) directFn(j);
+            continue;
+        }
+        staged += 1;
+        if constexpr (kRecord == 2) {
+            // 32 bytes per candidate; with the interleaved records (vel = pos + 1, stride 2) a plain copy
+            for (int t = lane; t < 2 * len; t += 64) slice[t] = half[(size_t)(u0 + (t >> 1)) * S.stride];
+        } else {
+            for (int t = lane; t < len; t += 64) slice[t] = S.position(u0 + t);
+        }
+        __syncthreads();
+        // this lane's range in slots of the slice, [a, b) within [0, len); every read is clamped to slot len - 1
+        const int a = nonempty ? jsr - u0 : 0, b = nonempty ? jer - u0 : 0;
+        const int trips = __builtin_amdgcn_readfirstlane(wave_max_i32(b - a));
+        for (int k = 0; k < trips; k += kTrip) {
+            float4 c[kTrip][kRecord];
+#pragma unroll
+            for (int u = 0; u < kTrip; ++u) {
+                const int slot = min(a + k + u, len - 1);
+#pragma unroll
+                for (int w = 0; w < kRecord; ++w) c[u][w] = slice[kRecord * slot + w];
+            }
+#pragma unroll
+            for (int u = 0; u < kTrip; ++u) take(c[u], a + k + u < b);
+        }
+        __syncthreads(); // the slice has been read: the next run may overwrite it
     }
 }

@@ -212,6 +212,29 @@ def test_crowded_cells_runs_about_the_count_slice_and_lists_about_the_sort_slice
     sim.close()
 
 
+def test_the_scans_second_round_of_block_sums(monkeypatch):
+    """n = 524,289 = 256 x 2,048 + 1: the scan of the list lengths and the scan of the bodies' label flags take 257
+    tiles each, so their offsets kernel carries its total into a second round of block sums, and the last tile holds
+    one id.  Nothing the results are held to passes through a scan: the derived fields' neighbour counts, and numpy's
+    unique over the labels."""
+    for env in ("SPH_NEIGHBOURS_PLAIN", "SPH_BODIES_PLAIN", "SPH_DERIVE_PLAIN"):
+        monkeypatch.setenv(env, "0")
+    n = 256 * 2048 + 1
+    box = float(sph.default_settings(n, True).boxDim)
+    sim = simulator((np.random.default_rng(524289).random((n, 3)) * box).astype(F))
+    got = sim.neighbour_lists()
+    offsets = got["offsets"].astype(np.int64)
+    assert offsets.shape == (n + 1,) and offsets[0] == 0 and offsets[-1] == len(got["neighbours"])
+    assert np.array_equal(np.diff(offsets) + 1, sim.derive()["neighbours"].astype(np.int64))
+    bodies = sim.label_bodies()
+    labels, table = bodies["labels"], bodies["table"]
+    want, counts = np.unique(labels, return_counts=True)
+    assert bodies["num_bodies"] == len(want) == len(table)
+    assert np.array_equal(table[:, 0], want) and np.array_equal(table[:, 1], counts.astype(np.uint32))
+    assert np.array_equal(labels[table[:, 0]], table[:, 0])
+    sim.close()
+
+
 def test_max_entries(monkeypatch):
     monkeypatch.setenv("SPH_NEIGHBOURS_PLAIN", "0")
     pos, vel = BS.big("dense4096")
