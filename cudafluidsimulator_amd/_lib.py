@@ -34,6 +34,7 @@ EXPORTED_SYMBOLS = [
     "sph_tracers_set", "sph_tracers_advect", "sph_tracers_host", "sph_get_tracer_stats",
     "sph_derive", "sph_derived_host", "sph_get_derive_stats",
     "sph_label_bodies", "sph_bodies_host", "sph_get_body_stats",
+    "sph_measure_bodies", "sph_body_moments_host", "sph_body_values", "sph_get_body_measure_stats",
     "sph_neighbour_lists", "sph_neighbours_host", "sph_get_neighbour_stats",
 ]
 SPH_API_VERSION = 3
@@ -51,10 +52,13 @@ SPH_HAS_TRACERS = 1
 MAX_TRACERS = 1 << 24
 SPH_HAS_DERIVED = 1
 SPH_HAS_BODIES = 1
+SPH_HAS_BODY_MOMENTS = 1
 SPH_HAS_NEIGHBOURS = 1
 SPH_NEIGHBOURS_WALK_ORDER = 1
 BODY_TABLE = ("label", "count", "min_x", "min_y", "min_z", "max_x", "max_y", "max_z")   # words of a table row
 DIAG_SUMS = ("x", "y", "z", "vx", "vy", "vz", "rho", "prs", "v2")   # SPH_DIAG_SUM_*
+BODY_SUMS = DIAG_SUMS + ("xx", "yy", "zz", "xy", "xz", "yz", "lx", "ly", "lz")   # ... then SPH_BODY_SUM_*
+BODY_SIZE_BINS = 32
 DIAG_EXTREMA = ("x", "y", "z", "speed", "rho", "prs")               # SPH_DIAG_EXT_*
 DIAG_BINS = 256
 
@@ -196,6 +200,52 @@ class SphBodyStats(C.Structure):
                 ("unions", C.c_uint64), ("rounds", C.c_uint64), ("gave_up", C.c_uint64), ("seconds", C.c_double)]
 
 
+class SphBodyMeasureOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("link", C.c_float), ("max_bodies", C.c_uint32), ("pad_", C.c_int32)]
+
+
+class SphBodyMomentsRaw(C.Structure):
+    _fields_ = [("label", C.c_uint32), ("count", C.c_uint32), ("saturated", C.c_uint64), ("sum", SphSum128 * 18)]
+
+
+class SphBodyValues(C.Structure):
+    _fields_ = [("mass", C.c_double), ("com", C.c_double * 3), ("velocity", C.c_double * 3), ("momentum", C.c_double * 3),
+                ("kinetic", C.c_double), ("kinetic_internal", C.c_double), ("mean_rho", C.c_double), ("mean_prs", C.c_double),
+                ("covariance", C.c_double * 6), ("gyration", C.c_double), ("angular", C.c_double * 3),
+                ("saturated", C.c_uint64)]
+
+
+class SphBodyMeasureStats(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("pad_", C.c_int32), ("calls", C.c_int64), ("seconds", C.c_double)]
+
+
+def body_moments_dtype():
+    """the numpy dtype of an SphBodyMomentsRaw row: label, count, saturated, and sum as (18, 2) uint64 -- [k, 0] the low
+    and [k, 1] the high word of sum k (two's complement; BODY_SUMS names the sums)"""
+    import numpy as np
+    return np.dtype([("label", "<u4"), ("count", "<u4"), ("saturated", "<u8"), ("sum", "<u8", (18, 2))])
+
+
+def body_values_dtype():
+    """the numpy dtype of an SphBodyValues"""
+    import numpy as np
+    return np.dtype([(name, "<u8" if name == "saturated" else "<f8", () if not hasattr(t, "_length_") else (t._length_,))
+                     for name, t in SphBodyValues._fields_])
+
+
+def body_values(moments, settings):
+    """sph_body_values over a structured array of raw rows (body_moments_dtype) -> a structured array of
+    body_values_dtype, one entry per body.  Pure host code: no GPU, no handle."""
+    import numpy as np
+    rows = np.ascontiguousarray(moments, dtype=body_moments_dtype()).reshape(-1)
+    out = np.zeros(len(rows), body_values_dtype())
+    rc = load_library().sph_body_values(rows.ctypes.data_as(C.POINTER(SphBodyMomentsRaw)), len(rows), C.byref(settings),
+                                        out.ctypes.data_as(C.POINTER(SphBodyValues)))
+    if rc:
+        raise SphError(f"sph_body_values failed ({rc})")
+    return out
+
+
 class SphNeighbourOptions(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("radius", C.c_float), ("flags", C.c_int32), ("pad_", C.c_int32),
                 ("max_entries", C.c_uint64)]
@@ -309,6 +359,10 @@ def load_library():
     L.sph_bodies_host.argtypes = [hp, C.POINTER(u32p), C.POINTER(C.c_int), C.POINTER(u32p), C.POINTER(C.c_int),
                                   C.POINTER(C.c_uint32)]
     L.sph_get_body_stats.argtypes = [hp, C.POINTER(SphBodyStats), C.c_int]
+    L.sph_measure_bodies.argtypes = [hp, C.POINTER(SphBodyMeasureOptions)]
+    L.sph_body_moments_host.argtypes = [hp, C.POINTER(C.POINTER(SphBodyMomentsRaw)), C.POINTER(C.c_int), C.POINTER(u32p)]
+    L.sph_body_values.argtypes = [C.POINTER(SphBodyMomentsRaw), C.c_int, C.POINTER(SphSettings), C.POINTER(SphBodyValues)]
+    L.sph_get_body_measure_stats.argtypes = [hp, C.POINTER(SphBodyMeasureStats), C.c_int]
     L.sph_neighbour_lists.argtypes = [hp, C.POINTER(SphNeighbourOptions)]
     L.sph_neighbours_host.argtypes = [hp, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(u32p), C.POINTER(C.c_int),
                                       C.POINTER(C.c_uint64)]

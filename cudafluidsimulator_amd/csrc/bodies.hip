@@ -22,12 +22,11 @@
 // Both paths then share mark + scan (which particle ids are labels, and how many labels lie below each: the scan of
 // scan_common.h) and the table launches.  Candidates are read from global memory on both paths (no LDS staging;
 // section 10g says why).
+#include "body_common.h"
 #include "scan_common.h"
 #include "walk_common.h"
 
 namespace {
-
-constexpr uint32_t kNoId = 0xFFFFFFFFu;
 
 // a load that is served by the device's coherent level, never by this CU's L1 (the forest and the check path's
 // labels change under the launch that reads them)
@@ -137,24 +136,7 @@ __global__ __launch_bounds__(256) void k_body_flatten(BodyArgs A) {
     if (gave) atomicAdd(&A.counters->gaveUp, 1u);
 }
 
-// The lanes of a wave that hold the same key as its first lane still in `rest`, taken out of `rest`: a wave's rows are
-// neighbours in the stream, so they fall into a few groups, and each group makes one set of atomics instead of one per
-// row (a body of millions of rows would otherwise put them all on one address).  Wave-uniform.
-__device__ __forceinline__ unsigned long long next_group(uint32_t key, bool valid, unsigned long long &rest, uint32_t &key0, int &lead) {
-    lead = __ffsll((long long)rest) - 1;
-    key0 = (uint32_t)__shfl((int)key, lead);
-    const unsigned long long grp = __ballot(valid && key == key0) & rest;
-    rest &= ~grp;
-    return grp;
-}
-
-// Launches that reduce rows onto bodies give a block kBodyFold x 256 consecutive rows and a few words of LDS for the
-// body (or root) of its first row: groups of that body are folded there and leave the block as one set of global
-// atomics, groups of any other body go to global memory directly.  A body of millions of rows then costs a set per
-// 2,048 rows instead of one per wave -- the atomics of one address are served one after the other.
-constexpr int kBodyFold = 8;
-
-// rootId[root] = the smallest particle id of the tree
+// rootId[root] = the smallest particle id of the tree (next_group, kBodyFold: body_common.h)
 __global__ __launch_bounds__(256) void k_body_root_id(BodyArgs A) {
     __shared__ uint32_t fold[2]; // the root of the block's first row, the smallest id seen under it
     const int base = blockIdx.x * (256 * kBodyFold);
@@ -304,8 +286,6 @@ __global__ __launch_bounds__(256) void k_body_table_finish(BodyArgs A, int numBo
     packed = wave_max_u64(packed);
     if ((threadIdx.x & 63) == 0 && packed) atomicMax(&A.counters->largest, packed);
 }
-
-inline int fold_blocks_of(int n) { return blocks_of(n, 256 * kBodyFold); }
 
 void launch_mark_and_scan(const BodyArgs &A, bool plain, hipStream_t s) {
     k_body_mark<<<blocks_of(A.S.n, 256), 256, 0, s>>>(A, plain);

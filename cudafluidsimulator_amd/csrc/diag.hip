@@ -9,32 +9,13 @@
 // keys and the saturation count in registers over a grid-stride loop, the wave reduces them with shuffles of the
 // 32-bit halves, the four waves of a workgroup meet in LDS, and the workgroup sends at most one integer atomic per
 // word.  The check path (SPH_DIAG_PLAIN=1) sends every term of every row straight to global atomics.
-#include "sph_c_api.h"
-#include "sph_device.h"
+#include "row_terms.h"
 
 namespace {
 
 constexpr int kDiagThreads = 256;
 constexpr int kDiagWaves = kDiagThreads / SPH_WAVE;
 constexpr int kDiagMaxBlocks = 1024; // 4 workgroups per CU: every lane takes ceil(n / 2^18) rows beyond that
-
-// q(t): NaN -> 0, t >= 2^31 -> INT64_MAX, t < -2^31 -> INT64_MIN (each counted in sat), else (int64)floor(t 2^32).
-// The scaling is exact, and the floor of a double below 2^63 in magnitude converts exactly.
-__device__ __forceinline__ long long diag_q(double t, uint32_t &sat) {
-    if (t != t) {
-        sat += 1u;
-        return 0ll;
-    }
-    if (t >= 2147483648.0) {
-        sat += 1u;
-        return 0x7FFFFFFFFFFFFFFFll;
-    }
-    if (t < -2147483648.0) {
-        sat += 1u;
-        return (long long)0x8000000000000000ull;
-    }
-    return (long long)floor(t * 4294967296.0);
-}
 
 // One row: its nine terms and the bit patterns of its six extrema candidates.
 struct DiagRow {
@@ -45,18 +26,7 @@ struct DiagRow {
 __device__ __forceinline__ DiagRow diag_row(const float4 p, const float4 v, uint32_t &sat) {
     DiagRow r;
     const uint32_t prsBits = field_bits(v, SPH_FIELD_PRESSURE);
-    r.q[SPH_DIAG_SUM_X] = diag_q((double)p.x, sat);
-    r.q[SPH_DIAG_SUM_Y] = diag_q((double)p.y, sat);
-    r.q[SPH_DIAG_SUM_Z] = diag_q((double)p.z, sat);
-    r.q[SPH_DIAG_SUM_VX] = diag_q((double)v.x, sat);
-    r.q[SPH_DIAG_SUM_VY] = diag_q((double)v.y, sat);
-    r.q[SPH_DIAG_SUM_VZ] = diag_q((double)v.z, sat);
-    r.q[SPH_DIAG_SUM_RHO] = diag_q((double)v.w, sat);
-    r.q[SPH_DIAG_SUM_PRS] = diag_q((double)__uint_as_float(prsBits), sat);
-    // (the three products are exact in fp64 -- 24 x 24 significant bits -- so a fused multiply-add would round the
-    // same two sums)
-    const double vx = (double)v.x, vy = (double)v.y, vz = (double)v.z;
-    r.q[SPH_DIAG_SUM_V2] = diag_q((vx * vx + vy * vy) + vz * vz, sat);
+    diag_sum_terms(p, v, prsBits, r.q, sat); // (row_terms.h)
     r.b[SPH_DIAG_EXT_X] = __float_as_uint(p.x);
     r.b[SPH_DIAG_EXT_Y] = __float_as_uint(p.y);
     r.b[SPH_DIAG_EXT_Z] = __float_as_uint(p.z);

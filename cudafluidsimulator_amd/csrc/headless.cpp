@@ -225,6 +225,40 @@ static bool write_bodies(Simulator *simulator, const char *dir, int f, float lin
     return ok;
 }
 
+// SPH_FREE_BODY_TABLE=<f>, f in (0, 1], the link length in units of h: beside each written frame the bodies' moments
+// (sph_measure_bodies, sph_body_values) as <dir>/body_table_%04d.jsonl: one JSON line per body in label order with
+// `label`, `count` and every field of SphBodyValues; doubles as %.17g, which reads back to the same double.
+static void put_doubles(FILE *out, const char *name, const double *v, int k) {
+    fprintf(out, ", \"%s\": [", name);
+    for (int i = 0; i < k; ++i) fprintf(out, i ? ", %.17g" : "%.17g", v[i]);
+    fputc(']', out);
+}
+static bool write_body_table(Simulator *simulator, const char *dir, int f, float link) {
+    const SphBodyMomentsRaw *rows = NULL;
+    int bodies = 0;
+    if (!simulator->measureBodies(link, &rows, &bodies, NULL)) return false;
+    std::vector<SphBodyValues> values((size_t)(bodies > 0 ? bodies : 0));
+    SphSettings s; // (Settings and SphSettings share their layout)
+    memcpy(&s, simulator->settings, sizeof s);
+    if (sph_body_values(rows, bodies, &s, values.data()) != SPH_OK) return false;
+    FILE *out = open_out(dir, "body_table_%04d.jsonl", f);
+    if (!out) return false;
+    for (int b = 0; b < bodies; ++b) {
+        const SphBodyValues &v = values[(size_t)b];
+        fprintf(out, "{\"label\": %u, \"count\": %u, \"mass\": %.17g", rows[b].label, rows[b].count, v.mass);
+        put_doubles(out, "com", v.com, 3);
+        put_doubles(out, "velocity", v.velocity, 3);
+        put_doubles(out, "momentum", v.momentum, 3);
+        fprintf(out, ", \"kinetic\": %.17g, \"kinetic_internal\": %.17g, \"mean_rho\": %.17g, \"mean_prs\": %.17g", v.kinetic,
+                v.kinetic_internal, v.mean_rho, v.mean_prs);
+        put_doubles(out, "covariance", v.covariance, 6);
+        fprintf(out, ", \"gyration\": %.17g", v.gyration);
+        put_doubles(out, "angular", v.angular, 3);
+        fprintf(out, ", \"saturated\": %llu}\n", (unsigned long long)v.saturated);
+    }
+    return fclose(out) == 0;
+}
+
 // SPH_FREE_NEIGHBOURS=<f>, f in (0, 1], the radius in units of h: beside each written frame every particle's
 // neighbours within that radius (sph_neighbour_lists) as <dir>/neighbours_%04d.bin: the 8 bytes `SPHNBR01`, uint32 n,
 // uint32 0, uint64 entries, the n + 1 uint64 offsets, the uint32 ids, all little-endian; and one line on stderr,
@@ -305,6 +339,16 @@ void startVisualization(Simulator *simulator) {
         else
             bodyLink = v * simulator->settings->h;
     }
+    float bodyTableLink = 0.f; // 0: no body tables
+    if (framesDir && getenv("SPH_FREE_BODY_TABLE")) {
+        const char *e = getenv("SPH_FREE_BODY_TABLE");
+        char *end = NULL;
+        const float v = strtof(e, &end);
+        if (end == e || *end || !std::isfinite(v) || !(v > 0.f) || v > 1.f)
+            fprintf(stderr, "sph: SPH_FREE_BODY_TABLE=%s is not a link length in (0, 1] (units of h) -- writing no body tables\n", e);
+        else
+            bodyTableLink = v * simulator->settings->h;
+    }
     float neighbourRadius = 0.f; // 0: no neighbour files
     if (framesDir && getenv("SPH_FREE_NEIGHBOURS")) {
         const char *e = getenv("SPH_FREE_NEIGHBOURS");
@@ -331,6 +375,7 @@ void startVisualization(Simulator *simulator) {
         if (framesDir && tracers > 0 && f % every == 0 && !write_tracers(simulator, framesDir, f)) tracers = 0;
         if (framesDir && particles && f % every == 0 && !write_particles(simulator, framesDir, f)) particles = false;
         if (framesDir && bodyLink > 0.f && f % every == 0 && !write_bodies(simulator, framesDir, f, bodyLink)) bodyLink = 0.f;
+        if (framesDir && bodyTableLink > 0.f && f % every == 0 && !write_body_table(simulator, framesDir, f, bodyTableLink)) bodyTableLink = 0.f;
         if (framesDir && neighbourRadius > 0.f && f % every == 0 && !write_neighbours(simulator, framesDir, f, neighbourRadius))
             neighbourRadius = 0.f;
         if (framesDir && f % every == 0 && !write_frame(simulator, framesDir, f, field)) framesDir = NULL;

@@ -269,6 +269,25 @@ bool Simulator::labelBodies(float link, const uint32_t **labels, const uint32_t 
     return true;
 }
 
+bool Simulator::measureBodies(float link, const SphBodyMomentsRaw **rows, int *numBodies, const uint32_t **sizeHist) {
+    if (multi) {
+        fprintf(stderr, "sph: measureBodies: a multi-GPU run (SPH_GPUS > 1) labels no bodies\n");
+        return false;
+    }
+    if (!impl) return false;
+    SphBodyMeasureOptions o = {};
+    o.struct_size = (int32_t)sizeof o;
+    o.link = link;
+    const int rc = sph_measure_bodies(impl, &o);
+    if (rc == SPH_ESTATE || rc == SPH_EINVAL || rc == SPH_ENOMEM) { // (SPH_SWEEP=linked, a link longer than h, ...): nothing computed, nothing broken
+        fprintf(stderr, "sph: measureBodies: %s\n", sph_last_error(impl));
+        return false;
+    }
+    check(impl, rc, "sph_measure_bodies");
+    check(impl, sph_body_moments_host(impl, rows, numBodies, sizeHist), "sph_body_moments_host");
+    return true;
+}
+
 bool Simulator::neighbourLists(float radius, const uint64_t **offsets, const uint32_t **neighbours, uint64_t *entries) {
     if (multi) {
         fprintf(stderr, "sph: neighbourLists: a multi-GPU run (SPH_GPUS > 1) lists no neighbours\n");

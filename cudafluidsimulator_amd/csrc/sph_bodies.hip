@@ -45,17 +45,12 @@ int body_fetch_counters(sph_handle *h) {
 
 } // namespace
 
-extern "C" {
+namespace sph_host {
 
-int sph_label_bodies(sph_handle *h, const SphBodyOptions *opt) {
-    if (!h) return SPH_EINVAL;
-    SPH_ON_DEVICE(h);
-    int rc = analysis_begin(h, "the bodies' labelling", ": multi-GPU runs label no bodies");
-    if (rc) return rc;
-    SphBodyOptions o{};
-    if ((rc = copy_options(h, opt, o, "SphBodyOptions.struct_size is not set"))) return rc;
-    if (!std::isfinite(o.link) || o.link < 0.f || o.link > h->P.h) return fail(h, SPH_EINVAL, "link must be 0 (= h) or finite with 0 < link <= h");
-    const float link = o.link == 0.f ? h->P.h : o.link;
+int label_bodies(sph_handle *h, float linkOption, const char *who) {
+    int rc;
+    if (!std::isfinite(linkOption) || linkOption < 0.f || linkOption > h->P.h) return fail(h, SPH_EINVAL, "link must be 0 (= h) or finite with 0 < link <= h");
+    const float link = linkOption == 0.f ? h->P.h : linkOption;
     const int n = h->n;
     if (n == 0) { // nothing to sweep, nothing to copy
         if ((rc = outbound_fence(h, h->body.out))) return rc;
@@ -98,9 +93,9 @@ int sph_label_bodies(sph_handle *h, const SphBodyOptions *opt) {
     h->body.calls += 1;
     h->bodyRounds += rounds;
     h->bodyGaveUp += C.gaveUp;
-    if (C.gaveUp) return fail(h, SPH_EHIP, "sph_label_bodies: a bounded loop of the union-find ran out of trips; no results");
+    if (C.gaveUp) return fail(h, SPH_EHIP, std::string(who) + ": a bounded loop of the union-find ran out of trips; no results");
     const size_t bodies = C.numBodies;
-    if (bodies == 0 || bodies > (size_t)n) return fail(h, SPH_EHIP, "sph_label_bodies: the particle ids are not a permutation of [0, n)");
+    if (bodies == 0 || bodies > (size_t)n) return fail(h, SPH_EHIP, std::string(who) + ": the particle ids are not a permutation of [0, n)");
     h->bodyLinks += C.links;
     h->bodyUnions += plain ? (unsigned long long)n - bodies : C.unions;
     if ((rc = body_reserve_table(h, bodies))) return rc;
@@ -114,6 +109,20 @@ int sph_label_bodies(sph_handle *h, const SphBodyOptions *opt) {
     h->bodyCount = (int)bodies;
     h->body.valid = true;
     return SPH_OK;
+}
+
+} // namespace sph_host
+
+extern "C" {
+
+int sph_label_bodies(sph_handle *h, const SphBodyOptions *opt) {
+    if (!h) return SPH_EINVAL;
+    SPH_ON_DEVICE(h);
+    int rc = analysis_begin(h, "the bodies' labelling", ": multi-GPU runs label no bodies");
+    if (rc) return rc;
+    SphBodyOptions o{};
+    if ((rc = copy_options(h, opt, o, "SphBodyOptions.struct_size is not set"))) return rc;
+    return label_bodies(h, o.link, "sph_label_bodies");
 }
 
 int sph_bodies_host(sph_handle *h, const uint32_t **labels, int *n, const uint32_t **table, int *num_bodies, uint32_t *largest) {

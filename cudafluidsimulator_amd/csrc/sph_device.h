@@ -405,6 +405,24 @@ void sph_launch_bodies_plain_end(const BodyArgs &A, hipStream_t s);
 // both paths: the table of numBodies rows, labels in id order, counters->largest
 void sph_launch_bodies_table(const BodyArgs &A, int numBodies, hipStream_t s);
 
+// ---- per-body moments (body_moments.hip; defined in DESIGN.md section 10k) ----
+// A body's row is kBodyMomentStride 64-bit words, on the device and as SphBodyMomentsRaw.  While the rows are reduced
+// it holds the accumulators -- [0, 18) the sums of the terms' low words, [18, 36) of their arithmetic high words, [36]
+// the saturation count --, written by integer atomics only; the finish launch rewrites it in place as the raw row.
+constexpr int kBodyMomentWords = 2 * SPH_BODY_SUMS + 1; // 37
+constexpr int kBodyMomentStride = 38;
+struct BodyMomentArgs {
+    StreamView S;                 // the rows, n > 0
+    const uint32_t *rowLabel;     // [n] the labelling's label of every row ...
+    const uint32_t *rank;         // [n] ... its table row per label ...
+    const uint32_t *table;        // [8 numBodies] ... and the table itself (label, count, ...)
+    int numBodies;                // > 0
+    unsigned long long *rows;     // [kBodyMomentStride numBodies] the result
+    uint32_t *sizeHist;           // [SPH_BODY_SIZE_BINS] the result
+};
+// clear + reduce + finish; plain = the one-thread-per-row, one-atomic-per-word check path
+void sph_launch_body_moments(const BodyMomentArgs &A, bool plain, hipStream_t s);
+
 // ---- neighbour lists: every particle's neighbours within a radius, as CSR (neighbours.hip) ----
 struct NeighbourArgs {
     StreamView S;            // the rows and their candidates, n > 0 (the velocities are not read)

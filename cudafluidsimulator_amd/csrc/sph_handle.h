@@ -46,7 +46,8 @@ using sph_owned::PinnedBuf;
 //   SPH_SURFACE_PLAIN     0        call    non-zero: sph_extract_surface takes the check path, for its sample and its extraction
 //   SPH_TRACER_PLAIN      0        call    non-zero: sph_tracers_advect takes the one-thread-per-tracer check path
 //   SPH_DERIVE_PLAIN      0        call    non-zero: sph_derive takes the one-thread-per-row check path
-//   SPH_BODIES_PLAIN      0        call    non-zero: sph_label_bodies takes the check path (min-label propagation in rounds)
+//   SPH_BODIES_PLAIN      0        call    non-zero: sph_label_bodies takes the check path (min-label propagation in rounds),
+//                                          and sph_measure_bodies with it, for its labelling and for its moments (one atomic per word)
 //   SPH_NEIGHBOURS_PLAIN  0        call    non-zero: sph_neighbour_lists takes the check path (one thread per row, one per list)
 //   SPH_NEIGHBOURS_TIME_PHASE 0    call    1 count, 2 scan, 3 emit, 4 sort: SphNeighbourStats.seconds sums that phase alone
 //                                          (scripts/studies/neighbours.py); 0: all four
@@ -340,6 +341,17 @@ struct sph_handle {
     sph_host::Pass body;             // out: the results on their way to the pinned buffers; seconds: every kernel of the call
     unsigned long long bodyLinks = 0, bodyUnions = 0, bodyRounds = 0, bodyGaveUp = 0; // sums over calls
 
+    // ---- sph_body_moments.hip ----
+    // Per-body moments (body_moments.hip): one row of kBodyMomentStride words per body and the 32 size bins, on the
+    // device and in pinned memory; the rows grow on demand by sph_measure_bodies, the bins come with its first call.
+    sph_host::DeviceBuf<unsigned long long> momentRows;
+    sph_host::PinnedBuf<unsigned long long> momentRowsHost;
+    sph_host::DeviceBuf<uint32_t> momentHist;
+    sph_host::PinnedBuf<uint32_t> momentHistHost;
+    size_t momentCap = 0;            // bodies either row buffer holds
+    int momentCount = 0;             // bodies of the last sph_measure_bodies
+    sph_host::Pass moment;           // out: rows and bins on their way to the pinned buffers; seconds: the moment launches alone
+
     // ---- sph_neighbours.hip ----
     // Neighbour lists (neighbours.hip): the length of every list and the CSR offsets in id order, the scan's block sums,
     // the lists themselves, the two words the call waits for (the total, the longest list), and the pinned copies of
@@ -404,7 +416,7 @@ int outbound_fence(sph_handle *h, Outbound &o);
 int outbound_send(sph_handle *h, Outbound &o, std::initializer_list<OutboundCopy> copies);
 hipError_t outbound_wait(const Outbound &o);
 // What the passes over the grid's sorted stream share (the field sample, the surface mesh, the tracers, the derived
-// fields, the bodies, the neighbour lists).  analysis_begin: the state checks, in this order -- a slab handle (`slab_hint` ends that message),
+// fields, the bodies and their moments, the neighbour lists).  analysis_begin: the state checks, in this order -- a slab handle (`slab_hint` ends that message),
 // no state yet, SPH_SWEEP_LINKED, SPH_KEY_MORTON, a phase-split step still open; `what` names the pass in the messages.
 // analysis_grid: a grid of the state the handle holds NOW.  Phase 1: it exists (sph_phase_grid, or built ahead by a
 // timed step).  Phase 0: the table of the last step is the pre-integration one; the next step's grid is built here,
@@ -439,6 +451,10 @@ int timed_launch(sph_handle *h, double *seconds, F &&launch) {
 // the smallest dimension allowed differs) and its kernel arguments over the stream of the current grid
 const char *bad_lattice(int nx, int ny, int nz, const float (&origin)[3], const float (&spacing)[3], int minDim);
 SampleArgs lattice_args(const sph_handle *h, int nx, int ny, int nz, const float (&origin)[3], const float (&spacing)[3], int field);
+// sph_bodies.hip: all of sph_label_bodies behind its state checks and its options' copy -- the link's check, the
+// labelling of the state the handle holds now on either path, the table, the copies, the SphBodyStats accounting.
+// `who` names the entry point in the messages.  sph_measure_bodies (sph_body_moments.hip) labels through it too.
+int label_bodies(sph_handle *h, float link, const char *who);
 // sph_readback.hip
 void sdma_init(sph_handle *h);
 int sdma_wait(sph_handle *h, int slot);

@@ -452,6 +452,39 @@ class Simulator:
         self._check(self._L.sph_get_body_stats(self._h, C.byref(st), 1 if reset else 0), "sph_get_body_stats")
         return dict(calls=st.calls, links=st.links, unions=st.unions, rounds=st.rounds, gave_up=st.gave_up, seconds=st.seconds)
 
+    # -- per-body moments: mass, momentum, spin and shape of every body (sph_measure_bodies) --
+    def measure_bodies(self, link=0.0, max_bodies=0):
+        """label_bodies()'s dict of the current state plus "moments": a structured array of their own of the raw rows
+        (_lib.body_moments_dtype(): label, count, saturated, sum (18, 2) uint64 low / high words of the exact Q32.32
+        sums named by _lib.BODY_SUMS), one per body in the table's order, and "size_hist": (32,) uint32, the number
+        of bodies with floor(log2(count)) == b.  The moments of more than `max_bodies` bodies (0: no cap) are refused.
+        body_values() turns the rows into floats."""
+        opt = _lib.SphBodyMeasureOptions(C.sizeof(_lib.SphBodyMeasureOptions), link, int(max_bodies), 0)
+        self._check(self._L.sph_measure_bodies(self._h, C.byref(opt)), "sph_measure_bodies")
+        lab, tab, n, k, big = C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint32)(), C.c_int(0), C.c_int(0), C.c_uint32(0)
+        self._check(self._L.sph_bodies_host(self._h, C.byref(lab), C.byref(n), C.byref(tab), C.byref(k), C.byref(big)), "sph_bodies_host")
+        rows, m, hist = C.POINTER(_lib.SphBodyMomentsRaw)(), C.c_int(0), C.POINTER(C.c_uint32)()
+        self._check(self._L.sph_body_moments_host(self._h, C.byref(rows), C.byref(m), C.byref(hist)), "sph_body_moments_host")
+        words = _rows(C.cast(rows, C.POINTER(C.c_uint64)), m.value, C.sizeof(_lib.SphBodyMomentsRaw) // 8, np.uint64)
+        return dict(labels=_rows(lab, n.value, None, np.uint32), table=_rows(tab, k.value, 8, np.uint32),
+                    num_bodies=k.value, largest=big.value,
+                    moments=words.view(_lib.body_moments_dtype()).reshape(-1),
+                    size_hist=_rows(hist, _lib.BODY_SIZE_BINS, None, np.uint32))
+
+    def body_values(self, moments):
+        """The floats behind measure_bodies()["moments"], a structured array (_lib.body_values_dtype()) with one entry
+        per body: mass, com, velocity, momentum, kinetic, kinetic_internal (less the energy of the body moving as a
+        whole), mean_rho, mean_prs, covariance (xx yy zz xy xz yz of the positions about com), gyration, angular
+        (about com) and saturated.  Pure host code."""
+        return _lib.body_values(moments, self.settings)
+
+    def body_measure_stats(self, reset=False):
+        """dict(calls, seconds): sums since create or the last reset; `seconds` is the GPU time of the moment launches
+        alone (the labelling's is body_stats()["seconds"])."""
+        st = _lib.SphBodyMeasureStats()
+        self._check(self._L.sph_get_body_measure_stats(self._h, C.byref(st), 1 if reset else 0), "sph_get_body_measure_stats")
+        return dict(calls=st.calls, seconds=st.seconds)
+
     # -- neighbour lists: every particle's neighbours within a radius, as CSR (sph_neighbour_lists) --
     def neighbour_lists(self, radius=0.0, walk_order=False, max_entries=0):
         """{"offsets": (n + 1,) uint64, "neighbours": (entries,) uint32}: arrays of their own.  The neighbours of

@@ -67,6 +67,7 @@ struct sph_handle;
 struct sph_mgpu;
 struct SphDiagnostics;    // include/sph_c_api.h
 struct SphDiagnosticsRaw;
+struct SphBodyMomentsRaw;
 
 class Simulator {
   private:
@@ -131,6 +132,12 @@ class Simulator {
     // body with the most particles.  Any out-pointer may be NULL.  false (with a message on stderr) with SPH_GPUS > 1
     // and where the library answers SPH_ESTATE or SPH_EINVAL.
     bool labelBodies(float link, const uint32_t **labels, const uint32_t **table, int *numBodies, uint32_t *largest);
+    // The moments of the bodies of the current state (sph_measure_bodies in sph_c_api.h): labels them as labelBodies
+    // does, then numBodies raw rows in the table's order -- label, count, the exact sums; sph_body_values derives
+    // mass, centre, momentum, energies, covariance and angular momentum from them -- and the 32 bins of the size
+    // distribution, owned by the simulator, valid until the next measureBodies.  Any out-pointer may be NULL.  false
+    // (with a message on stderr) with SPH_GPUS > 1 and where the library answers SPH_ESTATE, SPH_EINVAL or SPH_ENOMEM.
+    bool measureBodies(float link, const SphBodyMomentsRaw **rows, int *numBodies, const uint32_t **sizeHist);
     // The neighbour lists of the current state (sph_neighbour_lists in sph_c_api.h) as CSR in particle-id order: the
     // neighbours of particle i -- the particles within `radius` of it (0: h; else 0 < radius <= h), in ascending id
     // order -- are neighbours[offsets[i]] .. neighbours[offsets[i + 1] - 1]; n + 1 offsets, *entries ids, owned by the

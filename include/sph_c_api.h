@@ -755,6 +755,73 @@ typedef struct SphBodyStats {
 /* Sums since create or since the last reset.  Blocks. */
 int sph_get_body_stats(sph_handle *h, SphBodyStats *out, int reset);
 
+/* ---- per-body moments: mass, momentum, spin and shape of every body ----
+ * Additive to version 3: test for SPH_HAS_BODY_MOMENTS.  Defined to the bit in DESIGN.md section 10k ("Body
+ * moments").  The join of the bodies and the diagnostics: per body of sph_label_bodies, eighteen sums of the
+ * diagnostics' Q32.32 terms q(t) over the body's rows (the rows sph_download_state returns), integers only, with the
+ * diagnostics' NaN and saturation rules, reported as SphSum128.  Sums 0-8 are SPH_DIAG_SUM_*, same indices, same
+ * terms.  The term of XX .. YZ is (double)a (double)b, exact in fp64; that of LX is (double)y vz - (double)z vy, of LY
+ * (double)z vx - (double)x vz, of LZ (double)x vy - (double)y vx: both products exact, one rounding, by the
+ * subtraction.  The words depend on the set of rows of each body only: the same for any schedule, kernel path or sweep
+ * backend. */
+#define SPH_HAS_BODY_MOMENTS 1
+enum { /* indices of SphBodyMomentsRaw.sum beyond SPH_DIAG_SUM_* */
+    SPH_BODY_SUM_XX = 9, SPH_BODY_SUM_YY = 10, SPH_BODY_SUM_ZZ = 11,
+    SPH_BODY_SUM_XY = 12, SPH_BODY_SUM_XZ = 13, SPH_BODY_SUM_YZ = 14,
+    SPH_BODY_SUM_LX = 15, SPH_BODY_SUM_LY = 16, SPH_BODY_SUM_LZ = 17,
+    SPH_BODY_SUMS = 18
+};
+#define SPH_BODY_SIZE_BINS 32
+typedef struct SphBodyMeasureOptions {
+    int32_t struct_size;        /* sizeof(SphBodyMeasureOptions) */
+    float link;                 /* as SphBodyOptions.link */
+    uint32_t max_bodies;        /* the call refuses the moments of more bodies; 0 = no cap */
+    int32_t pad_;               /* 0 */
+} SphBodyMeasureOptions;
+typedef struct SphBodyMomentsRaw { /* 304 bytes */
+    uint32_t label, count;      /* the label table's */
+    uint64_t saturated;         /* terms of the body that took a NaN or saturating branch */
+    SphSum128 sum[SPH_BODY_SUMS];
+} SphBodyMomentsRaw;
+/* The derived values of one body (DESIGN.md section 10k gives every expression; Python floats reproduce them bit for
+ * bit).  A body of one particle: covariance and kinetic_internal are rounding residue around 0, either sign. */
+typedef struct SphBodyValues {
+    double mass;                /* count MASS */
+    double com[3];              /* centre of mass */
+    double velocity[3];         /* mean velocity */
+    double momentum[3];         /* MASS sum(v) */
+    double kinetic;             /* 0.5 MASS sum(v^2) */
+    double kinetic_internal;    /* ... less the kinetic energy of the body moving as a whole */
+    double mean_rho, mean_prs;
+    double covariance[6];       /* of the positions about com: xx yy zz xy xz yz */
+    double gyration;            /* radius of gyration: sqrt(max(0, trace)) */
+    double angular[3];          /* angular momentum about com */
+    uint64_t saturated;
+} SphBodyValues;
+/* Labels the state the handle holds NOW exactly as sph_label_bodies does -- the same state rules, error codes, grid
+ * handling, both paths, the same SphBodyStats accounting; sph_bodies_host afterwards serves this labelling -- and then
+ * queues the moment launches over that labelling and the copies of their results; labels and moments are always of
+ * the same state.  opt == NULL: link = h, no cap.  SPH_EINVAL also for a non-zero pad_.  More bodies than a non-zero
+ * max_bodies: SPH_ENOMEM, the message names both numbers, nothing is allocated for the refused moments and the handle
+ * holds no moments (the labelling stands).  A raw row is 304 bytes, on the device and in pinned memory.  No
+ * particles: SPH_OK, no bodies.  SPH_BODIES_PLAIN=1 selects the check path of the moments too (one thread per row,
+ * every term a global integer atomic; identical words). */
+int sph_measure_bodies(sph_handle *h, const SphBodyMeasureOptions *opt);
+/* The results of the last sph_measure_bodies, owned by the handle, valid until the next one: num_bodies rows in the
+ * label table's order (ascending label), and size_hist = SPH_BODY_SIZE_BINS words, size_hist[b] the number of bodies
+ * with floor(log2(count)) == b.  Blocks until the copies have landed.  Any out-pointer may be NULL; *rows may be NULL
+ * without bodies.  SPH_ESTATE before the first sph_measure_bodies and after one that was refused. */
+int sph_body_moments_host(sph_handle *h, const SphBodyMomentsRaw **rows, int *num_bodies, const uint32_t **size_hist);
+/* Pure host code, no GPU and no handle: out[b] = the derived values of rows[b], b < num_bodies. */
+int sph_body_values(const SphBodyMomentsRaw *rows, int num_bodies, const SphSettings *settings, SphBodyValues *out);
+typedef struct SphBodyMeasureStats {
+    int32_t struct_size, pad_;  /* sizeof(SphBodyMeasureStats), 0: both written by the call */
+    int64_t calls;              /* calls that queued moment launches (either path) */
+    double seconds;             /* GPU time of the moment launches alone (the labelling's: SphBodyStats.seconds) */
+} SphBodyMeasureStats;
+/* Sums since create or since the last reset.  Blocks. */
+int sph_get_body_measure_stats(sph_handle *h, SphBodyMeasureStats *out, int reset);
+
 /* ---- neighbour lists: every particle's neighbours within a radius, as CSR in particle-id order ----
  * Additive to version 3: test for SPH_HAS_NEIGHBOURS.  Defined to the bit in DESIGN.md section 10j ("Neighbour
  * lists"); all fp32, every operation rounded on its own, in both math modes.  With r2 = radius radius, particle j is a
