@@ -35,6 +35,7 @@ EXPORTED_SYMBOLS = [
     "sph_derive", "sph_derived_host", "sph_get_derive_stats",
     "sph_label_bodies", "sph_bodies_host", "sph_get_body_stats",
     "sph_measure_bodies", "sph_body_moments_host", "sph_body_values", "sph_get_body_measure_stats",
+    "sph_track_bodies", "sph_body_tracks_host", "sph_track_reset", "sph_get_body_track_stats",
     "sph_neighbour_lists", "sph_neighbours_host", "sph_get_neighbour_stats",
 ]
 SPH_API_VERSION = 3
@@ -53,6 +54,11 @@ MAX_TRACERS = 1 << 24
 SPH_HAS_DERIVED = 1
 SPH_HAS_BODIES = 1
 SPH_HAS_BODY_MOMENTS = 1
+SPH_HAS_BODY_TRACKS = 1
+SPH_TRACK_WITH_MOMENTS = 1
+SPH_EDGE_MAIN_PARENT, SPH_EDGE_MAIN_CHILD = 1, 2
+SPH_TRACK_CONTINUES, SPH_TRACK_BORN, SPH_TRACK_MERGED = 1, 2, 4
+SPH_FATE_CONTINUES, SPH_FATE_ENDED, SPH_FATE_SPLIT = 1, 2, 4
 SPH_HAS_NEIGHBOURS = 1
 SPH_NEIGHBOURS_WALK_ORDER = 1
 BODY_TABLE = ("label", "count", "min_x", "min_y", "min_z", "max_x", "max_y", "max_z")   # words of a table row
@@ -246,6 +252,60 @@ def body_values(moments, settings):
     return out
 
 
+class SphBodyTrackOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("link", C.c_float), ("max_edges", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class SphBodyEdge(C.Structure):
+    _fields_ = [("prev", C.c_uint32), ("cur", C.c_uint32), ("count", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class SphBodyTrack(C.Structure):
+    _fields_ = [("track", C.c_uint64), ("parents", C.c_uint32), ("main_parent", C.c_uint32), ("main_overlap", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
+class SphBodyFate(C.Structure):
+    _fields_ = [("track", C.c_uint64), ("label", C.c_uint32), ("count", C.c_uint32), ("children", C.c_uint32),
+                ("main_child", C.c_uint32), ("main_overlap", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class SphBodyTrackSummary(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("pad_", C.c_int32), ("previous_bodies", C.c_uint32), ("bodies", C.c_uint32),
+                ("edges", C.c_uint32), ("continued", C.c_uint32), ("born", C.c_uint32), ("ended", C.c_uint32),
+                ("merges", C.c_uint32), ("splits", C.c_uint32), ("next_track", C.c_uint64), ("sequence", C.c_uint64)]
+
+
+class SphBodyTrackStats(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("pad_", C.c_int32), ("calls", C.c_int64), ("partials", C.c_uint64),
+                ("edges", C.c_uint64), ("seconds", C.c_double)]
+
+
+TRACK_SUMMARY = ("previous_bodies", "bodies", "edges", "continued", "born", "ended", "merges", "splits", "next_track", "sequence")
+
+
+def _struct_dtype(struct):
+    import numpy as np
+    kinds = {C.c_uint32: "<u4", C.c_uint64: "<u8"}
+    return np.dtype([(name, kinds[t]) for name, t in struct._fields_])
+
+
+def body_edge_dtype():
+    """the numpy dtype of an SphBodyEdge: prev, cur (rows of the two tables), count, flags"""
+    return _struct_dtype(SphBodyEdge)
+
+
+def body_track_dtype():
+    """the numpy dtype of an SphBodyTrack (one per current body): track, parents, main_parent, main_overlap, flags"""
+    return _struct_dtype(SphBodyTrack)
+
+
+def body_fate_dtype():
+    """the numpy dtype of an SphBodyFate (one per previous body): track, label, count, children, main_child,
+    main_overlap, flags"""
+    return _struct_dtype(SphBodyFate)
+
+
 class SphNeighbourOptions(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("radius", C.c_float), ("flags", C.c_int32), ("pad_", C.c_int32),
                 ("max_entries", C.c_uint64)]
@@ -363,6 +423,12 @@ def load_library():
     L.sph_body_moments_host.argtypes = [hp, C.POINTER(C.POINTER(SphBodyMomentsRaw)), C.POINTER(C.c_int), C.POINTER(u32p)]
     L.sph_body_values.argtypes = [C.POINTER(SphBodyMomentsRaw), C.c_int, C.POINTER(SphSettings), C.POINTER(SphBodyValues)]
     L.sph_get_body_measure_stats.argtypes = [hp, C.POINTER(SphBodyMeasureStats), C.c_int]
+    L.sph_track_bodies.argtypes = [hp, C.POINTER(SphBodyTrackOptions)]
+    L.sph_body_tracks_host.argtypes = [hp, C.POINTER(C.POINTER(SphBodyTrack)), C.POINTER(C.c_int), C.POINTER(C.POINTER(SphBodyFate)),
+                                       C.POINTER(C.c_int), C.POINTER(C.POINTER(SphBodyEdge)), C.POINTER(C.c_int),
+                                       C.POINTER(SphBodyTrackSummary)]
+    L.sph_track_reset.argtypes = [hp]
+    L.sph_get_body_track_stats.argtypes = [hp, C.POINTER(SphBodyTrackStats), C.c_int]
     L.sph_neighbour_lists.argtypes = [hp, C.POINTER(SphNeighbourOptions)]
     L.sph_neighbours_host.argtypes = [hp, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(u32p), C.POINTER(C.c_int),
                                       C.POINTER(C.c_uint64)]

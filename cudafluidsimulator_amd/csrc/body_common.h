@@ -1,5 +1,5 @@
 // What the launches that reduce rows onto bodies share (bodies.hip: the roots' ids and the table; body_moments.hip:
-// the moments): the split of a wave's rows into groups of equal body and the shape of a folding block.  DESIGN.md
+// the moments; body_tracks.hip: the partial edges): the split of a wave's rows into groups of equal body and the shape of a folding block.  DESIGN.md
 // sections 10g, 10k.  Device code only.
 #pragma once
 
@@ -14,6 +14,17 @@ __device__ __forceinline__ unsigned long long next_group(uint32_t key, bool vali
     lead = __ffsll((long long)rest) - 1;
     key0 = (uint32_t)__shfl((int)key, lead);
     const unsigned long long grp = __ballot(valid && key == key0) & rest;
+    rest &= ~grp;
+    return grp;
+}
+
+// The same for a key of two words (body_tracks.hip: a row's previous and current body).
+__device__ __forceinline__ unsigned long long next_group(uint32_t keyA, uint32_t keyB, bool valid, unsigned long long &rest, uint32_t &a0,
+                                                         uint32_t &b0, int &lead) {
+    lead = __ffsll((long long)rest) - 1;
+    a0 = (uint32_t)__shfl((int)keyA, lead);
+    b0 = (uint32_t)__shfl((int)keyB, lead);
+    const unsigned long long grp = __ballot(valid && keyA == a0 && keyB == b0) & rest;
     rest &= ~grp;
     return grp;
 }

@@ -259,6 +259,42 @@ static bool write_body_table(Simulator *simulator, const char *dir, int f, float
     return fclose(out) == 0;
 }
 
+// SPH_FREE_BODY_TRACKS=<f>, f in (0, 1], the link length in units of h: beside each written frame the bodies' tracks
+// (sph_track_bodies; the reference is the previous written frame) as <dir>/body_tracks_%04d.jsonl: a line with the frame
+// number and every field of the summary, one line per body in table order, one line per edge with `prev` and `cur` as
+// labels; and one line on stderr, `tracks <frame> <bodies> <continued> <born> <ended> <merges> <splits>`.
+static bool write_body_tracks(Simulator *simulator, const char *dir, int f, float link) {
+    const uint32_t *table = NULL;
+    const SphBodyTrack *tracks = NULL;
+    const SphBodyFate *previous = NULL;
+    const SphBodyEdge *edges = NULL;
+    int bodies = 0, before = 0, numEdges = 0;
+    SphBodyTrackSummary s;
+    if (!simulator->trackBodies(link, &table, &tracks, &bodies, &previous, &before, &edges, &numEdges, &s)) return false;
+    FILE *out = open_out(dir, "body_tracks_%04d.jsonl", f);
+    if (!out) return false;
+    fprintf(out,
+            "{\"frame\": %d, \"previous_bodies\": %u, \"bodies\": %u, \"edges\": %u, \"continued\": %u, \"born\": %u, \"ended\": %u, "
+            "\"merges\": %u, \"splits\": %u, \"next_track\": %llu, \"sequence\": %llu}\n",
+            f, s.previous_bodies, s.bodies, s.edges, s.continued, s.born, s.ended, s.merges, s.splits, (unsigned long long)s.next_track,
+            (unsigned long long)s.sequence);
+    for (int b = 0; b < bodies; ++b) {
+        const SphBodyTrack &t = tracks[b];
+        fprintf(out, "{\"label\": %u, \"count\": %u, \"track\": %llu, \"parents\": %u, \"main_parent\": ", table[8 * (size_t)b],
+                table[8 * (size_t)b + 1], (unsigned long long)t.track, t.parents);
+        if (t.parents && t.main_parent < (uint32_t)before) fprintf(out, "%u", previous[t.main_parent].label);
+        else fputs("null", out);
+        fprintf(out, ", \"main_overlap\": %u, \"continues\": %s}\n", t.main_overlap, (t.flags & SPH_TRACK_CONTINUES) ? "true" : "false");
+    }
+    for (int e = 0; e < numEdges; ++e)
+        fprintf(out, "{\"prev\": %u, \"cur\": %u, \"count\": %u, \"main_parent\": %s, \"main_child\": %s}\n", previous[edges[e].prev].label,
+                table[8 * (size_t)edges[e].cur], edges[e].count, (edges[e].flags & SPH_EDGE_MAIN_PARENT) ? "true" : "false",
+                (edges[e].flags & SPH_EDGE_MAIN_CHILD) ? "true" : "false");
+    const bool ok = fclose(out) == 0;
+    if (ok) fprintf(stderr, "tracks %d %u %u %u %u %u %u\n", f, s.bodies, s.continued, s.born, s.ended, s.merges, s.splits);
+    return ok;
+}
+
 // SPH_FREE_NEIGHBOURS=<f>, f in (0, 1], the radius in units of h: beside each written frame every particle's
 // neighbours within that radius (sph_neighbour_lists) as <dir>/neighbours_%04d.bin: the 8 bytes `SPHNBR01`, uint32 n,
 // uint32 0, uint64 entries, the n + 1 uint64 offsets, the uint32 ids, all little-endian; and one line on stderr,
@@ -349,6 +385,16 @@ void startVisualization(Simulator *simulator) {
         else
             bodyTableLink = v * simulator->settings->h;
     }
+    float bodyTrackLink = 0.f; // 0: no body tracks
+    if (framesDir && getenv("SPH_FREE_BODY_TRACKS")) {
+        const char *e = getenv("SPH_FREE_BODY_TRACKS");
+        char *end = NULL;
+        const float v = strtof(e, &end);
+        if (end == e || *end || !std::isfinite(v) || !(v > 0.f) || v > 1.f)
+            fprintf(stderr, "sph: SPH_FREE_BODY_TRACKS=%s is not a link length in (0, 1] (units of h) -- writing no body tracks\n", e);
+        else
+            bodyTrackLink = v * simulator->settings->h;
+    }
     float neighbourRadius = 0.f; // 0: no neighbour files
     if (framesDir && getenv("SPH_FREE_NEIGHBOURS")) {
         const char *e = getenv("SPH_FREE_NEIGHBOURS");
@@ -376,6 +422,7 @@ void startVisualization(Simulator *simulator) {
         if (framesDir && particles && f % every == 0 && !write_particles(simulator, framesDir, f)) particles = false;
         if (framesDir && bodyLink > 0.f && f % every == 0 && !write_bodies(simulator, framesDir, f, bodyLink)) bodyLink = 0.f;
         if (framesDir && bodyTableLink > 0.f && f % every == 0 && !write_body_table(simulator, framesDir, f, bodyTableLink)) bodyTableLink = 0.f;
+        if (framesDir && bodyTrackLink > 0.f && f % every == 0 && !write_body_tracks(simulator, framesDir, f, bodyTrackLink)) bodyTrackLink = 0.f;
         if (framesDir && neighbourRadius > 0.f && f % every == 0 && !write_neighbours(simulator, framesDir, f, neighbourRadius))
             neighbourRadius = 0.f;
         if (framesDir && f % every == 0 && !write_frame(simulator, framesDir, f, field)) framesDir = NULL;

@@ -288,6 +288,33 @@ bool Simulator::measureBodies(float link, const SphBodyMomentsRaw **rows, int *n
     return true;
 }
 
+bool Simulator::trackBodies(float link, const uint32_t **table, const SphBodyTrack **tracks, int *numBodies, const SphBodyFate **previous,
+                            int *numPrevious, const SphBodyEdge **edges, int *numEdges, SphBodyTrackSummary *summary) {
+    if (multi) {
+        fprintf(stderr, "sph: trackBodies: a multi-GPU run (SPH_GPUS > 1) labels no bodies\n");
+        return false;
+    }
+    if (!impl) return false;
+    SphBodyTrackOptions o = {};
+    o.struct_size = (int32_t)sizeof o;
+    o.link = link;
+    const int rc = sph_track_bodies(impl, &o);
+    if (rc == SPH_ESTATE || rc == SPH_EINVAL || rc == SPH_ENOMEM) { // (SPH_SWEEP=linked, a link longer than h, ...): nothing computed, nothing broken
+        fprintf(stderr, "sph: trackBodies: %s\n", sph_last_error(impl));
+        return false;
+    }
+    check(impl, rc, "sph_track_bodies");
+    check(impl, sph_bodies_host(impl, NULL, NULL, table, NULL, NULL), "sph_bodies_host");
+    check(impl, sph_body_tracks_host(impl, tracks, numBodies, previous, numPrevious, edges, numEdges, summary), "sph_body_tracks_host");
+    return true;
+}
+
+bool Simulator::resetTracks() {
+    if (multi || !impl) return false;
+    check(impl, sph_track_reset(impl), "sph_track_reset");
+    return true;
+}
+
 bool Simulator::neighbourLists(float radius, const uint64_t **offsets, const uint32_t **neighbours, uint64_t *entries) {
     if (multi) {
         fprintf(stderr, "sph: neighbourLists: a multi-GPU run (SPH_GPUS > 1) lists no neighbours\n");

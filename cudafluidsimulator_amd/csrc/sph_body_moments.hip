@@ -27,24 +27,16 @@ int moment_reserve(sph_handle *h, size_t bodies) {
 
 } // namespace
 
-extern "C" {
+namespace sph_host {
 
-int sph_measure_bodies(sph_handle *h, const SphBodyMeasureOptions *opt) {
-    if (!h) return SPH_EINVAL;
-    SPH_ON_DEVICE(h);
-    int rc = analysis_begin(h, "the bodies' labelling", ": multi-GPU runs label no bodies");
-    if (rc) return rc;
-    SphBodyMeasureOptions o{};
-    if ((rc = copy_options(h, opt, o, "SphBodyMeasureOptions.struct_size is not set"))) return rc;
-    if (o.pad_ != 0) return fail(h, SPH_EINVAL, "SphBodyMeasureOptions.pad_ must be 0");
-    if ((rc = label_bodies(h, o.link, "sph_measure_bodies"))) return rc;
-    // the labelling stands from here on, whatever becomes of the moments
+int measure_labelled(sph_handle *h, uint32_t max_bodies, const char *who) {
+    int rc;
     const int n = h->bodyN;
     const size_t bodies = (size_t)h->bodyCount;
-    if (o.max_bodies && bodies > (size_t)o.max_bodies) {
+    if (max_bodies && bodies > (size_t)max_bodies) {
         h->moment.valid = false;
-        return fail(h, SPH_ENOMEM, "sph_measure_bodies: the state has " + std::to_string(bodies) + " bodies, more than max_bodies = " +
-                                       std::to_string(o.max_bodies) + "; no moments");
+        return fail(h, SPH_ENOMEM, std::string(who) + ": the state has " + std::to_string(bodies) + " bodies, more than max_bodies = " +
+                                       std::to_string(max_bodies) + "; no moments");
     }
     if ((rc = moment_reserve(h, bodies))) return rc;
     if ((rc = outbound_fence(h, h->moment.out))) return rc; // the previous call's copies still read the device buffers
@@ -66,6 +58,23 @@ int sph_measure_bodies(sph_handle *h, const SphBodyMeasureOptions *opt) {
     h->momentCount = (int)bodies;
     h->moment.valid = true;
     return SPH_OK;
+}
+
+} // namespace sph_host
+
+extern "C" {
+
+int sph_measure_bodies(sph_handle *h, const SphBodyMeasureOptions *opt) {
+    if (!h) return SPH_EINVAL;
+    SPH_ON_DEVICE(h);
+    int rc = analysis_begin(h, "the bodies' labelling", ": multi-GPU runs label no bodies");
+    if (rc) return rc;
+    SphBodyMeasureOptions o{};
+    if ((rc = copy_options(h, opt, o, "SphBodyMeasureOptions.struct_size is not set"))) return rc;
+    if (o.pad_ != 0) return fail(h, SPH_EINVAL, "SphBodyMeasureOptions.pad_ must be 0");
+    if ((rc = label_bodies(h, o.link, "sph_measure_bodies"))) return rc;
+    // the labelling stands from here on, whatever becomes of the moments
+    return measure_labelled(h, o.max_bodies, "sph_measure_bodies");
 }
 
 int sph_body_moments_host(sph_handle *h, const SphBodyMomentsRaw **rows, int *num_bodies, const uint32_t **size_hist) {

@@ -423,6 +423,54 @@ struct BodyMomentArgs {
 // clear + reduce + finish; plain = the one-thread-per-row, one-atomic-per-word check path
 void sph_launch_body_moments(const BodyMomentArgs &A, bool plain, hipStream_t s);
 
+// ---- body tracks: the overlap of two labellings (body_tracks.hip; defined in DESIGN.md section 10l) ----
+// What one call counts, on the device: cleared by the first launch of a call, the two words the host waits for
+// (partials, edges) and what leaves with the results.
+struct TrackCounters {
+    unsigned long long nextTrack; // after the call (k_track_close)
+    uint32_t partials;            // partial edges (the fold's appends; check path: n)
+    uint32_t edges;               // the heads' scan total
+    uint32_t continued, born, ended, merges, splits;
+    uint32_t pad;
+};
+struct TrackArgs {
+    StreamView S;                 // the rows, n > 0 (the fold reads the ids alone)
+    const uint32_t *rowLabel;     // [n] the labelling's label of every row ...
+    const uint32_t *rank;         // [n] ... its table row per label ...
+    const uint32_t *labels;       // [n] ... the labels in particle-id order ...
+    const uint32_t *table;        // [8 numBodies] ... and the table
+    int numBodies;                // > 0
+    int numPrev;                  // bodies of the reference; 0: there is none, and the three below are not read
+    const uint32_t *prow;         // [n] the reference: the table row of every particle id's body ...
+    const uint2 *prevBody;        // [numPrev] ... (label, count) of its bodies ...
+    const unsigned long long *prevTrack; // [numPrev] ... and their tracks
+    uint32_t *crow;               // [n] the same three of this labelling: the next reference once the call has succeeded
+    uint2 *curBody;               // [numBodies]
+    unsigned long long *curTrack; // [numBodies]
+    unsigned long long *nextTrack; // the handle's next_track, on the device
+    uint32_t *pPrev, *pCur, *pCount; // [n] the partial edges, in arrival order (check path: pCount holds the heads' positions)
+    uint32_t *head;               // [n] per sorted partial: 1 = first of its pair; then per body: 1 = born
+    uint32_t *edgeOf;             // [n] the exclusive scan of head; then of the born flags
+    uint32_t *blockSum;           // [sph_track_scan_blocks(n)] the scans' per-block sums, then offsets
+    SortWorkspace ws;             // the pass's own, capacity n
+    uint32_t *parents, *children; // [numBodies], [numPrev] edges into / out of a body
+    unsigned long long *bestParent, *bestChild; // count << 32 | ~row of the main parent / child
+    SphBodyEdge *edges;           // [edges] the results
+    SphBodyTrack *tracks;         // [numBodies]
+    SphBodyFate *fates;           // [numPrev]
+    TrackCounters *counters;
+};
+int sph_track_scan_blocks(int n);
+// clear + one thread per particle id (crow; on the check path also the partial edges) + (default path) the fold: the
+// partial edges and counters->partials
+void sph_launch_track_partials(const TrackArgs &A, bool plain, hipStream_t s);
+// the two stable sorts of m partials + heads + scan, which leaves counters->edges; returns which of ws.vals holds the order
+int sph_launch_track_sort(const TrackArgs &A, int m, hipStream_t s);
+// the edges' rows, counts and the per-body tallies from the m sorted partials (order: ws.vals[order])
+void sph_launch_track_edges(const TrackArgs &A, int m, int numEdges, int order, bool plain, hipStream_t s);
+// both paths: continues or born, tracks, fates, edge flags, the summary's counters, nextTrack
+void sph_launch_track_assign(const TrackArgs &A, int numEdges, hipStream_t s);
+
 // ---- neighbour lists: every particle's neighbours within a radius, as CSR (neighbours.hip) ----
 struct NeighbourArgs {
     StreamView S;            // the rows and their candidates, n > 0 (the velocities are not read)

@@ -47,7 +47,8 @@ using sph_owned::PinnedBuf;
 //   SPH_TRACER_PLAIN      0        call    non-zero: sph_tracers_advect takes the one-thread-per-tracer check path
 //   SPH_DERIVE_PLAIN      0        call    non-zero: sph_derive takes the one-thread-per-row check path
 //   SPH_BODIES_PLAIN      0        call    non-zero: sph_label_bodies takes the check path (min-label propagation in rounds),
-//                                          and sph_measure_bodies with it, for its labelling and for its moments (one atomic per word)
+//                                          and sph_measure_bodies with it, for its labelling and for its moments (one atomic per word),
+//                                          and sph_track_bodies, for all three (every particle id a partial edge)
 //   SPH_NEIGHBOURS_PLAIN  0        call    non-zero: sph_neighbour_lists takes the check path (one thread per row, one per list)
 //   SPH_NEIGHBOURS_TIME_PHASE 0    call    1 count, 2 scan, 3 emit, 4 sort: SphNeighbourStats.seconds sums that phase alone
 //                                          (scripts/studies/neighbours.py); 0: all four
@@ -352,6 +353,40 @@ struct sph_handle {
     int momentCount = 0;             // bodies of the last sph_measure_bodies
     sph_host::Pass moment;           // out: rows and bins on their way to the pinned buffers; seconds: the moment launches alone
 
+    // ---- sph_body_tracks.hip ----
+    // Body tracks (body_tracks.hip).  The reference, on the device: the table row of every particle id's body, (label,
+    // count) and the track of every body, each twice -- [trackRef] is the reference, the other side is written by the
+    // call and becomes the reference when the call has succeeded --, and next_track.  The working arrays over n (a
+    // labelling may have n bodies), the pass's own sort workspace, the results on the device and in pinned memory
+    // (grown on demand, each on its own), the counter block, its pinned copy the call waits for and the one that
+    // leaves with the results.
+    sph_host::DeviceBuf<uint32_t> trackRow[2];
+    sph_host::DeviceBuf<uint2> trackBody[2];
+    sph_host::DeviceBuf<unsigned long long> trackId[2];
+    sph_host::DeviceBuf<unsigned long long> trackNext;
+    int trackRef = 0;
+    bool trackHasRef = false;        // a successful call since create / reset
+    int trackRefBodies = 0;          // bodies of the reference
+    uint64_t trackSequence = 0;      // successful calls since create / reset
+    sph_host::DeviceBuf<uint32_t> trackPPrev, trackPCur, trackPCount, trackHead, trackEdgeOf, trackBlockSum, trackParents, trackChildren;
+    sph_host::DeviceBuf<unsigned long long> trackBestParent, trackBestChild;
+    sph_host::DeviceBuf<uint32_t> trackKeys[2], trackVals[2], trackBlockHist, trackDigitTotal;
+    SortWorkspace trackWs{};         // views of the six above
+    size_t trackCap = 0;             // particles the buffers above hold
+    sph_host::DeviceBuf<SphBodyTrack> trackTracks;
+    sph_host::PinnedBuf<SphBodyTrack> trackTracksHost;
+    sph_host::DeviceBuf<SphBodyFate> trackFates;
+    sph_host::PinnedBuf<SphBodyFate> trackFatesHost;
+    sph_host::DeviceBuf<SphBodyEdge> trackEdges;
+    sph_host::PinnedBuf<SphBodyEdge> trackEdgesHost;
+    size_t trackTracksCap = 0, trackFatesCap = 0, trackEdgesCap = 0; // rows either buffer of a result holds
+    sph_host::DeviceBuf<TrackCounters> trackCounters;
+    sph_host::PinnedBuf<TrackCounters> trackCountersHost, trackFinalHost;
+    sph_host::Event trackCounted;    // the counter block has landed
+    int trackBodies = 0, trackPrevious = 0, trackEdgeCount = 0; // of the last sph_track_bodies
+    sph_host::Pass track;            // out: the results on their way to the pinned buffers; seconds: the track launches alone
+    unsigned long long trackPartialsSum = 0, trackEdgesSum = 0; // sums over calls
+
     // ---- sph_neighbours.hip ----
     // Neighbour lists (neighbours.hip): the length of every list and the CSR offsets in id order, the scan's block sums,
     // the lists themselves, the two words the call waits for (the total, the longest list), and the pinned copies of
@@ -455,6 +490,10 @@ SampleArgs lattice_args(const sph_handle *h, int nx, int ny, int nz, const float
 // labelling of the state the handle holds now on either path, the table, the copies, the SphBodyStats accounting.
 // `who` names the entry point in the messages.  sph_measure_bodies (sph_body_moments.hip) labels through it too.
 int label_bodies(sph_handle *h, float link, const char *who);
+// sph_body_moments.hip: what follows the labelling in sph_measure_bodies -- the cap (0: none), the buffers, the moment
+// launches over the labelling the handle holds, the copies, the SphBodyMeasureStats accounting.  sph_track_bodies
+// (sph_body_tracks.hip) measures through it too.
+int measure_labelled(sph_handle *h, uint32_t max_bodies, const char *who);
 // sph_readback.hip
 void sdma_init(sph_handle *h);
 int sdma_wait(sph_handle *h, int slot);

@@ -485,6 +485,58 @@ class Simulator:
         self._check(self._L.sph_get_body_measure_stats(self._h, C.byref(st), 1 if reset else 0), "sph_get_body_measure_stats")
         return dict(calls=st.calls, seconds=st.seconds)
 
+    # -- body tracks: which body is which body of the last call, merges and splits (sph_track_bodies) --
+    def track_bodies(self, link=0.0, max_edges=0, moments=False):
+        """label_bodies()'s dict of the current state plus its join with the labelling of the last successful
+        track_bodies() on this simulator (the reference): "tracks", a structured array (_lib.body_track_dtype()) with
+        one entry per body in the table's order -- track, parents, main_parent (row of the previous table, 0xFFFFFFFF
+        without parents), main_overlap, flags (_lib.SPH_TRACK_*); "previous" (_lib.body_fate_dtype()), one entry per
+        body of the reference -- track, label, count, children, main_child, main_overlap, flags (_lib.SPH_FATE_*);
+        "edges" (_lib.body_edge_dtype()): prev, cur, count, flags (_lib.SPH_EDGE_*) in ascending (cur, prev) order; and
+        "summary", a dict with the keys of _lib.TRACK_SUMMARY.  A body continues the previous body it shares the most
+        particles with where that body's largest piece is this one, and keeps its track; every other body is born with
+        a new track.  A result of more than `max_edges` edges (0: no cap) is refused and leaves the reference alone.
+        moments=True: also "moments" and "size_hist" as measure_bodies() returns them, of the same labelling."""
+        opt = _lib.SphBodyTrackOptions(C.sizeof(_lib.SphBodyTrackOptions), link, int(max_edges),
+                                       _lib.SPH_TRACK_WITH_MOMENTS if moments else 0)
+        self._check(self._L.sph_track_bodies(self._h, C.byref(opt)), "sph_track_bodies")
+        lab, tab, n, k, big = C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint32)(), C.c_int(0), C.c_int(0), C.c_uint32(0)
+        self._check(self._L.sph_bodies_host(self._h, C.byref(lab), C.byref(n), C.byref(tab), C.byref(k), C.byref(big)), "sph_bodies_host")
+        tr, fa, ed = C.POINTER(_lib.SphBodyTrack)(), C.POINTER(_lib.SphBodyFate)(), C.POINTER(_lib.SphBodyEdge)()
+        nt, nf, ne, summ = C.c_int(0), C.c_int(0), C.c_int(0), _lib.SphBodyTrackSummary()
+        self._check(self._L.sph_body_tracks_host(self._h, C.byref(tr), C.byref(nt), C.byref(fa), C.byref(nf), C.byref(ed), C.byref(ne),
+                                                 C.byref(summ)), "sph_body_tracks_host")
+
+        def structs(p, count, struct, dtype):
+            words = _rows(C.cast(p, C.POINTER(C.c_uint32)), count, C.sizeof(struct) // 4, np.uint32)
+            return words.view(dtype).reshape(-1)
+
+        out = dict(labels=_rows(lab, n.value, None, np.uint32), table=_rows(tab, k.value, 8, np.uint32),
+                   num_bodies=k.value, largest=big.value,
+                   tracks=structs(tr, nt.value, _lib.SphBodyTrack, _lib.body_track_dtype()),
+                   previous=structs(fa, nf.value, _lib.SphBodyFate, _lib.body_fate_dtype()),
+                   edges=structs(ed, ne.value, _lib.SphBodyEdge, _lib.body_edge_dtype()),
+                   summary={name: int(getattr(summ, name)) for name in _lib.TRACK_SUMMARY})
+        if moments:
+            rows, m, hist = C.POINTER(_lib.SphBodyMomentsRaw)(), C.c_int(0), C.POINTER(C.c_uint32)()
+            self._check(self._L.sph_body_moments_host(self._h, C.byref(rows), C.byref(m), C.byref(hist)), "sph_body_moments_host")
+            words = _rows(C.cast(rows, C.POINTER(C.c_uint64)), m.value, C.sizeof(_lib.SphBodyMomentsRaw) // 8, np.uint64)
+            out.update(moments=words.view(_lib.body_moments_dtype()).reshape(-1),
+                       size_hist=_rows(hist, _lib.BODY_SIZE_BINS, None, np.uint32))
+        return out
+
+    def track_reset(self):
+        """Forgets the reference of track_bodies(): the next call finds no previous bodies and starts tracks at 0."""
+        self._check(self._L.sph_track_reset(self._h), "sph_track_reset")
+
+    def body_track_stats(self, reset=False):
+        """dict(calls, partials, edges, seconds): sums since create or the last reset; `partials` is the number of
+        partial edges the calls sorted (the one number that depends on the kernel path), `edges` the edges, `seconds`
+        the GPU time of the track launches alone (the labelling's is body_stats()["seconds"])."""
+        st = _lib.SphBodyTrackStats()
+        self._check(self._L.sph_get_body_track_stats(self._h, C.byref(st), 1 if reset else 0), "sph_get_body_track_stats")
+        return dict(calls=st.calls, partials=st.partials, edges=st.edges, seconds=st.seconds)
+
     # -- neighbour lists: every particle's neighbours within a radius, as CSR (sph_neighbour_lists) --
     def neighbour_lists(self, radius=0.0, walk_order=False, max_entries=0):
         """{"offsets": (n + 1,) uint64, "neighbours": (entries,) uint32}: arrays of their own.  The neighbours of

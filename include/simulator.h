@@ -68,6 +68,10 @@ struct sph_mgpu;
 struct SphDiagnostics;    // include/sph_c_api.h
 struct SphDiagnosticsRaw;
 struct SphBodyMomentsRaw;
+struct SphBodyTrack;
+struct SphBodyFate;
+struct SphBodyEdge;
+struct SphBodyTrackSummary;
 
 class Simulator {
   private:
@@ -138,6 +142,16 @@ class Simulator {
     // distribution, owned by the simulator, valid until the next measureBodies.  Any out-pointer may be NULL.  false
     // (with a message on stderr) with SPH_GPUS > 1 and where the library answers SPH_ESTATE, SPH_EINVAL or SPH_ENOMEM.
     bool measureBodies(float link, const SphBodyMomentsRaw **rows, int *numBodies, const uint32_t **sizeHist);
+    // The tracks of the bodies of the current state (sph_track_bodies in sph_c_api.h): labels them as labelBodies does
+    // and joins the labelling with that of the last successful trackBodies -- numBodies SphBodyTrack beside the
+    // numBodies rows of `table` (8 words each: label, count, bounding box), numPrevious SphBodyFate for the bodies of
+    // the last call, numEdges SphBodyEdge in ascending (cur, prev) order and the summary, owned by the simulator, valid
+    // until the next trackBodies.  Any out-pointer may be NULL.  resetTracks forgets the last call's labelling: the
+    // next trackBodies finds no previous bodies and numbers its tracks from 0.  false (with a message on stderr) with
+    // SPH_GPUS > 1 and where the library answers SPH_ESTATE, SPH_EINVAL or SPH_ENOMEM.
+    bool trackBodies(float link, const uint32_t **table, const SphBodyTrack **tracks, int *numBodies, const SphBodyFate **previous,
+                     int *numPrevious, const SphBodyEdge **edges, int *numEdges, SphBodyTrackSummary *summary);
+    bool resetTracks();
     // The neighbour lists of the current state (sph_neighbour_lists in sph_c_api.h) as CSR in particle-id order: the
     // neighbours of particle i -- the particles within `radius` of it (0: h; else 0 < radius <= h), in ascending id
     // order -- are neighbours[offsets[i]] .. neighbours[offsets[i + 1] - 1]; n + 1 offsets, *entries ids, owned by the

@@ -872,6 +872,90 @@ typedef struct SphNeighbourStats {
 /* Sums since create or since the last reset (a reset clears `longest` too).  Blocks. */
 int sph_get_neighbour_stats(sph_handle *h, SphNeighbourStats *out, int reset);
 
+/* ---- body tracks: which body of this labelling is which body of the last one, merges and splits ----
+ * Additive to version 3: test for SPH_HAS_BODY_TRACKS.  Defined in DESIGN.md section 10l ("Body tracks"); integers
+ * only.  cur is the labelling of the state the handle holds now, prev the labelling of the last successful
+ * sph_track_bodies on this handle (its reference); particle ids denote the same particles in both.  With prow[id] and
+ * crow[id] the table rows (ascending label) of particle id's body in prev and cur, an edge is a distinct pair
+ * (prow[id], crow[id]) and its count the number of ids with that pair; edges stand in ascending (cur, prev) order.  The
+ * main parent of a current body is the edge into it with the greatest count, the main child of a previous body the
+ * edge out of it with the greatest count, a tie going to the smallest row.  c continues p exactly when p is c's main
+ * parent and c is p's main child; it then takes p's track.  Every other current body is born, with track
+ * next_track + (born bodies in rows before it); after the call next_track += born.  A previous body nobody continues
+ * has ended.  The first call after create or sph_track_reset has no previous bodies and no edges: every body is born
+ * with parents = 0, main_parent = 0xFFFFFFFF, main_overlap = 0.  The words are the same for any schedule, kernel path
+ * or sweep backend. */
+#define SPH_HAS_BODY_TRACKS 1
+typedef struct SphBodyTrackOptions {
+    int32_t struct_size;        /* sizeof(SphBodyTrackOptions) */
+    float link;                 /* as SphBodyOptions.link; may differ from call to call */
+    uint32_t max_edges;         /* the call refuses a result with more edges; 0 = no cap */
+    uint32_t flags;             /* SPH_TRACK_* */
+} SphBodyTrackOptions;
+enum { SPH_TRACK_WITH_MOMENTS = 1 };
+typedef struct SphBodyEdge { /* 16 bytes */
+    uint32_t prev, cur;         /* rows of the previous and of the current table */
+    uint32_t count;             /* particle ids with that pair */
+    uint32_t flags;             /* SPH_EDGE_* */
+} SphBodyEdge;
+enum { SPH_EDGE_MAIN_PARENT = 1, SPH_EDGE_MAIN_CHILD = 2 };
+typedef struct SphBodyTrack { /* per current body, 24 bytes */
+    uint64_t track;
+    uint32_t parents;           /* edges into the body */
+    uint32_t main_parent;       /* row of the previous table, 0xFFFFFFFF without parents */
+    uint32_t main_overlap;      /* that edge's count */
+    uint32_t flags;             /* SPH_TRACK_CONTINUES or SPH_TRACK_BORN, SPH_TRACK_MERGED with parents >= 2 */
+} SphBodyTrack;
+typedef struct SphBodyFate { /* per previous body, 32 bytes */
+    uint64_t track;
+    uint32_t label, count;      /* the previous table's */
+    uint32_t children;          /* edges out of the body */
+    uint32_t main_child;        /* row of the current table */
+    uint32_t main_overlap;      /* that edge's count */
+    uint32_t flags;             /* SPH_FATE_CONTINUES or SPH_FATE_ENDED, SPH_FATE_SPLIT with children >= 2 */
+} SphBodyFate;
+enum { SPH_TRACK_CONTINUES = 1, SPH_TRACK_BORN = 2, SPH_TRACK_MERGED = 4,
+       SPH_FATE_CONTINUES = 1, SPH_FATE_ENDED = 2, SPH_FATE_SPLIT = 4 };
+typedef struct SphBodyTrackSummary {
+    int32_t struct_size, pad_;  /* sizeof(SphBodyTrackSummary), 0: both written by the call */
+    uint32_t previous_bodies, bodies, edges;
+    uint32_t continued, born;   /* continued + born == bodies */
+    uint32_t ended;             /* continued + ended == previous_bodies */
+    uint32_t merges, splits;    /* current bodies with >= 2 parents, previous bodies with >= 2 children */
+    uint64_t next_track;        /* after the call */
+    uint64_t sequence;          /* successful calls since create or sph_track_reset, this one included */
+} SphBodyTrackSummary;
+/* Labels the state the handle holds NOW exactly as sph_label_bodies does -- the same state rules, error codes, grid
+ * handling, both paths, the same SphBodyStats accounting; sph_bodies_host afterwards serves this labelling -- and then
+ * joins it with the reference.  opt == NULL: link = h, no cap, no flags.  SPH_EINVAL also for an unknown flag bit.
+ * Beyond the labelling's wait the call waits on the host at most twice, for the number of partial edges (which sizes
+ * the sort) and the number of edges; the rest is queued.  More edges than a non-zero max_edges: SPH_ENOMEM, the
+ * message names both numbers, the handle holds no track results, the labelling stands, and the reference and
+ * next_track stay what they were: the next call behaves as if the refused one had never happened.  Only a successful
+ * call makes cur the reference.  SPH_TRACK_WITH_MOMENTS: the call then queues the moments of this labelling as
+ * sph_measure_bodies with max_bodies = 0 would, and sph_body_moments_host serves them, row for row beside the tracks.
+ * No particles: SPH_OK, nothing.  A call that ends in SPH_EHIP forgets the reference as sph_track_reset does.
+ * SPH_BODIES_PLAIN=1 selects the check path here too (every particle id a partial edge, run lengths instead of
+ * atomics, one thread per body; identical words). */
+int sph_track_bodies(sph_handle *h, const SphBodyTrackOptions *opt);
+/* The results of the last sph_track_bodies, owned by the handle, valid until the next one: one SphBodyTrack per
+ * current body and one SphBodyFate per previous body, each in its table's order, and the edges.  Blocks until the
+ * copies have landed.  Any out-pointer may be NULL; pointers returned for empty results may be NULL.  SPH_ESTATE
+ * before the first sph_track_bodies and after one that was refused. */
+int sph_body_tracks_host(sph_handle *h, const SphBodyTrack **tracks, int *num_bodies, const SphBodyFate **previous, int *num_previous,
+                         const SphBodyEdge **edges, int *num_edges, SphBodyTrackSummary *summary);
+/* Forgets the reference and the track results; next_track and sequence start from 0 again. */
+int sph_track_reset(sph_handle *h);
+typedef struct SphBodyTrackStats {
+    int32_t struct_size, pad_;  /* sizeof(SphBodyTrackStats), 0: both written by the call */
+    int64_t calls;              /* calls that queued track launches (either path) */
+    uint64_t partials;          /* partial edges the calls sorted: the only number that depends on the path and the stream */
+    uint64_t edges;             /* sum of the edges over the calls; a refused call adds what it counted */
+    double seconds;             /* GPU time of the track launches alone (the labelling's: SphBodyStats.seconds) */
+} SphBodyTrackStats;
+/* Sums since create or since the last reset.  Blocks. */
+int sph_get_body_track_stats(sph_handle *h, SphBodyTrackStats *out, int reset);
+
 const char *sph_build_info(void);
 
 #ifdef __cplusplus
