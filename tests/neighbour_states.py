@@ -7,17 +7,23 @@ import grid_states as G
 F = np.float32
 
 
+def put_on_the_walls(pos, g, what, first=0):
+    """rows first .. of pos moved (in place) onto the wall planes: coordinates 0 and the largest float below the box"""
+    top = np.nextafter(G.box_of(g["h"], g["cells"]), F(0))
+    k = min(len(pos) // 4, 24)
+    assert first + k + 1 < len(pos)
+    for i in range(k):
+        pos[first + i, i % 3] = F(0) if (i // 3) % 2 == 0 else top
+    pos[first + k] = (F(0), F(0), F(0))
+    pos[first + k + 1] = (top, top, top)
+    G.assert_inside(pos, g["h"], g["cells"], what)
+    return pos
+
+
 def on_the_walls(name):
     """a grid_states state with rows moved onto the wall planes: coordinates 0 and the largest float below the box"""
     pos, vel, g = G.grid_state(name)
-    top = np.nextafter(G.box_of(g["h"], g["cells"]), F(0))
-    k = min(len(pos) // 4, 24)
-    for i in range(k):
-        pos[i, i % 3] = F(0) if (i // 3) % 2 == 0 else top
-    pos[k] = (F(0), F(0), F(0))
-    pos[k + 1] = (top, top, top)
-    G.assert_inside(pos, g["h"], g["cells"], name)
-    return pos, vel, g
+    return put_on_the_walls(pos, g, name), vel, g
 
 
 def far_pair():
