@@ -37,6 +37,7 @@ EXPORTED_SYMBOLS = [
     "sph_measure_bodies", "sph_body_moments_host", "sph_body_values", "sph_get_body_measure_stats",
     "sph_track_bodies", "sph_body_tracks_host", "sph_track_reset", "sph_get_body_track_stats",
     "sph_neighbour_lists", "sph_neighbours_host", "sph_get_neighbour_stats",
+    "sph_pair_edges", "sph_pair_statistics", "sph_pair_statistics_host", "sph_pair_values", "sph_get_pair_stats",
 ]
 SPH_API_VERSION = 3
 SPH_SHADE_FLAT, SPH_SHADE_COUNT = 0, 1
@@ -61,6 +62,9 @@ SPH_TRACK_CONTINUES, SPH_TRACK_BORN, SPH_TRACK_MERGED = 1, 2, 4
 SPH_FATE_CONTINUES, SPH_FATE_ENDED, SPH_FATE_SPLIT = 1, 2, 4
 SPH_HAS_NEIGHBOURS = 1
 SPH_NEIGHBOURS_WALK_ORDER = 1
+SPH_HAS_PAIR_STATS = 1
+PAIR_MAX_BINS = 128
+PAIR_SUMS = ("d2", "w2", "a", "l2")   # SPH_PAIR_SUM_*
 BODY_TABLE = ("label", "count", "min_x", "min_y", "min_z", "max_x", "max_y", "max_z")   # words of a table row
 DIAG_SUMS = ("x", "y", "z", "vx", "vy", "vz", "rho", "prs", "v2")   # SPH_DIAG_SUM_*
 BODY_SUMS = DIAG_SUMS + ("xx", "yy", "zz", "xy", "xz", "yz", "lx", "ly", "lz")   # ... then SPH_BODY_SUM_*
@@ -316,6 +320,64 @@ class SphNeighbourStats(C.Structure):
                 ("longest", C.c_uint64), ("runs_staged", C.c_uint64), ("runs_direct", C.c_uint64), ("seconds", C.c_double)]
 
 
+class SphPairOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("flags", C.c_int32), ("radius", C.c_float), ("bins", C.c_int32), ("pad_", C.c_int32)]
+
+
+class SphPairBinRaw(C.Structure):
+    _fields_ = [("pairs", C.c_uint64), ("sums", SphSum128 * 4), ("saturated", C.c_uint64)]
+
+
+class SphPairValues(C.Structure):
+    _fields_ = [("r_lo", C.c_double), ("r_hi", C.c_double), ("pairs", C.c_double), ("mean_r2", C.c_double), ("s2", C.c_double),
+                ("s2_par", C.c_double), ("approach", C.c_double), ("g", C.c_double), ("saturated", C.c_uint64)]
+
+
+class SphPairStats(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("pad_", C.c_int32), ("calls", C.c_int64), ("pairs", C.c_uint64),
+                ("runs_staged", C.c_uint64), ("runs_direct", C.c_uint64), ("seconds", C.c_double)]
+
+
+def pair_bin_dtype():
+    """the numpy dtype of an SphPairBinRaw row: pairs, sums as (4, 2) uint64 -- [k, 0] the low and [k, 1] the high word of
+    sum k (two's complement; PAIR_SUMS names the sums) --, saturated"""
+    import numpy as np
+    return np.dtype([("pairs", "<u8"), ("sums", "<u8", (4, 2)), ("saturated", "<u8")])
+
+
+def pair_values_dtype():
+    """the numpy dtype of an SphPairValues"""
+    import numpy as np
+    return np.dtype([(name, "<u8" if name == "saturated" else "<f8") for name, _ in SphPairValues._fields_])
+
+
+def pair_edges(radius, h, bins=0):
+    """sph_pair_edges: the (bins,) float32 squared outer edges of `bins` bins (0: 32) of equal width up to `radius`
+    (0: h).  Pure host code: no GPU, no handle."""
+    import numpy as np
+    out = np.zeros(PAIR_MAX_BINS, np.float32)
+    rc = load_library().sph_pair_edges(C.c_float(radius), C.c_float(h), int(bins), out.ctypes.data_as(C.POINTER(C.c_float)))
+    if rc:
+        raise SphError(f"sph_pair_edges failed ({rc})")
+    return out[:int(bins) if bins else 32].copy()
+
+
+def pair_values(rows, edges2, settings, n):
+    """sph_pair_values over a structured array of raw rows (pair_bin_dtype) and their squared edges -> a structured array
+    of pair_values_dtype, one entry per bin, for n particles in the box of `settings`.  Pure host code."""
+    import numpy as np
+    rows = np.ascontiguousarray(rows, dtype=pair_bin_dtype()).reshape(-1)
+    edges2 = np.ascontiguousarray(edges2, dtype=np.float32).reshape(-1)
+    if len(edges2) != len(rows):
+        raise SphError("pair_values: as many edges as rows")
+    out = np.zeros(len(rows), pair_values_dtype())
+    rc = load_library().sph_pair_values(rows.ctypes.data_as(C.POINTER(SphPairBinRaw)), edges2.ctypes.data_as(C.POINTER(C.c_float)),
+                                        len(rows), C.byref(settings), int(n), out.ctypes.data_as(C.POINTER(SphPairValues)))
+    if rc:
+        raise SphError(f"sph_pair_values failed ({rc})")
+    return out
+
+
 class SphKernelTimes(C.Structure):
     _fields_ = [("hash", C.c_double), ("sort", C.c_double), ("gather", C.c_double),
                 ("density", C.c_double), ("force", C.c_double), ("readback", C.c_double),
@@ -433,5 +495,10 @@ def load_library():
     L.sph_neighbours_host.argtypes = [hp, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(u32p), C.POINTER(C.c_int),
                                       C.POINTER(C.c_uint64)]
     L.sph_get_neighbour_stats.argtypes = [hp, C.POINTER(SphNeighbourStats), C.c_int]
+    L.sph_pair_edges.argtypes = [C.c_float, C.c_float, C.c_int, fp]
+    L.sph_pair_statistics.argtypes = [hp, C.POINTER(SphPairOptions)]
+    L.sph_pair_statistics_host.argtypes = [hp, C.POINTER(C.POINTER(SphPairBinRaw)), C.POINTER(fp), C.POINTER(C.c_int)]
+    L.sph_pair_values.argtypes = [C.POINTER(SphPairBinRaw), fp, C.c_int, C.POINTER(SphSettings), C.c_int64, C.POINTER(SphPairValues)]
+    L.sph_get_pair_stats.argtypes = [hp, C.POINTER(SphPairStats), C.c_int]
     _lib = L
     return L

@@ -295,6 +295,38 @@ static bool write_body_tracks(Simulator *simulator, const char *dir, int f, floa
     return ok;
 }
 
+// SPH_FREE_PAIR_STATS=<bins>, 1 .. 128: beside each written frame the pair statistics of the state within h
+// (sph_pair_statistics, sph_pair_values) as <dir>/pair_stats_%04d.jsonl: one JSON line per bin with `bin` and every field
+// of SphPairValues, doubles as %.17g; and one line on stderr, `pairs <frame> <pairs> <saturated>`.
+static bool write_pair_stats(Simulator *simulator, const char *dir, int f, int bins) {
+    const SphPairBinRaw *rows = NULL;
+    const float *edges2 = NULL;
+    int k = 0;
+    if (!simulator->pairStatistics(bins, 0.f, &rows, &edges2, &k)) return false;
+    std::vector<SphPairValues> v((size_t)k);
+    SphSettings s; // (Settings and SphSettings share their layout)
+    memcpy(&s, simulator->settings, sizeof s);
+    if (sph_pair_values(rows, edges2, k, &s, s.numParticles, v.data()) != SPH_OK) {
+        fprintf(stderr, "sph: sph_pair_values refused the table\n");
+        return false;
+    }
+    FILE *out = open_out(dir, "pair_stats_%04d.jsonl", f);
+    if (!out) return false;
+    unsigned long long pairs = 0, saturated = 0;
+    for (int b = 0; b < k; ++b) {
+        fprintf(out,
+                "{\"bin\": %d, \"r_lo\": %.17g, \"r_hi\": %.17g, \"pairs\": %.17g, \"mean_r2\": %.17g, \"s2\": %.17g, "
+                "\"s2_par\": %.17g, \"approach\": %.17g, \"g\": %.17g, \"saturated\": %llu}\n",
+                b, v[b].r_lo, v[b].r_hi, v[b].pairs, v[b].mean_r2, v[b].s2, v[b].s2_par, v[b].approach, v[b].g,
+                (unsigned long long)v[b].saturated);
+        pairs += rows[b].pairs;
+        saturated += rows[b].saturated;
+    }
+    const bool ok = fclose(out) == 0;
+    if (ok) fprintf(stderr, "pairs %d %llu %llu\n", f, pairs, saturated);
+    return ok;
+}
+
 // SPH_FREE_NEIGHBOURS=<f>, f in (0, 1], the radius in units of h: beside each written frame every particle's
 // neighbours within that radius (sph_neighbour_lists) as <dir>/neighbours_%04d.bin: the 8 bytes `SPHNBR01`, uint32 n,
 // uint32 0, uint64 entries, the n + 1 uint64 offsets, the uint32 ids, all little-endian; and one line on stderr,
@@ -405,6 +437,16 @@ void startVisualization(Simulator *simulator) {
         else
             neighbourRadius = v * simulator->settings->h;
     }
+    int pairBins = 0; // 0: no pair statistics
+    if (framesDir && getenv("SPH_FREE_PAIR_STATS")) {
+        const char *e = getenv("SPH_FREE_PAIR_STATS");
+        char *end = NULL;
+        const long v = strtol(e, &end, 10);
+        if (end == e || *end || v < 1 || v > SPH_PAIR_MAX_BINS)
+            fprintf(stderr, "sph: SPH_FREE_PAIR_STATS=%s is not a number of bins in 1 .. 128 -- writing no pair statistics\n", e);
+        else
+            pairBins = (int)v;
+    }
     FILE *stats = NULL;
     if (framesDir && getenv("SPH_FREE_STATS") && atoi(getenv("SPH_FREE_STATS")) != 0) {
         const std::string path = std::string(framesDir) + "/stats.jsonl";
@@ -425,6 +467,7 @@ void startVisualization(Simulator *simulator) {
         if (framesDir && bodyTrackLink > 0.f && f % every == 0 && !write_body_tracks(simulator, framesDir, f, bodyTrackLink)) bodyTrackLink = 0.f;
         if (framesDir && neighbourRadius > 0.f && f % every == 0 && !write_neighbours(simulator, framesDir, f, neighbourRadius))
             neighbourRadius = 0.f;
+        if (framesDir && pairBins > 0 && f % every == 0 && !write_pair_stats(simulator, framesDir, f, pairBins)) pairBins = 0;
         if (framesDir && f % every == 0 && !write_frame(simulator, framesDir, f, field)) framesDir = NULL;
         if (framesDir && slice >= 0 && f % every == 0 && !write_slice(simulator, framesDir, f, slice)) slice = -1;
         if (framesDir && surfaceIso > 0.f && f % every == 0 && !write_surface(simulator, framesDir, f, surfaceIso)) surfaceIso = 0.f;

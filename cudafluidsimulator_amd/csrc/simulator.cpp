@@ -335,6 +335,26 @@ bool Simulator::neighbourLists(float radius, const uint64_t **offsets, const uin
     return true;
 }
 
+bool Simulator::pairStatistics(int bins, float radius, const SphPairBinRaw **rows, const float **edges2, int *numBins) {
+    if (multi) {
+        fprintf(stderr, "sph: pairStatistics: a multi-GPU run (SPH_GPUS > 1) gathers no pair statistics\n");
+        return false;
+    }
+    if (!impl) return false;
+    SphPairOptions o = {};
+    o.struct_size = (int32_t)sizeof o;
+    o.radius = radius;
+    o.bins = bins;
+    const int rc = sph_pair_statistics(impl, &o);
+    if (rc == SPH_ESTATE || rc == SPH_EINVAL) { // (SPH_SWEEP=linked, a radius longer than h, ...): no table, nothing broken
+        fprintf(stderr, "sph: pairStatistics: %s\n", sph_last_error(impl));
+        return false;
+    }
+    check(impl, rc, "sph_pair_statistics");
+    check(impl, sph_pair_statistics_host(impl, rows, edges2, numBins), "sph_pair_statistics_host");
+    return true;
+}
+
 bool Simulator::getVelocity(float *vel_xyz) {
     if (multi || !impl || !vel_xyz) return false;
     check(impl, sph_download_state(impl, NULL, vel_xyz, NULL, NULL), "sph_download_state");

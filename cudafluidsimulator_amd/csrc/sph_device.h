@@ -492,6 +492,38 @@ void sph_launch_neighbour_scan(const NeighbourArgs &A, hipStream_t s);
 void sph_launch_neighbour_emit(const DevParams &P, const NeighbourArgs &A, bool plain, hipStream_t s);
 void sph_launch_neighbour_sort(const NeighbourArgs &A, bool plain, hipStream_t s);
 
+// ---- pair statistics: per bin of separation the pairs and four exact sums (pairs.hip) ----
+// A partial row holds kPairWords words per bin, word-major (word w of bin b at [w bins + b]): the count, the four sums'
+// low words, their high words, the saturation count, and the four sums' top words (what a high word sheds before it
+// could wrap); the sum is lo + hi 2^32 + top 2^64.
+constexpr int kPairCount = 0, kPairLo = 1, kPairHi = 5, kPairSat = 9, kPairTop = 10, kPairWords = 14;
+constexpr int kPairLdsWords = kPairTop; // what the default path keeps in LDS: everything but the top words
+constexpr int kPairMaxN = 1 << 24;      // the default path's bound on n (pairs.hip says why)
+struct PairEdges {
+    float e[SPH_PAIR_MAX_BINS];
+};
+struct PairArgs {
+    StreamView S;            // the rows and their candidates, n > 0
+    float r2;                // radius squared, rounded once: the last edge
+    float perRadius;         // bins / radius: where the default path starts its search of the table
+    int bins;
+    const float *edges2;     // [bins] squared outer edges, non-decreasing (left by sph_launch_pair_table)
+    unsigned long long *partials; // [rows][kPairWords bins] one row per workgroup of the default path; the check path's one row
+    int rows;
+    unsigned int *tile;      // the default path's tile counter
+    long long shed;          // the default path: a hi word at or beyond +-shed sheds into its top word; 2^33 .. 2^62
+    SphPairBinRaw *out;      // [bins] the joined table
+    unsigned long long *counters; // [3] runs_staged, runs_direct (default path), the tables' pairs (the join)
+};
+constexpr int kPairCounters = 3;
+// workgroups the default path launches on a device of `cus` compute units for n rows (= partial rows; the check path: 1);
+// workgroups > 0: that many instead (SPH_PAIRS_WORKGROUPS), never more than tiles
+int sph_pair_rows(int n, int cus, bool plain, int workgroups);
+// the edges into device memory and an all-zero table (what a call without particles returns)
+void sph_launch_pair_table(const PairEdges &E, const PairArgs &A, hipStream_t s);
+// clear + walk + join; plain = the check path
+void sph_launch_pair_statistics(const DevParams &P, const PairArgs &A, bool plain, hipStream_t s);
+
 // ---- the surface mesh (surface.hip; defined in DESIGN.md section 10d) ----
 struct SurfaceArgs {
     int nx, ny, nz;          // lattice points per axis, each >= 2; point (ix, iy, iz) has L = (iz ny + iy) nx + ix

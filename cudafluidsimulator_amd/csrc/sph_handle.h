@@ -52,6 +52,12 @@ using sph_owned::PinnedBuf;
 //   SPH_NEIGHBOURS_PLAIN  0        call    non-zero: sph_neighbour_lists takes the check path (one thread per row, one per list)
 //   SPH_NEIGHBOURS_TIME_PHASE 0    call    1 count, 2 scan, 3 emit, 4 sort: SphNeighbourStats.seconds sums that phase alone
 //                                          (scripts/studies/neighbours.py); 0: all four
+//   SPH_PAIRS_PLAIN       0        call    non-zero: sph_pair_statistics takes the check path (one thread per row, the bin by a
+//                                          linear scan, every word a global atomic)
+//   SPH_PAIRS_WORKGROUPS  0        call    1 .. 65536: the default path of sph_pair_statistics launches that many workgroups
+//                                          (at most one per tile) instead of 16 per compute unit; same words
+//   SPH_PAIRS_SHED_BITS   62       call    33 .. 62: a high word of that path's table sheds into its top word at 2^bits
+//                                          instead of 2^62 (pairs.hip); same words
 //   SPH_MGPU_THREADS      0        (libsph_mgpu.so, its own object: sph_mgpu_create in mgpu_state.cpp) non-zero: one
 //                                          host thread per local slab
 // (The SPH_* variables the command-line front end reads -- SPH_SWEEP, SPH_GPUS, SPH_TRANSPORT, SPH_RECUT_EVERY,
@@ -406,6 +412,22 @@ struct sph_handle {
     uint64_t nbrNoOffsets = 0;       // the offsets of a result without particles: {0}
     sph_host::CounterBlock nbrCounters{kNeighbourCounters}; // runs_staged, runs_direct
     sph_host::Pass nbr;              // out: offsets and lists on their way to the pinned buffers; seconds: count + scan + emit + sort
+
+    // ---- sph_pairs.hip ----
+    // Pair statistics (pairs.hip): the table of squared edges and the joined rows on the device and in pinned memory
+    // (SPH_PAIR_MAX_BINS of each, allocated by the first call), the partial rows (grown on demand) and the default
+    // path's tile counter; the three counters.
+    sph_host::DeviceBuf<float> pairEdges;
+    sph_host::PinnedBuf<float> pairEdgesHost;
+    sph_host::DeviceBuf<SphPairBinRaw> pairRows;
+    sph_host::PinnedBuf<SphPairBinRaw> pairRowsHost;
+    sph_host::DeviceBuf<unsigned long long> pairPartials;
+    sph_host::DeviceBuf<unsigned int> pairTile;
+    size_t pairPartialCap = 0;       // words pairPartials holds
+    int pairBins = 0;                // bins of the last sph_pair_statistics
+    int pairCUs = 0;                 // compute units of the device (0: not asked yet)
+    sph_host::CounterBlock pairCounters{kPairCounters}; // runs_staged, runs_direct, pairs
+    sph_host::Pass pair;             // out: rows and edges on their way to the pinned buffers; seconds: clear + walk + join
 };
 
 #define HIPCHK(h, call)                                                               \

@@ -1,4 +1,4 @@
-// What the analysis passes' kernels share (sample.hip, tracers.hip, derived.hip, bodies.hip, neighbours.hip): the walks of a
+// What the analysis passes' kernels share (sample.hip, tracers.hip, derived.hip, bodies.hip, neighbours.hip, pairs.hip): the walks of a
 // StreamView (sph_device.h) around a point or a row.  sweep_common.h stays the step's; from it come only sweep_cell and
 // load_runs.  Every function is __forceinline__ and none holds a barrier -- those stay in the kernels, in plain sight --
 // but one: walk_runs_staged, the staged walk of a row's nine runs, whose two barriers and the wave-uniform conditions
@@ -42,11 +42,14 @@ __device__ __forceinline__ Poly6 poly6_mass(const DevParams &P, float d2) {
     return K;
 }
 
-// the link test of the bodies and the neighbour lists (DESIGN.md sections 10g, 10j): c is the candidate, pi the row
-__device__ __forceinline__ bool linked(const float4 pi, const float4 c, float r2) {
+// the link test of the bodies, the neighbour lists and the pair statistics (DESIGN.md sections 10g, 10j, 10m): c is the
+// candidate, pi the row; link_d2 is the squared distance the test compares, for the pass that also bins it
+__device__ __forceinline__ float link_d2(const float4 pi, const float4 c) {
     const float ex = c.x - pi.x, ey = c.y - pi.y, ez = c.z - pi.z;
-    const float d2 = (ex * ex + ey * ey) + ez * ez;
-    return d2 <= r2; // (false for a NaN)
+    return (ex * ex + ey * ey) + ez * ez;
+}
+__device__ __forceinline__ bool linked(const float4 pi, const float4 c, float r2) {
+    return link_d2(pi, c) <= r2; // (false for a NaN)
 }
 
 // the nine runs of the row at pi (load_runs around sweep_cell of its position), clipped to the stream

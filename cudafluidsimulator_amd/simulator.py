@@ -560,6 +560,45 @@ class Simulator:
         return dict(calls=st.calls, entries=st.entries, longest=st.longest, runs_staged=st.runs_staged,
                     runs_direct=st.runs_direct, seconds=st.seconds)
 
+    # -- pair statistics: g(r) and the velocity structure functions, per bin of separation (sph_pair_statistics) --
+    def pair_statistics(self, bins=0, radius=0.0):
+        """{"pairs": (B,) uint64, "sums": a (B, 4) object array of Python ints, "words": (B, 4, 2) uint64 -- the low and
+        the high word of every sum --, "saturated": (B,) uint64, "edges2": (B,) float32, "rows": the raw rows
+        (_lib.pair_bin_dtype())}: arrays of their own.  The unordered pairs of particles within `radius` (0: h; else
+        0 < radius <= h) of each other in `bins` bins (0: 32; at most 128) of equal width in r; bin k holds the pairs
+        with edges2[k - 1] < d2 <= edges2[k].  sums[k] are the exact Q32.32 sums (value = int / 2**32) named by
+        _lib.PAIR_SUMS: d2, |dv|^2, e.dv and (e.dv)^2 / d2.  pair_values() turns them into floats."""
+        opt = _lib.SphPairOptions(C.sizeof(_lib.SphPairOptions), 0, radius, int(bins), 0)
+        self._check(self._L.sph_pair_statistics(self._h, C.byref(opt)), "sph_pair_statistics")
+        rows, edges, b = C.POINTER(_lib.SphPairBinRaw)(), C.POINTER(C.c_float)(), C.c_int(0)
+        self._check(self._L.sph_pair_statistics_host(self._h, C.byref(rows), C.byref(edges), C.byref(b)), "sph_pair_statistics_host")
+        words = _rows(C.cast(rows, C.POINTER(C.c_uint64)), b.value, C.sizeof(_lib.SphPairBinRaw) // 8, np.uint64)
+        raw = words.view(_lib.pair_bin_dtype()).reshape(-1)
+        sums = np.empty((b.value, 4), object)
+        for k in range(b.value):
+            for s in range(4):
+                lo, hi = int(raw["sums"][k, s, 0]), int(raw["sums"][k, s, 1])
+                sums[k, s] = ((hi - (1 << 64) if hi >> 63 else hi) << 64) | lo
+        return dict(pairs=raw["pairs"].copy(), sums=sums, words=raw["sums"].copy(), saturated=raw["saturated"].copy(),
+                    edges2=_rows(edges, b.value, None, np.float32), rows=raw)
+
+    def pair_values(self, stats=None, bins=0, radius=0.0):
+        """The floats behind pair_statistics() -- of `stats`, a dict it returned, or of a call made here with `bins` and
+        `radius` --, a structured array (_lib.pair_values_dtype()) with one entry per bin: r_lo, r_hi, pairs, mean_r2,
+        s2 (<|dv|^2>), s2_par (<u_par^2>), approach (<r u_par>: negative where the pairs are closing), g (the radial
+        distribution function against an ideal gas of n particles in the box; the walls are not corrected for) and
+        saturated.  Pure host code."""
+        stats = self.pair_statistics(bins, radius) if stats is None else stats
+        return _lib.pair_values(stats["rows"], stats["edges2"], self.settings, self.settings.numParticles)
+
+    def pair_stats(self, reset=False):
+        """dict(calls, pairs, runs_staged, runs_direct, seconds): sums since create or the last reset; `pairs` sums the
+        tables' pairs over the calls, the two run counters are derive_stats()'s, `seconds` the GPU time of clear + walk
+        + join."""
+        st = _lib.SphPairStats()
+        self._check(self._L.sph_get_pair_stats(self._h, C.byref(st), 1 if reset else 0), "sph_get_pair_stats")
+        return dict(calls=st.calls, pairs=st.pairs, runs_staged=st.runs_staged, runs_direct=st.runs_direct, seconds=st.seconds)
+
     def phase(self, name):
         self._check(getattr(self._L, "sph_phase_" + name)(self._h), "sph_phase_" + name)
 

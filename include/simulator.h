@@ -72,6 +72,7 @@ struct SphBodyTrack;
 struct SphBodyFate;
 struct SphBodyEdge;
 struct SphBodyTrackSummary;
+struct SphPairBinRaw;
 
 class Simulator {
   private:
@@ -158,6 +159,12 @@ class Simulator {
     // simulator, valid until the next neighbourLists.  Any out-pointer may be NULL.  false (with a message on stderr)
     // with SPH_GPUS > 1 and where the library answers an error (SPH_ENOMEM: more than 1 << 28 ids).
     bool neighbourLists(float radius, const uint64_t **offsets, const uint32_t **neighbours, uint64_t *entries);
+    // The pair statistics of the current state (sph_pair_statistics in sph_c_api.h): per bin of separation -- `bins`
+    // bins (0: 32; at most 128) of equal width up to `radius` (0: h; else 0 < radius <= h) -- the number of pairs and
+    // the exact sums behind g(r) and the velocity structure functions; *numBins rows and squared edges, owned by the
+    // simulator, valid until the next pairStatistics; sph_pair_values turns them into floats.  Any out-pointer may be
+    // NULL.  false (with a message on stderr) with SPH_GPUS > 1 and where the library answers SPH_ESTATE or SPH_EINVAL.
+    bool pairStatistics(int bins, float radius, const SphPairBinRaw **rows, const float **edges2, int *numBins);
     // The velocities of the current state (sph_download_state), n x 3 floats in particle-id order, into the caller's
     // buffer.  false with SPH_GPUS > 1 and before setup().
     bool getVelocity(float *vel_xyz);

@@ -956,6 +956,80 @@ typedef struct SphBodyTrackStats {
 /* Sums since create or since the last reset.  Blocks. */
 int sph_get_body_track_stats(sph_handle *h, SphBodyTrackStats *out, int reset);
 
+/* ---- pair statistics: the radial distribution and the velocity structure of the fluid, per bin of separation ----
+ * Additive to version 3: test for SPH_HAS_PAIR_STATS.  Defined to the bit in DESIGN.md section 10m ("Pair
+ * statistics").  The pairs are the unordered pairs {i, j} of distinct particle ids that the neighbour lists' test takes
+ * at `radius` (e = p_j - p_i in fp32, d2 = (ex ex + ey ey) + ez ez, taken when d2 <= r2 = radius radius; a NaN d2 is
+ * not), each counted once.  The bin of a pair is the number of k < bins - 1 with edges2[k] < d2, edges2 the table of
+ * sph_pair_edges: bins of equal width in r, compared as squares; d2 == edges2[k] lies in bin k.  Per bin: the number of
+ * pairs and four sums of the diagnostics' Q32.32 terms q(t) (NaN and saturation rules included, `saturated` counts
+ * them), integers only, reported as SphSum128.  With w = v_j - v_i per axis in fp32 and everything after it in fp64, one
+ * rounding per operation: D2 sums (double)d2, W2 sums (wx wx + wy wy) + wz wz, A sums (ex wx + ey wy) + ez wz (half
+ * the rate of change of d2: negative means closing), L2 sums (A A) / (double)d2 (0 where d2 == 0): the squared
+ * velocity difference along the separation.  Every term is the same word for (i, j) and (j, i), and the words are the
+ * same for any row order, sweep backend, kernel path or launch shape.  The sum of `pairs` over the bins is
+ * SphBodyStats.links of sph_label_bodies at link = radius and half of sph_neighbour_lists' entries.  Out of scope:
+ * multi-GPU runs, radii above h, other binnings, pairs restricted to or across bodies, wall corrections, device
+ * pointers to the table. */
+#define SPH_HAS_PAIR_STATS 1
+#define SPH_PAIR_MAX_BINS 128
+enum { SPH_PAIR_SUM_D2 = 0, SPH_PAIR_SUM_W2 = 1, SPH_PAIR_SUM_A = 2, SPH_PAIR_SUM_L2 = 3, SPH_PAIR_SUMS = 4 };
+typedef struct SphPairOptions {
+    int32_t struct_size;   /* = sizeof(SphPairOptions) */
+    int32_t flags;         /* none defined: 0 */
+    float radius;          /* 0 = h, else finite with 0 < radius <= h */
+    int32_t bins;          /* 1 .. SPH_PAIR_MAX_BINS; 0 = 32 */
+    int32_t pad_;          /* 0 */
+} SphPairOptions;
+typedef struct SphPairBinRaw { /* 80 bytes */
+    uint64_t pairs;
+    SphSum128 sums[SPH_PAIR_SUMS];
+    uint64_t saturated;    /* terms of the bin that took a NaN or saturating branch */
+} SphPairBinRaw;
+typedef struct SphPairValues { /* per bin; DESIGN.md section 10m gives every expression, Python floats reproduce them */
+    double r_lo, r_hi;     /* the bin's edges: fp64 square roots of edges2[k - 1] (0 for bin 0) and edges2[k] */
+    double pairs;
+    double mean_r2;        /* value(D2) / pairs; like the next three 0 for an empty bin */
+    double s2;             /* value(W2) / pairs: <|dv|^2> */
+    double s2_par;         /* value(L2) / pairs: <u_par^2> */
+    double approach;       /* value(A) / pairs: <r u_par>, negative where the bin's pairs are closing */
+    double g;              /* pairs over what n ideal-gas particles in the box would put into the shell: walls not corrected for */
+    uint64_t saturated;    /* the bin's, over its four sums */
+} SphPairValues;
+/* Pure host code: the squared outer edges of `bins` bins (0 = 32: then 32 floats are written) of equal width up to
+ * `radius` (0 = h): edges2[k] = (float)(t t), t = ((double)radius (double)(k + 1)) / (double)bins, every fp64 operation
+ * rounded on its own; the last edge is r2 = radius radius in fp32 itself.  Non-decreasing; a tiny radius with many
+ * bins may repeat an edge.  SPH_EINVAL: bins outside [0, 128], an h that is not finite and positive, a radius that is
+ * not finite, negative or above h, a NULL table. */
+int sph_pair_edges(float radius_or_0, float h, int bins, float *edges2);
+/* Queues the walk over the pairs of the state the handle holds NOW, the join of its table and the copy of the table
+ * and of the edges it used; does not block and waits for nothing on the host.  opt == NULL: every default.  State
+ * rules, grid handling and error codes are sph_neighbour_lists's: the grid is found (phase 1) or built ahead (phase 0),
+ * the next step consumes it and no result of any step changes; SPH_ESTATE before any state, inside an open phase-split
+ * step, for SPH_FLAG_EXTERNAL_STATE handles (pairs cross slab boundaries), with SPH_SWEEP_LINKED and with
+ * SPH_KEY_MORTON; SPH_EINVAL for an unset struct_size, any flag, a non-zero pad_, bins outside [0, 128], a radius that
+ * is not finite, negative or greater than h, and, on the default path, more than 1 << 24 particles (the bound up to
+ * which no accumulator can wrap).  No particles: SPH_OK, an all-zero table.
+ * SPH_PAIRS_PLAIN=1 in the environment selects the check path (one thread per row, every candidate loaded from global
+ * memory, the bin by a linear scan, every word a global atomic; identical words, exact for any n). */
+int sph_pair_statistics(sph_handle *h, const SphPairOptions *opt);
+/* The result of the last sph_pair_statistics, owned by the handle, valid until the next one: *bins rows and the *bins
+ * squared edges the call used.  Blocks until the copies have landed.  Any out-pointer may be NULL.  SPH_ESTATE before
+ * the first sph_pair_statistics. */
+int sph_pair_statistics_host(sph_handle *h, const SphPairBinRaw **rows, const float **edges2, int *bins);
+/* Pure host code, no GPU and no handle: out[k] = the derived values of bin k, k < bins, for n particles in the box of
+ * `settings`.  SPH_EINVAL: bins outside [1, 128], n < 0, a NULL pointer, a table that holds a NaN or decreases. */
+int sph_pair_values(const SphPairBinRaw *rows, const float *edges2, int bins, const SphSettings *settings, int64_t n, SphPairValues *out);
+typedef struct SphPairStats {
+    int32_t struct_size, pad_;  /* sizeof(SphPairStats), 0: both written by the call */
+    int64_t calls;              /* calls that ran a kernel (either path) */
+    uint64_t pairs;             /* sum of the tables' pairs over those calls */
+    uint64_t runs_staged, runs_direct; /* as SphDeriveStats; check path: 0 */
+    double seconds;             /* GPU time of clear + walk + join (HIP events on the compute stream) */
+} SphPairStats;
+/* Sums since create or since the last reset.  Blocks. */
+int sph_get_pair_stats(sph_handle *h, SphPairStats *out, int reset);
+
 const char *sph_build_info(void);
 
 #ifdef __cplusplus
