@@ -1,4 +1,4 @@
-"""Random call sequences over the thirteen analysis passes: the plan of a seed, the model that says what every call
+"""Random call sequences over the fourteen analysis passes: the plan of a seed, the model that says what every call
 must return, and the driver that walks a plan.  tests/test_pass_sequences_cpu.py runs the plans with the oracle alone
 (what they cover, what they reach, what the restatements cost); tests/test_gpu_pass_sequences.py runs them on a
 Simulator.  Imports nothing from the product.
@@ -24,6 +24,7 @@ import field_sample_restatement as FS
 import grid_states as G
 import liquid_frame_restatement as LF
 import neighbour_restatement as NR
+import pair_restatement as PR
 import render_restatement as R
 import row_walk_cases as RW
 import surface_restatement as SR
@@ -31,20 +32,23 @@ import tracer_restatement as TR
 
 F = np.float32
 SEEDS = list(range(24))
+# what a seed's draws are seeded with, less the seed: the first of 7000, 7001, ... with which the seed list covers what
+# tests/test_pass_sequences_cpu.py asserts, every pass call finds the floors, and every pass makes 20 working calls
+PLAN_SEED = 7160
 GRIDS = ("D7", "D10h025", "D41", "D102")
 SWEEPS = ("list", "lds", "direct")
 # tests/test_gpu_api_fuzz.py's KNOBS (tests/test_gpu_pass_sequences.py asserts that they are)
 KNOBS = {"SPH_PIPELINE": ("0", "1"), "SPH_READBACK_SDMA": ("0", "1"),
          "SPH_ZERO_PAIR_FILTER": ("0", "1"), "SPH_SLIM_DIV": ("0", "1"), "SPH_XCD_ROTATE": ("0", "1", "5")}
 FRAMES = ("flat", "field", "column", "liquid")
-PASSES = FRAMES + ("sample", "surface", "diagnose", "tracers", "derive", "lists", "label", "measure", "track")
+PASSES = FRAMES + ("sample", "surface", "diagnose", "tracers", "derive", "lists", "label", "measure", "track", "pairs")
 PLAIN = {"flat": "SPH_RENDER_PLAIN", "field": "SPH_RENDER_PLAIN", "column": "SPH_RENDER_PLAIN", "liquid": "SPH_RENDER_PLAIN",
          "sample": "SPH_SAMPLE_PLAIN", "surface": "SPH_SURFACE_PLAIN", "diagnose": "SPH_DIAG_PLAIN", "tracers": "SPH_TRACER_PLAIN",
          "derive": "SPH_DERIVE_PLAIN", "lists": "SPH_NEIGHBOURS_PLAIN", "label": "SPH_BODIES_PLAIN", "measure": "SPH_BODIES_PLAIN",
-         "track": "SPH_BODIES_PLAIN"}
+         "track": "SPH_BODIES_PLAIN", "pairs": "SPH_PAIRS_PLAIN"}
 # the passes under the state rules of analysis_begin: SPH_ESTATE in phases 2 and 3 (the frames and the diagnostics
 # read pos4[cur] / vel4[cur] in any phase; what these hold inside a step is not defined, and no plan calls them there)
-WALKERS = ("sample", "surface", "tracers", "derive", "lists", "label", "measure", "track")
+WALKERS = ("sample", "surface", "tracers", "derive", "lists", "label", "measure", "track", "pairs")
 AFTER = ("step", "timed", "click", "upload", "snapshot", "open_grid")   # what every pass must directly follow
 STEPPING = ("step", "timed", "click", "snapshot", "open_grid", "phases")
 SIZES = ((800, 600), (160, 120), (97, 61))
@@ -52,9 +56,14 @@ LATTICES = ((8, 8, 8), (5, 9, 17), (20, 20, 20))       # (nz, ny, nx)
 TRACER_COUNTS = (0, 1, 130, 2000)
 FIELD_RANGES = {"speed": (0.25, 3.0), "density": (100.0, 1500.0), "pressure": (0.0, 40.0)}
 DIAGNOSE = (dict(hist=None, value_range=None), dict(hist="speed", value_range=(0.0, 4.0)), dict(hist="density", value_range=None))
-REFUSALS = ("max_edges", "max_bodies", "max_entries", "phase2", "phase3")
+# the pair statistics' table sizes (0 means 32) and, per call, SPH_PAIRS_WORKGROUPS ("0": the default launch; 1 and 3
+# workgroups carry their tables across tiles, with other passes' launches between the calls)
+PAIR_BINS = (0, 1, 7, 128)
+PAIR_WORKGROUPS = ("0", "1", "3")
+# "pair_options": a pairs call with 129 bins or a radius just above h, SPH_EINVAL; it leaves the previous result readable
+REFUSALS = ("max_edges", "max_bodies", "max_entries", "phase2", "phase3", "pair_options")
 # the result a host reader serves again, by pass: sph_frame_host, sph_sample_host, ... ("bodies": sph_bodies_host)
-READERS = ("frame", "sample", "surface", "diagnose", "tracers", "derive", "lists", "bodies", "moments", "tracks")
+READERS = ("frame", "sample", "surface", "diagnose", "tracers", "derive", "lists", "bodies", "moments", "tracks", "pairs")
 GAPS = 8                    # state operations of a seed that the schedule below pairs with the pass that follows them
 MAX_STEPS = 16
 # the floors of every pass call (conditions on the plans, asserted by tests/test_pass_sequences_cpu.py)
@@ -67,6 +76,11 @@ SCHEDULE = [SCHEDULE[i] for i in np.random.default_rng(0).permutation(len(SCHEDU
 
 def radii(h):
     return RW.radii(h)
+
+
+def above(h):
+    """the float32 next above h, as a Python float: the smallest radius the pair statistics refuse"""
+    return float(np.nextafter(F(h), F(np.inf)))
 
 
 def centre(g):
@@ -120,9 +134,11 @@ def draw_pass(rng, name, g, scheduled=False, tracers_set=True, cheap=False):
         op.update(link=radii(h)[rng.integers(3)])
     elif name == "track":
         op.update(link=radii(h)[rng.integers(3)], moments=bool(rng.integers(2)))
-    if cheap and name in ("lists", "label", "measure", "track"):
+    elif name == "pairs":
+        op.update(bins=int(PAIR_BINS[rng.integers(4)]), radius=radii(h)[rng.integers(3)], workgroups=PAIR_WORKGROUPS[rng.integers(3)])
+    if cheap and name in ("lists", "label", "measure", "track", "pairs"):
         # D102's cluster: a thousand rows within h of each other, a million entries at radius h
-        op["radius" if name == "lists" else "link"] = radii(h)[1 + rng.integers(2)]
+        op["radius" if name in ("lists", "pairs") else "link"] = radii(h)[1 + rng.integers(2)]
     return op
 
 
@@ -142,7 +158,8 @@ def readers_of(op):
 
 def follow(held, op):
     """held: reader -> has the state moved since the result it holds was made; updated for one operation of a plan, as
-    tests/test_gpu_pass_sequences.py's Device keeps `last`.  A refused call empties its own reader (and has labelled)."""
+    tests/test_gpu_pass_sequences.py's Device keeps `last`.  A call refused by a cap empties its own reader (and has
+    labelled); a pairs call refused for its options leaves the pairs' reader as it was."""
     kind = op["kind"]
 
     def called(q):
@@ -154,7 +171,9 @@ def follow(held, op):
     elif kind == "track_reset":
         held.pop("tracks", None)
     elif kind == "refuse":
-        if op["what"] == "max_entries":
+        if op["what"] == "pair_options":
+            pass
+        elif op["what"] == "max_entries":
             held.pop("lists", None)
         else:
             held["bodies"] = False
@@ -171,7 +190,7 @@ def follow(held, op):
 
 def plan(seed):
     """-> dict(seed, grid, sweep, env, ops): a pure function of the seed"""
-    rng = np.random.default_rng(7000 + seed)
+    rng = np.random.default_rng(PLAN_SEED + seed)
     grid = GRIDS[seed % 4]
     g = G.GRIDS[grid]
     sweep = SWEEPS[rng.integers(3)]
@@ -231,6 +250,11 @@ def plan(seed):
                 if probe["kind"] == "tracers":
                     probe["set"] = None               # (sph_tracers_set has no state rule: the advect alone is refused)
                 op["probe"] = (int(what[-1]), probe)
+                return op
+            if what == "pair_options":         # SPH_EINVAL: too many bins, or a radius one ulp above h
+                bad = dict(bins=129, radius=0.0) if rng.integers(2) else dict(bins=int(PAIR_BINS[rng.integers(4)]), radius=above(g["h"]))
+                op = dict(kind="refuse", what=what, plain=str(rng.integers(2)), **bad)
+                op["then"] = a_pass("pairs")
                 return op
             link = radii(g["h"])[2]
             op = dict(kind="refuse", what=what, link=link, moments=bool(rng.integers(2)), plain=str(rng.integers(2)))
@@ -314,6 +338,7 @@ class Model:
         self.tracers = np.zeros((0, 3), F)
         self.tracker = T.Tracker()
         self.fields = {}
+        self.prepared = {}
         self.cost = {}
 
     def close(self):
@@ -351,6 +376,28 @@ class Model:
         st = self.ref.download()
         _, ids, cells = NR.grid_of(st["pos"], self.h, self.D)
         return Inputs(st, ids, cells)
+
+    def assert_sorted(self, i, tag):
+        """the grid a walker left behind sph_download_grid is a stable sort of the downloaded state by cell: every id
+        once, the rows' cells in ascending order -- the CPU sort's sequence of cells; the product sorts the previous
+        step's order, not the id order, so the rows of one cell may stand in another order than the CPU's --, the CPU's
+        run for every occupied cell and no rows in any other"""
+        _, ids, cells = NR.grid_of(i.pos, self.h, self.D)
+        c = BR.row_cells(i.pos, self.h, self.D).astype(np.int64)
+        key = (c[:, 2] * self.D + c[:, 1]) * self.D + c[:, 0]
+        assert np.array_equal(np.sort(i.ids), np.arange(len(i.pos))), f"{tag}: sph_download_grid's ids are not a permutation of the ids"
+        assert np.array_equal(key[i.ids], key[ids]), f"{tag}: sph_download_grid's ids are not sorted by the cells of the state"
+        got = np.asarray(i.cells).reshape(-1, 2)
+        assert got.shape == cells.shape, f"{tag}: {got.shape} cell ranges"
+        full = cells[:, 1] > cells[:, 0]
+        assert np.array_equal(got[full], cells[full]) and (got[~full, 1] <= got[~full, 0]).all(), f"{tag}: sph_download_grid's cell ranges are not the state's"
+
+    def pairs(self, i, radius):
+        key = (i.key(), radius)
+        if key not in self.prepared:
+            self.prepared.clear()           # (the calls on one state follow each other)
+            self.prepared[key] = PR.prepared(i.pos, i.vel, self.h, radius)
+        return self.prepared[key]
 
     def walks(self, op):
         """does this pass call find or build the grid of the state (sph_download_grid then returns the one it walked)?
@@ -452,6 +499,8 @@ class Model:
             else:
                 r = NR.all_pairs(i.pos, h, op["radius"])
             return dict(offsets=r[0], neighbours=r[1])
+        if kind == "pairs":
+            return self.pairs(i, op["radius"]).table(PR.edges2(op["radius"], h, op["bins"]))
         b = self.bodies(i, op["link"], helpers)
         out = {k: b[k] for k in ("labels", "table", "num_bodies", "largest")}
         if kind == "measure" or (kind == "track" and op["moments"]):
@@ -464,8 +513,9 @@ class Model:
         return out
 
     def refused(self, op, i, helpers=None):
-        """what a call refused by a cap leaves: the labelling it made (max_bodies, max_edges), nothing else"""
-        if op["what"] == "max_entries":
+        """what a call refused by a cap leaves: the labelling it made (max_bodies, max_edges), nothing else; a pairs call
+        refused for its options (which i may be None for: it walks no grid) leaves nothing and takes nothing"""
+        if op["what"] in ("max_entries", "pair_options"):
             return None
         b = self.bodies(i, op["link"], helpers or {})
         if op["what"] == "max_edges":
@@ -509,7 +559,8 @@ def passes_of(p):
             after, first = kind, True
         else:
             if kind == "refuse":
-                first = False           # (the refused call walked the grid before it was refused)
+                if op["what"] != "pair_options":
+                    first = False       # (the call walked the grid before a cap refused it; bad options are refused before)
                 note(k, op["then"], None, False)
             after = None            # a refusal, a reread or a reset stands between
     return out
@@ -530,8 +581,11 @@ def drive(p, model, device=None, bare=None, on_pass=None):
             model.want(op, model.inputs(), iso=iso)
             return
         got = device.call(op, iso)
+        i = device.inputs(model.walks(op))
+        if op["kind"] == "pairs":
+            model.assert_sorted(i, tag)
         try:
-            want = model.want(op, device.inputs(model.walks(op)), device.helpers(), iso)
+            want = model.want(op, i, device.helpers(), iso)
         except AssertionError as e:     # (a restatement that cannot make sense of the grid and the state it was given)
             raise AssertionError(f"{tag}: the restatement over sph_download_grid + sph_download_state after the call: {e}") from e
         device.compare(op, got, want, tag)
@@ -553,7 +607,8 @@ def drive(p, model, device=None, bare=None, on_pass=None):
                 model.refused(op, model.inputs())
             else:
                 device.refuse(op, tag)
-                device.refused(op, model.refused(op, device.inputs(True), device.helpers()), tag)
+                i = None if op["what"] == "pair_options" else device.inputs(True)
+                device.refused(op, model.refused(op, i, device.helpers()), tag)
             a_pass(k, op["then"], f"{tag}: the next call, {describe(op['then'])}")
         elif kind in ("open_grid", "phases"):
             for d in (device, bare):

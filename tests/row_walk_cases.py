@@ -1,6 +1,6 @@
 """What tests/test_row_walks_cpu.py (restatements, without a GPU) and tests/test_gpu_row_walks.py (the kernels) share:
-the states the five passes that walk the nine runs around every ROW of the sorted stream -- derived fields, neighbour
-lists, bodies, per-body moments, body tracks -- are held to off the reference's 100^3 grid, the lengths they are asked
+the states the six passes that walk the nine runs around every ROW of the sorted stream -- derived fields, neighbour
+lists, bodies, per-body moments, body tracks, pair statistics -- are held to off the reference's 100^3 grid, the lengths they are asked
 for, and a plain restatement of what the staged row walk (walk_common.h, walk_runs_staged) counts.  The grids are
 walk_grid_cases.GRIDS.  Imports nothing from the product."""
 import functools

@@ -1,10 +1,11 @@
-"""Random sequences of steps, state changes and all thirteen analysis passes on one handle, held to a model
+"""Random sequences of steps, state changes and all fourteen analysis passes on one handle, held to a model
 (tests/pass_sequences.py): the state to the oracle after every state operation, every pass result to its restatement
 at the moment of the call -- fed by sph_download_state + sph_download_grid taken after the call, through the helpers of
 the passes' own test files --, every refusal to what it must leave alone, every host reader to the copy taken at the
 call, and the run's final state to that of a handle that made the same state operations and no pass call.  Off the
 100^3 grid: D7, D10h025, D41 and D102 of tests/grid_states.py, one sort plan each.  Every comparison is of words.
-tests/test_pass_sequences_cpu.py shows what the seed list covers.
+tests/test_pass_sequences_cpu.py shows what the seed list covers.  Measured on an MI355X: the 24 seeds and the knob
+check take 27.8 s, the costliest seed (23, D102) 3.2 s, every other under 2.8 s.
 
 The rules the readers are held to ("What a result outlives"):
   * a host reader serves the last successful call of its pass until the next call of that pass, across steps, clicks,
@@ -13,6 +14,9 @@ The rules the readers are held to ("What a result outlives
     last -- a call refused by max_bodies or max_edges included: it labelled before it was refused;
   * a refused call leaves no result of its own: sph_body_moments_host, sph_body_tracks_host, sph_neighbours_host are
     SPH_ESTATE after it, and so is sph_body_tracks_host after sph_track_reset;
+  * a call refused for its arguments is another matter: sph_pair_statistics with 129 bins or a radius above h is
+    SPH_EINVAL before it touches anything, and sph_pair_statistics_host goes on serving the previous result (SPH_ESTATE
+    where there was none);
   * the device-side readers (sph_download_frame_buffers and the like) are read at the call only."""
 import ctypes as C
 
@@ -24,6 +28,7 @@ from cudafluidsimulator_amd import _lib
 
 import body_tracks_restatement as T
 import diagnostics_restatement as D
+import pair_restatement as PR
 import grid_states as G
 import pass_sequences as PS
 import test_gpu_api_fuzz as FZ
@@ -166,6 +171,9 @@ class Device(Bare):
             return sim.derive()
         if kind == "lists":
             return sim.neighbour_lists(op["radius"], walk_order=op["walk_order"])
+        if kind == "pairs":
+            self.mp.setenv("SPH_PAIRS_WORKGROUPS", op["workgroups"])
+            return sim.pair_statistics(op["bins"], op["radius"])
         if kind == "label":
             return sim.label_bodies(op["link"])
         if kind == "measure":
@@ -178,6 +186,14 @@ class Device(Bare):
         if kind == "diagnose":
             D.assert_same_words(got["raw"], D.to_struct(want["raw"]), tag)
             last["diagnose"] = bytes(got["raw"])
+            return
+        if kind == "pairs":
+            # the table as Python ints, then the raw rows and edges word for word (as test_gpu_pairs.both_paths)
+            PR.assert_same_table(got, want, tag)
+            assert got["edges2"].dtype == F and got["pairs"].dtype == np.uint64, tag
+            assert PR.describe_difference(PR.from_rows(got["rows"], got["edges2"]), want) == [], tag
+            assert got["rows"].tobytes() == PR.to_rows(want).tobytes() and got["edges2"].tobytes() == want["edges2"].tobytes(), tag
+            last["pairs"] = dict(rows=got["rows"].copy(), edges2=got["edges2"].copy(), bins=len(got["rows"]))
             return
         if kind == "track":
             join = want.pop("join")
@@ -199,7 +215,13 @@ class Device(Bare):
 
     # -- the refusals --
     def refuse(self, op, tag):
-        sim, link = self.sim, op["link"]
+        sim = self.sim
+        if op["what"] == "pair_options":
+            self.mp.setenv("SPH_PAIRS_PLAIN", op["plain"])
+            with tagged(tag, -1):
+                sim.pair_statistics(op["bins"], op["radius"])
+            return
+        link = op["link"]
         self.mp.setenv("SPH_BODIES_PLAIN", op["plain"])
         self.mp.setenv("SPH_NEIGHBOURS_PLAIN", op["plain"])
         with tagged(tag, -3):
@@ -213,6 +235,14 @@ class Device(Bare):
     def refused(self, op, labelling, tag):
         """after a refusal: the labelling it made is the one sph_bodies_host serves, its own reader has nothing"""
         last = self.last
+        if op["what"] == "pair_options":
+            # SPH_EINVAL took nothing: the previous table is still served, word for word
+            if last["pairs"] is None:
+                with tagged(f"{tag}: pairs read after the refusal, with no result before it", -4):
+                    self.read("pairs")
+            else:
+                self.reread("pairs", f"{tag}: sph_pair_statistics_host after the refusal")
+            return
         if op["what"] == "max_entries":
             last["lists"] = None
             gone = ["lists"]
@@ -280,6 +310,11 @@ class Device(Bare):
             ck(L.sph_body_moments_host(h, C.byref(p), C.byref(m), C.byref(hist)), "sph_body_moments_host")
             w = rows(C.cast(p, C.POINTER(C.c_uint64)), m.value, C.sizeof(_lib.SphBodyMomentsRaw) // 8, np.uint64)
             return dict(moments=w.view(_lib.body_moments_dtype()).reshape(-1), size_hist=rows(hist, _lib.BODY_SIZE_BINS, None, np.uint32))
+        if reader == "pairs":
+            pr, ed, b = C.POINTER(_lib.SphPairBinRaw)(), C.POINTER(C.c_float)(), C.c_int(-1)
+            ck(L.sph_pair_statistics_host(h, C.byref(pr), C.byref(ed), C.byref(b)), "sph_pair_statistics_host")
+            w = rows(C.cast(pr, C.POINTER(C.c_uint64)), b.value, C.sizeof(_lib.SphPairBinRaw) // 8, np.uint64)
+            return dict(rows=w.view(_lib.pair_bin_dtype()).reshape(-1), edges2=rows(ed, b.value, None, np.float32), bins=b.value)
         assert reader == "tracks", reader
         tr, fa, ed = C.POINTER(_lib.SphBodyTrack)(), C.POINTER(_lib.SphBodyFate)(), C.POINTER(_lib.SphBodyEdge)()
         nt, nf, ne, summ = C.c_int(0), C.c_int(0), C.c_int(0), _lib.SphBodyTrackSummary()

@@ -6,18 +6,25 @@ milliseconds).
 Measured with the committed seed list (0 .. 23, six seeds per grid; test_what_the_seed_list_covers prints the tables
 under pytest -s).  Seconds on one CPU core, floors included, summed over a grid's seeds / its costliest seed / the
 restatements that cost most:
-    D7       10.7 /  2.6 (seed  4)   liquid 1.2, measure 0.8, track 0.7, label 0.6
-    D10h025  15.6 /  5.1 (seed  5)   measure 2.7, derive 1.3, lists 0.6, track 0.6
-    D41      33.0 /  7.0 (seed  6)   measure 5.4, track 3.6, derive 2.8, label 1.9
-    D102     42.4 /  8.3 (seed  7)   measure 5.0, label 3.5, track 3.1, derive 2.0
+    D7        7.9 /  1.5 (seed 16)   liquid 1.1, measure 0.6, derive 0.5, pairs 0.5, track 0.4
+    D10h025  12.3 /  2.5 (seed 13)   measure 1.7, track 0.8, derive 0.8, lists 0.8, label 0.6, pairs 0.6
+    D41      22.9 /  4.3 (seed 10)   measure 3.0, derive 2.4, track 1.6, label 0.9, pairs 0.7
+    D102     40.1 /  8.6 (seed 23)   measure 5.1, track 4.3, label 2.2, derive 1.1, pairs 1.1
 The restatements alone are a third of that: the floors' all-pairs lists and bodies are the rest, and the GPU test does
-not compute them.  D102 is thinned first: three of four of its list, label, measure and track calls take 0.5 h or
-0.3 h, not h (its cluster of a thousand rows within h of each other makes a million entries at radius h); the count of
-calls and the kinds of pass are the other grids'.
-Pass calls that do work, over the seed list: flat 28, field 26, column 29, liquid 26, sample 31, surface 27, diagnose
-27, tracers 24, derive 27, lists 32, label 28, measure 43, track 31 (an advect of no tracers is not counted).
-Re-reads of a reader that holds a result, at once / after a step or an upload since: frame 3 / 14, sample 1 / 4,
-surface 4 / 4, diagnose 0 / 3, tracers 0 / 4, derive 3 / 7, lists 0 / 7, bodies 2 / 6, moments 2 / 6, tracks 1 / 6.
+not compute them.  D102 is thinned first: three of four of its list, label, measure, track and pairs calls take 0.5 h
+or 0.3 h, not h (its cluster of a thousand rows within h of each other makes a million entries at radius h); the count
+of calls and the kinds of pass are the other grids'.
+Pass calls that do work, over the seed list (at least 20 each, asserted): flat 24, field 22, column 23, liquid 25,
+sample 24, surface 23, diagnose 23, tracers 20, derive 23, lists 28, label 25, measure 41, track 28, pairs 25 (an advect
+of no tracers is not counted).
+Re-reads of a reader that holds a result, at once / after a step or an upload since: frame 4 / 10, sample 2 / 2,
+surface 2 / 6, diagnose 2 / 9, tracers 0 / 5, derive 0 / 2, lists 1 / 5, bodies 0 / 7, moments 2 / 5, tracks 1 / 5,
+pairs 2 / 9.
+Pairs calls refused for their options (SPH_EINVAL): 129 bins with and without a table to leave alone (seeds 2, 17), a
+radius one ulp above h with and without one (seeds 8 and 11, seed 5); each of the four is asserted to occur.
+The draws are seeded with pass_sequences.PLAN_SEED + seed.  PLAN_SEED is the first of 7000, 7001, ... under which
+everything this file asserts holds: a fourteenth pass changed every seed's draws, and under 7000 three seeds' plans
+took the state below the floors.
 """
 import functools
 import time
@@ -33,7 +40,7 @@ class Recorder(PS.Model):
 
     def __init__(self, p):
         super().__init__(p)
-        self.sizes = {k: [] for k in ("pixels", "sample", "surface", "tracers", "bodies", "edges", "entries", "moments")}
+        self.sizes = {k: [] for k in ("pixels", "sample", "surface", "tracers", "bodies", "edges", "entries", "moments", "bins")}
         self.floors = []
         self.reached = None
 
@@ -59,6 +66,8 @@ class Recorder(PS.Model):
             s["tracers"].append(len(out["pos"]))
         elif kind == "lists":
             s["entries"].append(len(out["neighbours"]))
+        elif kind == "pairs":
+            s["bins"].append(len(out["pairs"]))
         else:
             if "num_bodies" in out:
                 s["bodies"].append(out["num_bodies"])
@@ -107,6 +116,7 @@ def ups_and_downs(values):
 def test_what_the_seed_list_covers():
     plans = [walked(seed) for seed in PS.SEEDS]
     after, order, inside, frames, sizes, refusals, combos = set(), set(), set(), set(), set(), set(), set()
+    options = set()
     fresh, stale = {}, {}       # re-reads of a reader that holds a result: before / after the state has moved on
     calls = {}
     for p, model in plans:
@@ -133,6 +143,8 @@ def test_what_the_seed_list_covers():
         for k, op in enumerate(p["ops"]):
             if op["kind"] == "refuse":
                 refusals.add(op["what"])
+                if op["what"] == "pair_options":    # (what is wrong with them, does the pairs' reader hold a result)
+                    options.add(("bins" if op["bins"] > 128 else "radius", "pairs" in held))
             if op["kind"] == "phases" and op["probe"]:
                 refusals.add(f"phase{op['probe'][0]}")
             if op["kind"] == "reread":
@@ -147,6 +159,7 @@ def test_what_the_seed_list_covers():
     assert frames >= {(a, b) for a in PS.FRAMES for b in PS.FRAMES if a != b}, "a frame kind never follows another"
     assert sizes == set(PS.SIZES), "a frame size never follows a different one"
     assert refusals == set(PS.REFUSALS)
+    assert options == {(w, r) for w in ("bins", "radius") for r in (True, False)}, "a refused pairs call: never this option with / without a result to leave alone"
     # every host reader is read again while it holds a result, and at least once after a step or an upload since
     assert set(fresh) | set(stale) == set(PS.READERS), f"never re-read: {sorted(set(PS.READERS) - set(fresh) - set(stale))}"
     assert set(stale) == set(PS.READERS), f"never re-read after the state moved on: {sorted(set(PS.READERS) - set(stale))}"
@@ -158,7 +171,8 @@ def test_what_the_seed_list_covers():
             up, down = up or u, down or d
         assert up and down, f"{what}: never {'down' if up else 'up'} within a sequence"
     # the coverage and cost tables (pytest -s shows them)
-    print("pass calls over the seed list:", {q: calls[q] for q in PS.PASSES})
+    print("\npass calls over the seed list:", {q: calls[q] for q in PS.PASSES})
+    assert min(calls[q] for q in PS.PASSES) >= 20, "a pass makes fewer than 20 working calls over the seed list"
     print("re-reads (at once / after the state moved on):", {r: (fresh.get(r, 0), stale.get(r, 0)) for r in PS.READERS})
     for grid in PS.GRIDS:
         mine = [(p["seed"], m.seconds) for p, m in plans if p["grid"] == grid]

@@ -1,9 +1,12 @@
 """The restatements of the passes that walk the nine runs around every row of the sorted stream -- derived fields,
-neighbour lists, bodies -- on the states of tests/row_walk_cases.py (every grid of tests/walk_grid_cases.py with rows
+neighbour lists, bodies, pair statistics -- on the states of tests/row_walk_cases.py (every grid of tests/walk_grid_cases.py with rows
 on its walls, and D7 with one long run), without a GPU: the floors the states reach, the walk over the cell table
 against all pairs, the derived fields against float64 under the bound tests/test_derived_cpu.py derives, what the
-staged walk's restatement counts, and the premise of the case whose rows lie outside the grid."""
+staged walk's restatement counts, the premise of the case whose rows lie outside the grid, and the premises of the pair
+statistics' cases: tables with pairs in most bins, a slice that the counters tell from the derived fields', and a
+restatement that stays cheap."""
 import functools
+import time
 
 import numpy as np
 import pytest
@@ -12,12 +15,15 @@ import bodies_restatement as BR
 import derived_restatement as DR
 import grid_states as G
 import neighbour_restatement as NR
+import pair_restatement as PR
+import pair_states as PST
 import row_walk_cases as R
 from test_derived_cpu import hold_to_float64
 
 F = np.float32
 CASES = R.GRIDS + ["long run"]
 DERIVE_SLICE, NBR_SLICE = 320, 640      # derived.hip's kDeriveSlice, neighbours.hip's kNbrSlice
+PAIR_SLICE = PST.SLICE                  # pairs.hip's kPairSlice
 RATIOS, COUNTED = {}, {}
 
 
@@ -100,7 +106,7 @@ def test_the_derived_fields_stay_within_their_bound_of_float64(name):
 def counted(name):
     if name not in COUNTED:
         c = case(name)
-        COUNTED[name] = {s: R.staged_direct(c["rows"], c["cells"], c["h"], c["D"], s) for s in (DERIVE_SLICE, NBR_SLICE)}
+        COUNTED[name] = {s: R.staged_direct(c["rows"], c["cells"], c["h"], c["D"], s) for s in (PAIR_SLICE, DERIVE_SLICE, NBR_SLICE)}
     return COUNTED[name]
 
 
@@ -121,6 +127,47 @@ def test_what_the_staged_walk_counts():
     direct = [name for name in R.GRIDS if counted(name)[DERIVE_SLICE][1] > 0]
     print(f"grids with direct runs at slice {DERIVE_SLICE}: {direct}")
     assert direct
+
+
+def test_the_pair_walks_slice_shows_in_what_it_counts():
+    """The pair statistics stage runs of up to 192 rows, the derived fields runs of up to 320: the counters
+    tests/test_gpu_row_walks.py pins tell the two apart on D102's and on D40's walls state (a pair walk built with the
+    derived fields' slice gives the same words and other counters); the long run has direct runs at 192 as well."""
+    assert PAIR_SLICE == 192 < DERIVE_SLICE
+    for name in CASES:
+        got = counted(name)
+        print(f"{name}: slice {PAIR_SLICE}: {got[PAIR_SLICE]}, slice {DERIVE_SLICE}: {got[DERIVE_SLICE]}")
+        # (D1's one cell holds 256 rows: every run of it is longer than the pairs' slice)
+        assert (got[PAIR_SLICE][0] > 0 or name == "D1") and sum(got[PAIR_SLICE]) == sum(got[DERIVE_SLICE]) and got[PAIR_SLICE][1] >= got[DERIVE_SLICE][1], name
+    for name in ("D102", "D40"):
+        assert counted(name)[PAIR_SLICE] != counted(name)[DERIVE_SLICE], name
+    assert counted("long run")[PAIR_SLICE][1] > 0
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_the_pair_tables_of_the_states(name):
+    """What tests/test_gpu_row_walks.py asks of restatement (a) on one state -- the pairs at the three radii, found once
+    each, and two tables of each -- costs under 5 s on one core (a cap against a runaway state, not a performance
+    claim); at radius h the 32-bin table of every grid's walls state has pairs in at least half its bins, and its
+    total is half the entries of the all-pairs lists; no term saturates."""
+    c = case(name)
+    t0 = time.perf_counter()
+    tables = {}
+    for radius in c["lengths"]:
+        p = PR.prepared(c["pos"], c["vel"], c["h"], radius)
+        tables[radius] = [p.table(PR.edges2(radius, c["h"], bins)) for bins in (0, 128)]
+    seconds = time.perf_counter() - t0
+    table = tables[0.0][0]
+    total = int(table["pairs"].sum())
+    print(f"{name}: {seconds:.2f} s; {total} pairs within h, {int((table['pairs'] > 0).sum())} of 32 bins hold some")
+    assert seconds < 5.0, name
+    assert 2 * total == int(NR.all_pairs(c["pos"], c["h"], 0.0)[0][-1]) > 0, name
+    if name != "long run":
+        assert (table["pairs"] > 0).sum() >= 16, name
+    for radius in c["lengths"]:
+        for t in tables[radius]:
+            assert int(t["pairs"].sum()) == int(tables[radius][0]["pairs"].sum()) and not t["saturated"].any(), (name, radius)
+    assert int(tables[c["lengths"][1]][0]["pairs"].sum()) <= total
 
 
 def test_staged_direct_by_hand():
@@ -164,3 +211,7 @@ def test_after_one_step_every_row_of_D1_lies_outside_the_grid():
         out = BR.bodies(rows, ids, cells, h, D, radius)
         k, _, links = BR.all_pairs_components(p, h, radius)
         assert (out["num_bodies"], out["links"]) == (k, links) and 2 * links == int(want[0][-1])
+        # ... and the pair statistics: more than 10,000 pairs at every radius, the bodies' links
+        pairs = PR.all_pairs(p, after["vel"], h, radius, 9)["pairs"]
+        print(f"D1 after a step, radius {radius}: {int(pairs.sum())} pairs, by bin {pairs.tolist()}")
+        assert int(pairs.sum()) == links > 10000
