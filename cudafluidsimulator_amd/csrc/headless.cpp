@@ -81,14 +81,13 @@ static bool write_ply(const char *dir, const char *pattern, int f, long long cou
     return (fclose(out) == 0) && ok;
 }
 
-// SPH_FREE_FRAMES_DIR=<dir>: what the window would have shown after frame f, as <dir>/frame_%04d.ppm (binary P6)
-static bool write_frame(Simulator *simulator, const char *dir, int f, int field) {
-    int w = 0, h = 0;
-    const unsigned char *rgb = field < 0                ? simulator->renderFrame(&w, &h)
-                               : field == kShadeColumn ? simulator->renderColumn(&w, &h)
-                               : field == kShadeLiquid ? simulator->renderLiquid(&w, &h)
-                                                       : simulator->renderField(field, &w, &h);
-    return rgb && write_ppm(dir, "frame_%04d.ppm", f, w, h, rgb);
+// SPH_FREE_FRAMES_DIR=<dir>: what the window would have shown after frame f, as <dir>/frame_%04d.ppm (binary P6).
+// render_frame: the picture, or NULL where the run renders none (a multi-GPU run; the simulator has said so).
+static const unsigned char *render_frame(Simulator *simulator, int field, int *w, int *h) {
+    return field < 0                ? simulator->renderFrame(w, h)
+           : field == kShadeColumn ? simulator->renderColumn(w, h)
+           : field == kShadeLiquid ? simulator->renderLiquid(w, h)
+                                   : simulator->renderField(field, w, h);
 }
 
 // SPH_FREE_SLICE=speed|density|pressure: beside each frame the cut plane z = 5 of that field, sampled on 400 x 400
@@ -369,6 +368,7 @@ void startVisualization(Simulator *simulator) {
     int every = 1;
     if (const char *e = getenv("SPH_FREE_FRAME_EVERY")) every = atoi(e) > 0 ? atoi(e) : 1;
     const int field = framesDir ? shade_field() : -1;
+    bool frameFiles = framesDir != NULL; // false: no frame files (any more)
     int slice = framesDir ? env_field("SPH_FREE_SLICE", "writing no slices") : -1;
     float surfaceIso = 0.f; // 0: no surfaces
     if (framesDir && getenv("SPH_FREE_SURFACE")) {
@@ -468,7 +468,12 @@ void startVisualization(Simulator *simulator) {
         if (framesDir && neighbourRadius > 0.f && f % every == 0 && !write_neighbours(simulator, framesDir, f, neighbourRadius))
             neighbourRadius = 0.f;
         if (framesDir && pairBins > 0 && f % every == 0 && !write_pair_stats(simulator, framesDir, f, pairBins)) pairBins = 0;
-        if (framesDir && f % every == 0 && !write_frame(simulator, framesDir, f, field)) framesDir = NULL;
+        if (framesDir && frameFiles && f % every == 0) {
+            int w = 0, h = 0;
+            const unsigned char *rgb = render_frame(simulator, field, &w, &h);
+            if (!rgb) frameFiles = false; // no picture to write: the frames stop, the other outputs go on
+            else if (!write_ppm(framesDir, "frame_%04d.ppm", f, w, h, rgb)) framesDir = NULL; // the directory takes no files
+        }
         if (framesDir && slice >= 0 && f % every == 0 && !write_slice(simulator, framesDir, f, slice)) slice = -1;
         if (framesDir && surfaceIso > 0.f && f % every == 0 && !write_surface(simulator, framesDir, f, surfaceIso)) surfaceIso = 0.f;
         if (framesDir && stats && f % every == 0 && !write_stats(simulator, stats, f)) {
