@@ -38,6 +38,7 @@ EXPORTED_SYMBOLS = [
     "sph_track_bodies", "sph_body_tracks_host", "sph_track_reset", "sph_get_body_track_stats",
     "sph_neighbour_lists", "sph_neighbours_host", "sph_get_neighbour_stats",
     "sph_pair_edges", "sph_pair_statistics", "sph_pair_statistics_host", "sph_pair_values", "sph_get_pair_stats",
+    "sph_cast_rays", "sph_cast_host", "sph_render_view", "sph_download_view_buffer", "sph_get_cast_stats",
 ]
 SPH_API_VERSION = 3
 SPH_SHADE_FLAT, SPH_SHADE_COUNT = 0, 1
@@ -65,6 +66,12 @@ SPH_NEIGHBOURS_WALK_ORDER = 1
 SPH_HAS_PAIR_STATS = 1
 PAIR_MAX_BINS = 128
 PAIR_SUMS = ("d2", "w2", "a", "l2")   # SPH_PAIR_SUM_*
+SPH_HAS_RAY_CAST = 1
+CAST_MAX_RAYS = 1 << 24
+CAST_MISS = 0xFFFFFFFFFFFFFFFF
+SPH_VIEW_FLAT, SPH_VIEW_FIELD = 0, 1
+VIEW_SHADES = {"flat": SPH_VIEW_FLAT, "speed": SPH_VIEW_FIELD + SPH_FIELD_SPEED, "density": SPH_VIEW_FIELD + SPH_FIELD_DENSITY,
+               "pressure": SPH_VIEW_FIELD + SPH_FIELD_PRESSURE}
 BODY_TABLE = ("label", "count", "min_x", "min_y", "min_z", "max_x", "max_y", "max_z")   # words of a table row
 DIAG_SUMS = ("x", "y", "z", "vx", "vy", "vz", "rho", "prs", "v2")   # SPH_DIAG_SUM_*
 BODY_SUMS = DIAG_SUMS + ("xx", "yy", "zz", "xy", "xz", "yz", "lx", "ly", "lz")   # ... then SPH_BODY_SUM_*
@@ -338,6 +345,33 @@ class SphPairStats(C.Structure):
                 ("runs_staged", C.c_uint64), ("runs_direct", C.c_uint64), ("seconds", C.c_double)]
 
 
+class SphRay(C.Structure):
+    _fields_ = [("o", C.c_float * 3), ("t_min", C.c_float), ("d", C.c_float * 3), ("t_max", C.c_float)]
+
+
+class SphCastOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("radius", C.c_float)]
+
+
+class SphViewOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("eye", C.c_float * 3), ("target", C.c_float * 3), ("up", C.c_float * 3),
+                ("tan_half_x", C.c_float), ("tan_half_y", C.c_float), ("near", C.c_float), ("far", C.c_float),
+                ("radius", C.c_float), ("shade", C.c_int32), ("value_lo", C.c_float), ("value_hi", C.c_float),
+                ("light", C.c_float * 3), ("edge_radius", C.c_float)]
+
+
+class SphCastStats(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("pad_", C.c_int32), ("calls", C.c_int64), ("rays", C.c_uint64),
+                ("layers", C.c_uint64), ("tests", C.c_uint64), ("seconds", C.c_double)]
+
+
+def ray_dtype():
+    """the numpy dtype of an SphRay: o (3 floats), t_min, d (3 floats), t_max"""
+    import numpy as np
+    return np.dtype([("o", "<f4", (3,)), ("t_min", "<f4"), ("d", "<f4", (3,)), ("t_max", "<f4")])
+
+
 def pair_bin_dtype():
     """the numpy dtype of an SphPairBinRaw row: pairs, sums as (4, 2) uint64 -- [k, 0] the low and [k, 1] the high word of
     sum k (two's complement; PAIR_SUMS names the sums) --, saturated"""
@@ -500,5 +534,10 @@ def load_library():
     L.sph_pair_statistics_host.argtypes = [hp, C.POINTER(C.POINTER(SphPairBinRaw)), C.POINTER(fp), C.POINTER(C.c_int)]
     L.sph_pair_values.argtypes = [C.POINTER(SphPairBinRaw), fp, C.c_int, C.POINTER(SphSettings), C.c_int64, C.POINTER(SphPairValues)]
     L.sph_get_pair_stats.argtypes = [hp, C.POINTER(SphPairStats), C.c_int]
+    L.sph_cast_rays.argtypes = [hp, C.POINTER(SphRay), C.c_int, C.POINTER(SphCastOptions)]
+    L.sph_cast_host.argtypes = [hp, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_int)]
+    L.sph_render_view.argtypes = [hp, C.POINTER(SphViewOptions)]
+    L.sph_download_view_buffer.argtypes = [hp, C.POINTER(C.c_uint64)]
+    L.sph_get_cast_stats.argtypes = [hp, C.POINTER(SphCastStats), C.c_int]
     _lib = L
     return L

@@ -346,6 +346,38 @@ static bool write_neighbours(Simulator *simulator, const char *dir, int f, float
     return ok;
 }
 
+// SPH_FREE_VIEW=ex,ey,ez,tx,ty,tz[,flat|speed|density|pressure]: beside each written frame the state seen from the eye
+// (ex, ey, ez) looking at (tx, ty, tz) (sph_render_view: 800 x 600, up (0, 1, 0), every other option at its default)
+// as <dir>/view_%04d.ppm.  parse_view: the options, or false after one line on stderr.
+static bool parse_view(const char *e, SphViewOptions *o) {
+    SphViewOptions v = {};
+    float c[6];
+    int used = 0, k = 0; // k: SPH_VIEW_FLAT, SPH_VIEW_FIELD + SPH_FIELD_*
+    const char *names[4] = {"flat", "speed", "density", "pressure"};
+    bool ok = sscanf(e, "%f,%f,%f,%f,%f,%f%n", &c[0], &c[1], &c[2], &c[3], &c[4], &c[5], &used) == 6;
+    if (ok && e[used]) { // the shade's name and nothing else
+        while (k < 4 && strcmp(e + used + 1, names[k])) ++k;
+        ok = e[used] == ',' && k < 4;
+    }
+    for (int a = 0; ok && a < 6; ++a) ok = std::isfinite(c[a]);
+    ok = ok && !(c[0] == c[3] && c[1] == c[4] && c[2] == c[5]);
+    if (!ok) {
+        fprintf(stderr, "sph: SPH_FREE_VIEW=%s is not ex,ey,ez,tx,ty,tz[,flat|speed|density|pressure] with an eye off its target -- writing no views\n", e);
+        return false;
+    }
+    for (int a = 0; a < 3; ++a) v.eye[a] = c[a], v.target[a] = c[3 + a];
+    v.up[1] = 1.f;
+    v.shade = k;
+    *o = v;
+    return true;
+}
+
+static bool write_view(Simulator *simulator, const char *dir, int f, const SphViewOptions &view) {
+    int w = 0, h = 0;
+    const unsigned char *rgb = simulator->renderView(view, &w, &h);
+    return rgb && write_ppm(dir, "view_%04d.ppm", f, w, h, rgb);
+}
+
 // SPH_FREE_STATS=1: for each written frame one JSON line of run diagnostics (Simulator::diagnostics) in
 // <dir>/stats.jsonl; doubles as %.17g, which reads back to the same double
 static bool write_stats(Simulator *simulator, FILE *out, int f) {
@@ -447,6 +479,8 @@ void startVisualization(Simulator *simulator) {
         else
             pairBins = (int)v;
     }
+    SphViewOptions view = {};
+    bool views = framesDir && getenv("SPH_FREE_VIEW") && parse_view(getenv("SPH_FREE_VIEW"), &view);
     FILE *stats = NULL;
     if (framesDir && getenv("SPH_FREE_STATS") && atoi(getenv("SPH_FREE_STATS")) != 0) {
         const std::string path = std::string(framesDir) + "/stats.jsonl";
@@ -474,6 +508,7 @@ void startVisualization(Simulator *simulator) {
             if (!rgb) frameFiles = false; // no picture to write: the frames stop, the other outputs go on
             else if (!write_ppm(framesDir, "frame_%04d.ppm", f, w, h, rgb)) framesDir = NULL; // the directory takes no files
         }
+        if (framesDir && views && f % every == 0 && !write_view(simulator, framesDir, f, view)) views = false;
         if (framesDir && slice >= 0 && f % every == 0 && !write_slice(simulator, framesDir, f, slice)) slice = -1;
         if (framesDir && surfaceIso > 0.f && f % every == 0 && !write_surface(simulator, framesDir, f, surfaceIso)) surfaceIso = 0.f;
         if (framesDir && stats && f % every == 0 && !write_stats(simulator, stats, f)) {

@@ -312,24 +312,7 @@ __global__ __launch_bounds__(256) void k_field_range(const float4 *__restrict__ 
     }
 }
 
-// (r, g, b) = bytes 0, 1, 2: blue - cyan - green - yellow - red over q = 0..255, integers only
-__device__ __forceinline__ uint32_t field_ramp(uint32_t q) {
-    if (q < 64u) return ((4u * q) << 8) | 0xFF0000u;
-    if (q < 128u) return 0x00FF00u | ((255u - 4u * (q - 64u)) << 16);
-    if (q < 192u) return (4u * (q - 128u)) | 0x00FF00u;
-    return 0xFFu | ((255u - 4u * (q - 192u)) << 8);
-}
-
-// the quantiser of the field and column frames: q = 0..255 of s on the scale lo..hi
-__device__ __forceinline__ uint32_t field_quantise(float s, float lo, float hi) {
-    uint32_t q = 0u;
-    if (hi != lo) {
-        const float u = ((s - lo) / (hi - lo)) * 256.f;
-        if (u == u) q = (uint32_t)(int)fminf(fmaxf(floorf(u), 0.f), 255.f); // (NaN: q = 0)
-    }
-    return q;
-}
-
+// (field_ramp, field_quantise: sph_device.h)
 __device__ __forceinline__ uint32_t field_rgb(unsigned long long m, uint32_t c, uint32_t e, float lo, float hi) {
     const uint32_t d = (uint32_t)(m >> 32);
     if (e != 0xFFFFFFFFu && e <= d) return 0xFFFFFFu; // GL_LESS, lines drawn first
@@ -337,20 +320,7 @@ __device__ __forceinline__ uint32_t field_rgb(unsigned long long m, uint32_t c, 
     return field_ramp(field_quantise(__uint_as_float((uint32_t)m), lo, hi));
 }
 
-// four pixels = 12 bytes = three dwords per thread (rgb is padded to a multiple of four pixels); colour(p) = 0xBBGGRR of pixel p
-template <class Colour>
-__device__ __forceinline__ void compose_quad(int npix, uint32_t *__restrict__ rgb, Colour colour) {
-    const int g = blockIdx.x * 256 + threadIdx.x;
-    const int p0 = g * 4;
-    if (p0 >= npix) return;
-    uint32_t c[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) c[k] = (p0 + k < npix) ? colour(p0 + k) : 0u;
-    rgb[g * 3 + 0] = c[0] | (c[1] << 24);
-    rgb[g * 3 + 1] = (c[1] >> 8) | (c[2] << 16);
-    rgb[g * 3 + 2] = (c[2] >> 16) | (c[3] << 8);
-}
-
+// (compose_quad: sph_device.h)
 __global__ __launch_bounds__(256) void k_render_compose(const uint32_t *__restrict__ depth, const uint32_t *__restrict__ count,
                                                         const uint32_t *__restrict__ edge, int npix, int shade,
                                                         uint32_t *__restrict__ rgb) {
@@ -770,6 +740,13 @@ void sph_launch_render_field(const RenderParams &R, const FrameView &V, const fl
     if (reduce) k_field_range<<<min(blocks_of(n), 1024), 256, 0, s>>>(vel4, n, field, V.range);
     launch_splat(R, pos4, n, plain, SplatFrame<FieldPayload>{{V.packed, vel4, field}, V.count}, s);
     k_field_compose<<<blocks_of((npix + 3) / 4), 256, 0, s>>>(V.packed, V.count, V.edge, V.range, npix, V.depth, V.rgb);
+}
+
+void sph_launch_field_range(const float4 *vel4, int n, int field, bool autoRange, float lo, float hi, uint32_t *range, hipStream_t s) {
+    const bool reduce = autoRange && n > 0;
+    k_frame_clear<<<1, 256, 0, s>>>(nullptr, nullptr, 0ull, nullptr, 0, range, reduce ? 0xFFFFFFFFu : __builtin_bit_cast(uint32_t, lo),
+                                    reduce ? 0u : __builtin_bit_cast(uint32_t, hi), nullptr);
+    if (reduce) k_field_range<<<min(blocks_of(n), 1024), 256, 0, s>>>(vel4, n, field, range);
 }
 
 void sph_launch_render_column(const RenderParams &R, const FrameView &V, const float4 *pos4, int n, bool plain, float h, float h2,

@@ -355,6 +355,44 @@ bool Simulator::pairStatistics(int bins, float radius, const SphPairBinRaw **row
     return true;
 }
 
+bool Simulator::castRays(const SphRay *rays, int m, float radius, const uint64_t **words) {
+    if (multi) {
+        fprintf(stderr, "sph: castRays: a multi-GPU run (SPH_GPUS > 1) casts no rays\n");
+        return false;
+    }
+    if (!impl) return false;
+    SphCastOptions o = {};
+    o.struct_size = (int32_t)sizeof o;
+    o.radius = radius;
+    const int rc = sph_cast_rays(impl, rays, m, &o);
+    if (rc == SPH_ESTATE || rc == SPH_EINVAL) { // (SPH_SWEEP=linked, a radius longer than h, ...): no words, nothing broken
+        fprintf(stderr, "sph: castRays: %s\n", sph_last_error(impl));
+        return false;
+    }
+    check(impl, rc, "sph_cast_rays");
+    check(impl, sph_cast_host(impl, words, NULL), "sph_cast_host");
+    return true;
+}
+
+const unsigned char *Simulator::renderView(const SphViewOptions &view, int *width, int *height) {
+    if (multi) {
+        fprintf(stderr, "sph: renderView: frames of a multi-GPU run (SPH_GPUS > 1) are not rendered\n");
+        return NULL;
+    }
+    if (!impl) return NULL;
+    SphViewOptions o = view;
+    o.struct_size = (int32_t)sizeof o;
+    const int rc = sph_render_view(impl, &o);
+    if (rc == SPH_ESTATE || rc == SPH_EINVAL) { // (SPH_SWEEP=linked, a camera that looks along `up`, ...): no frame, nothing broken
+        fprintf(stderr, "sph: renderView: %s\n", sph_last_error(impl));
+        return NULL;
+    }
+    check(impl, rc, "sph_render_view");
+    const unsigned char *f = sph_frame_host(impl, width, height);
+    if (!f) check(impl, SPH_EHIP, "sph_frame_host");
+    return f;
+}
+
 bool Simulator::getVelocity(float *vel_xyz) {
     if (multi || !impl || !vel_xyz) return false;
     check(impl, sph_download_state(impl, NULL, vel_xyz, NULL, NULL), "sph_download_state");

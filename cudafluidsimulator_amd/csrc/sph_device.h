@@ -314,6 +314,38 @@ __device__ __forceinline__ uint32_t field_bits(const float4 v, int field) {
     return __float_as_uint(s);
 }
 
+// (r, g, b) = bytes 0, 1, 2: blue - cyan - green - yellow - red over q = 0..255, integers only
+__device__ __forceinline__ uint32_t field_ramp(uint32_t q) {
+    if (q < 64u) return ((4u * q) << 8) | 0xFF0000u;
+    if (q < 128u) return 0x00FF00u | ((255u - 4u * (q - 64u)) << 16);
+    if (q < 192u) return (4u * (q - 128u)) | 0x00FF00u;
+    return 0xFFu | ((255u - 4u * (q - 192u)) << 8);
+}
+
+// the quantiser of the field and column frames: q = 0..255 of s on the scale lo..hi
+__device__ __forceinline__ uint32_t field_quantise(float s, float lo, float hi) {
+    uint32_t q = 0u;
+    if (hi != lo) {
+        const float u = ((s - lo) / (hi - lo)) * 256.f;
+        if (u == u) q = (uint32_t)(int)fminf(fmaxf(floorf(u), 0.f), 255.f); // (NaN: q = 0)
+    }
+    return q;
+}
+
+// four pixels = 12 bytes = three dwords per thread (rgb is padded to a multiple of four pixels); colour(p) = 0xBBGGRR of pixel p
+template <class Colour>
+__device__ __forceinline__ void compose_quad(int npix, uint32_t *__restrict__ rgb, Colour colour) {
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    const int p0 = g * 4;
+    if (p0 >= npix) return;
+    uint32_t c[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) c[k] = (p0 + k < npix) ? colour(p0 + k) : 0u;
+    rgb[g * 3 + 0] = c[0] | (c[1] << 24);
+    rgb[g * 3 + 1] = (c[1] >> 8) | (c[2] << 16);
+    rgb[g * 3 + 2] = (c[2] >> 16) | (c[3] << 8);
+}
+
 // ---- the analysis passes ----
 // The cell-sorted stream of the last grid build, as every pass that walks it reads it: sorted row j is
 // position(j) = (x, y, z, id) and velocity(j) = (vx, vy, vz, rho).  Two layouts, told apart by the stride alone: the
@@ -523,6 +555,43 @@ int sph_pair_rows(int n, int cus, bool plain, int workgroups);
 void sph_launch_pair_table(const PairEdges &E, const PairArgs &A, hipStream_t s);
 // clear + walk + join; plain = the check path
 void sph_launch_pair_statistics(const DevParams &P, const PairArgs &A, bool plain, hipStream_t s);
+
+// ---- ray casting and the view frame (rays.hip; defined in DESIGN.md section 10n) ----
+// The view's camera with every default resolved: the basis computed by the host, passed as data
+struct ViewCamera {
+    float eye[3], fwd[3], s[3], u[3];
+    float tanX, tanY, tNear, tFar;
+    int width, height;
+    float Wf, Hf;
+};
+struct CastArgs {
+    StreamView S;            // the candidates
+    float r, r2;             // of the spheres; r r, rounded once
+    const SphRay *rays;      // [m] a batch in the caller's order, or null: the pixel-centre rays of `cam`
+    int m;                   // rays (a view: width x height)
+    ViewCamera cam;
+    unsigned long long *words; // [m] the result (a view: pixel (c, row) at [row width + c])
+    uint32_t *rows;          // [m] a view: the winner's row of the stream (0 for a miss: read for hits only); a batch: null
+    unsigned long long *partials; // [2 sph_cast_waves] default path: layers and tests of every wave ...
+    unsigned long long *counters; // [2] ... added up here behind the walk: layers, tests
+};
+constexpr int kCastCounters = 2;
+// waves of the default path's launch: 64 rays of a batch, an 8 x 8 tile of a view each
+int sph_cast_waves(const CastArgs &A);
+// one word per ray; plain = the one-thread-per-ray check path over every row
+void sph_launch_cast(const DevParams &P, const CastArgs &A, bool plain, hipStream_t s);
+// The view's picture from its words: shade: SPH_VIEW_*; range: the bits of lo / hi of a field
+// shade's scale; light: not normalised; edgeRadius < 0: no edges
+struct ViewShade {
+    int shade;
+    float light[3];
+    float edgeRadius;
+    const uint32_t *range;
+};
+void sph_launch_view_compose(const DevParams &P, const CastArgs &A, const ViewShade &V, uint32_t *rgb, hipStream_t s);
+// the bits of lo / hi of the field frame's colour scale into range[0..1]: the given ones, or (autoRange, n > 0) the
+// minimum and maximum of the field over vel4[0, n) (render.hip: the field frame's reduction)
+void sph_launch_field_range(const float4 *vel4, int n, int field, bool autoRange, float lo, float hi, uint32_t *range, hipStream_t s);
 
 // ---- the surface mesh (surface.hip; defined in DESIGN.md section 10d) ----
 struct SurfaceArgs {

@@ -1,6 +1,6 @@
-// The visualiser's frame: sph_render_frame / sph_render_field / sph_render_column / sph_render_liquid and what reads
-// their results
-// (kernels: render.hip).
+// The visualiser's frame: sph_render_frame / sph_render_field / sph_render_column / sph_render_liquid / sph_render_view
+// and what reads their results
+// (kernels: render.hip; the view's: rays.hip).
 #include "sph_handle.h"
 
 #include <cmath>
@@ -108,7 +108,7 @@ int frame_finish(sph_handle *h, FrameKind kind, Launch launch) {
     f.pass.valid = true;
     f.kind = kind;
     const OutboundCopy frame{f.host.get(), f.rgb.get(), (size_t)f.rp.width * f.rp.height * 3};
-    if (kind == FrameKind::Flat || kind == FrameKind::Liquid) return outbound_send(h, f.pass.out, {frame}); // (no colour scale to report)
+    if (kind == FrameKind::Flat || kind == FrameKind::Liquid || kind == FrameKind::View) return outbound_send(h, f.pass.out, {frame}); // (no colour scale to report)
     return outbound_send(h, f.pass.out, {frame, {f.rangeHost.get(), f.range.get(), 2 * sizeof(uint32_t)}});
 }
 
@@ -118,6 +118,7 @@ int last_frame_was(sph_handle *h, FrameKind kind) {
     if (h->frame.pass.valid && h->frame.kind == kind) return SPH_OK;
     return fail(h, SPH_ESTATE, kind == FrameKind::Field    ? "the last render was not a field frame (sph_render_field)"
                                : kind == FrameKind::Column ? "the last render was not a column frame (sph_render_column)"
+                               : kind == FrameKind::View   ? "the last render was not a view frame (sph_render_view)"
                                                            : "the last render was not a liquid frame (sph_render_liquid)");
 }
 
@@ -169,6 +170,7 @@ int sph_download_frame_buffers(sph_handle *h, uint32_t *depth_bits, uint32_t *co
     if (!f.pass.valid) return fail(h, SPH_ESTATE, "sph_render_frame must come first");
     if (f.kind == FrameKind::Column) return fail(h, SPH_ESTATE, "the last render was a column frame: it writes no depth or count (sph_download_column_buffer)");
     if (f.kind == FrameKind::Liquid) return fail(h, SPH_ESTATE, "the last render was a liquid frame: it writes no point depth or count (sph_download_liquid_buffers)");
+    if (f.kind == FrameKind::View) return fail(h, SPH_ESTATE, "the last render was a view frame: it writes no point depth or count (sph_download_view_buffer)");
     HIPCHK(h, hipStreamSynchronize(h->compute));
     const size_t bytes = (size_t)f.rp.width * f.rp.height * sizeof(uint32_t);
     if (depth_bits) HIPCHK(h, hipMemcpy(depth_bits, f.depth, bytes, hipMemcpyDeviceToHost));
@@ -279,6 +281,109 @@ int sph_download_liquid_buffers(sph_handle *h, uint32_t *front_bits, uint32_t *s
         HIPCHK(h, hipMemcpy(n4.data(), f.normals, npix * sizeof(float4), hipMemcpyDeviceToHost));
         for (size_t i = 0; i < npix; ++i) normals_xyz[3 * i] = n4[i].x, normals_xyz[3 * i + 1] = n4[i].y, normals_xyz[3 * i + 2] = n4[i].z;
     }
+    return SPH_OK;
+}
+
+// the view's basis, fp32, every operation rounded on its own; false: g or s0 vanishes or is not finite
+static bool view_basis(const SphViewOptions &o, ViewCamera &C) {
+    const auto dot = [](const float (&a)[3], const float (&b)[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; };
+    const auto usable = [&](const float (&a)[3]) {
+        const float d = dot(a, a);
+        return std::isfinite(d) && d > 0.f && std::isfinite(a[0]) && std::isfinite(a[1]) && std::isfinite(a[2]);
+    };
+    float g[3], s0[3];
+    for (int a = 0; a < 3; ++a) g[a] = o.target[a] - o.eye[a];
+    if (!usable(g)) return false;
+    const float glen = sqrtf(dot(g, g));
+    for (int a = 0; a < 3; ++a) C.fwd[a] = g[a] / glen;
+    for (int a = 0; a < 3; ++a) {
+        const int b = (a + 1) % 3, c = (a + 2) % 3;
+        s0[a] = C.fwd[b] * o.up[c] - C.fwd[c] * o.up[b];
+    }
+    if (!usable(s0)) return false;
+    const float slen = sqrtf(dot(s0, s0));
+    for (int a = 0; a < 3; ++a) C.s[a] = s0[a] / slen;
+    for (int a = 0; a < 3; ++a) {
+        const int b = (a + 1) % 3, c = (a + 2) % 3;
+        C.u[a] = C.s[b] * C.fwd[c] - C.s[c] * C.fwd[b];
+    }
+    for (int a = 0; a < 3; ++a) C.eye[a] = o.eye[a];
+    return true;
+}
+
+int sph_render_view(sph_handle *h, const SphViewOptions *opt) {
+    if (!h) return SPH_EINVAL;
+    SPH_ON_DEVICE(h);
+    int rc = analysis_begin(h, "the view frame", ": multi-GPU frames are not rendered");
+    if (rc) return rc;
+    const char *unset = "SphViewOptions.struct_size is not set";
+    if (!opt) return fail(h, SPH_EINVAL, unset); // (no defaults: a camera has to be given)
+    SphViewOptions o{};
+    ViewCamera cam{};
+    auto rest = [&](const SphViewOptions &o) -> const char * {
+        for (int a = 0; a < 3; ++a)
+            if (!std::isfinite(o.eye[a]) || !std::isfinite(o.target[a]) || !std::isfinite(o.up[a])) return "eye, target and up must be finite";
+        if (!view_basis(o, cam)) return "target - eye and (target - eye) x up must not vanish";
+        const bool noTan = o.tan_half_x == 0.f && o.tan_half_y == 0.f;
+        if (!noTan && !(o.tan_half_x > 0.f && o.tan_half_x <= 1024.f && o.tan_half_y > 0.f && o.tan_half_y <= 1024.f))
+            return "tan_half_x / tan_half_y must both be 0 or both in (0, 1024]";
+        if (!(o.near >= 0.f) || !std::isfinite(o.near)) return "near must be finite and >= 0 (0: h)";
+        if (!(o.far >= 0.f)) return "far must be >= 0 (0: +inf)";
+        if (o.far != 0.f && o.far < (o.near == 0.f ? h->P.h : o.near)) return "far < near";
+        if (const char *bad = bad_cast_radius(h, o.radius)) return bad;
+        if (o.shade != SPH_VIEW_FLAT && bad_field(o.shade - SPH_VIEW_FIELD)) return "unknown shade";
+        if (const char *bad = bad_value_range(o.value_lo, o.value_hi)) return bad;
+        for (float l : o.light)
+            if (!std::isfinite(l)) return "light must be finite";
+        if (!std::isfinite(o.edge_radius)) return "edge_radius must be finite";
+        return nullptr;
+    };
+    if ((rc = frame_begin(h, opt, unset, o, nullptr, rest, FrameKind::View))) return rc;
+    FrameState &f = h->frame;
+    cam.width = f.rp.width, cam.height = f.rp.height;
+    cam.Wf = f.rp.Wf, cam.Hf = f.rp.Hf;
+    cam.tanY = o.tan_half_y, cam.tanX = o.tan_half_x;
+    if (o.tan_half_x == 0.f && o.tan_half_y == 0.f) {
+        cam.tanY = 0.41421357f;
+        cam.tanX = cam.tanY * (cam.Wf / cam.Hf);
+    }
+    cam.tNear = o.near == 0.f ? h->P.h : o.near;
+    cam.tFar = o.far == 0.f ? INFINITY : o.far;
+    bool plain;
+    if ((rc = cast_path(h, (size_t)cam.width * cam.height, plain))) return rc;
+    if ((rc = analysis_grid(h))) return rc;
+    CastArgs A{};
+    A.m = cam.width * cam.height;
+    A.cam = cam;
+    A.words = f.packed;
+    A.rows = f.count;
+    if ((rc = cast_prepare(h, A, o.radius, plain))) return rc;
+    ViewShade V{};
+    V.shade = o.shade;
+    const bool dark = o.light[0] == 0.f && o.light[1] == 0.f && o.light[2] == 0.f;
+    const float sun[3] = {-0.35f, 0.8f, 0.5f};
+    for (int k = 0; k < 3; ++k) V.light[k] = dark ? sun[k] : o.light[k];
+    V.edgeRadius = o.edge_radius == 0.f ? 0.002f * h->P.boxDim : o.edge_radius;
+    V.range = f.range;
+    const bool autoRange = o.value_lo == 0.f && o.value_hi == 0.f;
+    // vel4[cur]: the rows sph_render_field reduces its range over
+    rc = frame_finish(h, FrameKind::View, [&] {
+        if (o.shade != SPH_VIEW_FLAT)
+            sph_launch_field_range(h->vel4[h->cur], h->n, o.shade - SPH_VIEW_FIELD, autoRange, o.value_lo, o.value_hi, f.range, h->compute);
+        sph_launch_cast(h->P, A, plain, h->compute);
+        sph_launch_view_compose(h->P, A, V, f.rgb, h->compute);
+    });
+    if (rc) return rc;
+    h->castViews += 1;
+    cast_account(h, A, plain);
+    return SPH_OK;
+}
+
+int sph_download_view_buffer(sph_handle *h, uint64_t *words) {
+    if (!h || !words) return SPH_EINVAL;
+    if (int rc = last_frame_was(h, FrameKind::View)) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->compute));
+    HIPCHK(h, hipMemcpy(words, h->frame.packed, (size_t)h->frame.rp.width * h->frame.rp.height * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return SPH_OK;
 }
 

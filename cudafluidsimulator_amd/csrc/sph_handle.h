@@ -58,6 +58,8 @@ using sph_owned::PinnedBuf;
 //                                          (at most one per tile) instead of 16 per compute unit; same words
 //   SPH_PAIRS_SHED_BITS   62       call    33 .. 62: a high word of that path's table sheds into its top word at 2^bits
 //                                          instead of 2^62 (pairs.hip); same words
+//   SPH_CAST_PLAIN        0        call    non-zero: sph_cast_rays / sph_render_view take the check path (one thread per ray, every
+//                                          row of the stream); admitted while rays x particles <= 2^32
 //   SPH_MGPU_THREADS      0        (libsph_mgpu.so, its own object: sph_mgpu_create in mgpu_state.cpp) non-zero: one
 //                                          host thread per local slab
 // (The SPH_* variables the command-line front end reads -- SPH_SWEEP, SPH_GPUS, SPH_TRANSPORT, SPH_RECUT_EVERY,
@@ -114,7 +116,7 @@ struct Pass {
 };
 
 // What the last render drew (sph_frame.hip): decides which buffers hold a result and who may read them
-enum class FrameKind { Flat, Field, Column, Liquid };
+enum class FrameKind { Flat, Field, Column, Liquid, View };
 
 // The visualiser's frame (sph_frame.hip; kernels: render.hip).  The first render of an image size allocates the
 // per-pixel depth bits, hit count and static box-edge layer and the RGB8 frame, on the device and in pinned memory.
@@ -428,6 +430,21 @@ struct sph_handle {
     int pairCUs = 0;                 // compute units of the device (0: not asked yet)
     sph_host::CounterBlock pairCounters{kPairCounters}; // runs_staged, runs_direct, pairs
     sph_host::Pass pair;             // out: rows and edges on their way to the pinned buffers; seconds: clear + walk + join
+
+    // ---- sph_rays.hip ----
+    // Ray casting (rays.hip): the rays and their words on the device and the words in pinned memory, grown on demand by
+    // sph_cast_rays; the default path's pair of words per wave (a cast's or a view's, grown on demand) and the two
+    // counters they are added up in.
+    sph_host::DeviceBuf<SphRay> castRays;
+    sph_host::DeviceBuf<unsigned long long> castWords;
+    sph_host::PinnedBuf<unsigned long long> castWordsHost;
+    sph_host::DeviceBuf<unsigned long long> castPartials;
+    size_t castCap = 0, castWaveCap = 0; // rays the three buffers hold / waves castPartials holds
+    int castM = 0;                   // rays of the last sph_cast_rays
+    sph_host::CounterBlock castCounters{kCastCounters}; // layers, tests (default path)
+    sph_host::Pass cast;             // out: the words on their way to castWordsHost; seconds, calls: the casts' kernels
+    long long castViews = 0;         // views that ran the cast kernel
+    unsigned long long castRaysSum = 0, castPlainTests = 0; // rays of casts and views; rays x particles of the check path's
 };
 
 #define HIPCHK(h, call)                                                               \
@@ -516,6 +533,14 @@ int label_bodies(sph_handle *h, float link, const char *who);
 // launches over the labelling the handle holds, the copies, the SphBodyMeasureStats accounting.  sph_track_bodies
 // (sph_body_tracks.hip) measures through it too.
 int measure_labelled(sph_handle *h, uint32_t max_bodies, const char *who);
+// sph_rays.hip: what sph_cast_rays and sph_render_view (sph_frame.hip) share -- the spheres' radius of an option (a
+// message or null); whether SPH_CAST_PLAIN asks for the check path, which admits `rays` of them or ends the call with
+// SPH_EINVAL; the stream, the spheres and the default path's wave words and counters (grown and allocated here) into A,
+// whose rays / cam / m are set; the accounting behind a launch
+const char *bad_cast_radius(const sph_handle *h, float radius);
+int cast_path(sph_handle *h, size_t rays, bool &plain);
+int cast_prepare(sph_handle *h, CastArgs &A, float radius, bool plain);
+void cast_account(sph_handle *h, const CastArgs &A, bool plain);
 // sph_readback.hip
 void sdma_init(sph_handle *h);
 int sdma_wait(sph_handle *h, int slot);

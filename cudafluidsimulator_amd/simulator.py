@@ -599,6 +599,64 @@ class Simulator:
         self._check(self._L.sph_get_pair_stats(self._h, C.byref(st), 1 if reset else 0), "sph_get_pair_stats")
         return dict(calls=st.calls, pairs=st.pairs, runs_staged=st.runs_staged, runs_direct=st.runs_direct, seconds=st.seconds)
 
+    # -- ray casting: what a line of sight hits first, and a frame from any camera (sph_cast_rays, sph_render_view) --
+    def cast_words(self, origins, directions, t_min=0.0, t_max=np.inf, radius=0.0):
+        """(m,) uint64 of its own: per ray o + t d the word (bits(t) << 32) | id of the nearest sphere it enters with
+        t_min <= t <= t_max, _lib.CAST_MISS where there is none.  origins, directions: (m, 3); t_min, t_max: numbers or
+        (m,) arrays; radius: of the spheres (0: 0.5 h)."""
+        o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+        rays = np.zeros(len(o), _lib.ray_dtype())
+        rays["o"] = o
+        rays["d"] = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
+        rays["t_min"], rays["t_max"] = t_min, t_max
+        opt = _lib.SphCastOptions(C.sizeof(_lib.SphCastOptions), radius)
+        self._check(self._L.sph_cast_rays(self._h, rays.ctypes.data_as(C.POINTER(_lib.SphRay)), len(rays), C.byref(opt)), "sph_cast_rays")
+        words, m = C.POINTER(C.c_uint64)(), C.c_int(0)
+        self._check(self._L.sph_cast_host(self._h, C.byref(words), C.byref(m)), "sph_cast_host")
+        return _rows(words, m.value, None, np.uint64)
+
+    def cast_rays(self, origins, directions, t_min=0.0, t_max=np.inf, radius=0.0):
+        """(t, ids): (m,) float32 and (m,) int64 of cast_words()' words, inf / -1 for a miss."""
+        words = self.cast_words(origins, directions, t_min, t_max, radius)
+        miss = words == np.uint64(_lib.CAST_MISS)
+        t = (words >> np.uint64(32)).astype(np.uint32).view(np.float32)
+        ids = (words & np.uint64(0xFFFFFFFF)).astype(np.int64)
+        return np.where(miss, np.float32(np.inf), t), np.where(miss, -1, ids)
+
+    def render_view(self, eye, target, up=(0.0, 1.0, 0.0), width=0, height=0, tan_half=(0.0, 0.0), near=0.0, far=0.0, radius=0.0,
+                    shade="flat", lo=0.0, hi=0.0, light=(0.0, 0.0, 0.0), edge_radius=0.0):
+        """Queue one lit frame of the current state from a pinhole camera at `eye` looking at `target`; does not block.
+        frame_host() serves its RGB, view_buffer() its words.  tan_half: (x, y) tangents of the half angles (both 0:
+        45 degrees in y, x by the aspect ratio); near / far: the rays' window (0: h / inf); shade: "flat", "speed",
+        "density", "pressure" over lo..hi (both 0: the range over all particles); light: towards the light, in world
+        space (all 0: the default); edge_radius: of the box edges (0: 0.002 boxDim; negative: none)."""
+        o = _lib.SphViewOptions()
+        o.struct_size = C.sizeof(_lib.SphViewOptions)
+        o.width, o.height = int(width), int(height)
+        o.eye[:], o.target[:], o.up[:] = [float(v) for v in eye], [float(v) for v in target], [float(v) for v in up]
+        o.tan_half_x, o.tan_half_y = float(tan_half[0]), float(tan_half[1])
+        o.near, o.far, o.radius = float(near), float(far), float(radius)
+        o.shade = _lib.VIEW_SHADES[shade] if isinstance(shade, str) else int(shade)
+        o.value_lo, o.value_hi = float(lo), float(hi)
+        o.light[:] = [float(v) for v in light]
+        o.edge_radius = float(edge_radius)
+        self._check(self._L.sph_render_view(self._h, C.byref(o)), "sph_render_view")
+
+    def view_buffer(self):
+        """(H, W) uint64: the word of each pixel's ray of the last view frame (cast_words()' words)."""
+        h, w = self._frame_size()[1:]
+        out = np.zeros((h, w), np.uint64)
+        self._check(self._L.sph_download_view_buffer(self._h, out.ctypes.data_as(C.POINTER(C.c_uint64))), "sph_download_view_buffer")
+        return out
+
+    def cast_stats(self, reset=False):
+        """dict(calls, rays, layers, tests, seconds): sums since create or the last reset over casts and views; `layers`
+        and `tests` count the grid layers looked into and the ray-particle pairs tested, `seconds` is the GPU time of
+        cast_rays()' kernels (a view's is in render_time())."""
+        st = _lib.SphCastStats()
+        self._check(self._L.sph_get_cast_stats(self._h, C.byref(st), 1 if reset else 0), "sph_get_cast_stats")
+        return dict(calls=st.calls, rays=st.rays, layers=st.layers, tests=st.tests, seconds=st.seconds)
+
     def phase(self, name):
         self._check(getattr(self._L, "sph_phase_" + name)(self._h), "sph_phase_" + name)
 

@@ -73,6 +73,8 @@ struct SphBodyFate;
 struct SphBodyEdge;
 struct SphBodyTrackSummary;
 struct SphPairBinRaw;
+struct SphRay;
+struct SphViewOptions;
 
 class Simulator {
   private:
@@ -165,6 +167,15 @@ class Simulator {
     // simulator, valid until the next pairStatistics; sph_pair_values turns them into floats.  Any out-pointer may be
     // NULL.  false (with a message on stderr) with SPH_GPUS > 1 and where the library answers SPH_ESTATE or SPH_EINVAL.
     bool pairStatistics(int bins, float radius, const SphPairBinRaw **rows, const float **edges2, int *numBins);
+    // What lines of sight hit first (sph_cast_rays in sph_c_api.h): m rays against the particles as spheres of `radius`
+    // (0: 0.5 h; else 0 < radius <= h); m words (bits(t) << 32) | id in the caller's order, SPH_CAST_MISS for a miss,
+    // owned by the simulator, valid until the next castRays.  false (with a message on stderr) with SPH_GPUS > 1 and
+    // where the library answers SPH_ESTATE or SPH_EINVAL.
+    bool castRays(const SphRay *rays, int m, float radius, const uint64_t **words);
+    // A lit frame of the current state from any pinhole camera (sph_render_view in sph_c_api.h), owned by the simulator,
+    // valid until the next render.  NULL (with a message on stderr) with SPH_GPUS > 1 and where the library answers
+    // SPH_ESTATE or SPH_EINVAL.
+    const unsigned char *renderView(const SphViewOptions &view, int *width, int *height);
     // The velocities of the current state (sph_download_state), n x 3 floats in particle-id order, into the caller's
     // buffer.  false with SPH_GPUS > 1 and before setup().
     bool getVelocity(float *vel_xyz);

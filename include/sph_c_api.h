@@ -1030,6 +1030,89 @@ typedef struct SphPairStats {
 /* Sums since create or since the last reset.  Blocks. */
 int sph_get_pair_stats(sph_handle *h, SphPairStats *out, int reset);
 
+/* ---- ray casting: what a line of sight hits first, and a lit frame from any pinhole camera ----
+ * Additive to version 3: test for SPH_HAS_RAY_CAST.  Defined to the bit in DESIGN.md section 10n ("Ray casting"); all
+ * fp32, every operation rounded on its own in both math modes, nothing but + - x / sqrtf, comparisons, selects and
+ * conversions.  Every particle is a sphere of `radius` r, r2 = r r; a particle is visible when each coordinate p has
+ * p >= 0 and p / h < numCellsPerDim: rows outside the grid and rows that are not finite are hit by no ray.  A ray is
+ * o + t d, d not normalised, dd = (dx dx + dy dy) + dz dz; it is valid when o and d are finite, 0 <= t_min <= t_max
+ * (t_max may be +inf), 2^-40 <= dd <= 2^40 and |o_a| <= 64 (numCellsPerDim h) on every axis; an invalid ray is not an
+ * error: it misses.  Ray and visible particle p with id i: e = p - o, b = (ex dx + ey dy) + ez dz, tc = b / dd,
+ * f = e - tc d, b2 = (fx fx + fy fy) + fz fz, a2 = r2 - b2; nothing unless a2 > 0; t = tc - sqrtf(a2 / dd); nothing
+ * unless t_min <= t <= t_max (a NaN fails every test); t == 0 is stored as +0.  The pair's word is
+ * (bits(t) << 32) | i, the ray's word the minimum over all pairs, 0xFFFFFFFFFFFFFFFF where there is none: the nearest
+ * entry, among equal entries the smallest id.  Entries only: a ray that starts inside a sphere does not see it. */
+#define SPH_HAS_RAY_CAST 1
+#define SPH_CAST_MAX_RAYS (1 << 24)
+#define SPH_CAST_MISS 0xFFFFFFFFFFFFFFFFull
+typedef struct SphRay { /* 32 bytes */
+    float o[3];
+    float t_min;
+    float d[3];
+    float t_max;
+} SphRay;
+typedef struct SphCastOptions {
+    int32_t struct_size;   /* = sizeof(SphCastOptions) */
+    float radius;          /* of the spheres; 0 = 0.5 h, else 0 < radius <= h */
+} SphCastOptions;
+/* Casts rays[0, m) against the state the handle holds NOW: blocks while the rays are uploaded, then queues the kernel
+ * and the copy of the m words.  opt == NULL: every default.  0 <= m <= SPH_CAST_MAX_RAYS.  State rules, grid handling
+ * and error codes are sph_sample_field's: the grid is found (phase 1) or built ahead (phase 0), the next step consumes
+ * it and no result of any step changes; SPH_ESTATE before any state, inside an open phase-split step, for
+ * SPH_FLAG_EXTERNAL_STATE handles, with SPH_SWEEP_LINKED and with SPH_KEY_MORTON; SPH_EINVAL for an unset struct_size,
+ * a bad radius, m out of range, a NULL rays with m > 0.  No particles: every ray misses.  The default path walks the
+ * cell grid along each ray, one lane per ray.  SPH_CAST_PLAIN=1 in the environment selects the check path, here and in
+ * sph_render_view: one thread per ray tests every row of the stream (identical words); admitted while rays x particles
+ * <= 2^32, SPH_EINVAL beyond. */
+int sph_cast_rays(sph_handle *h, const SphRay *rays, int m, const SphCastOptions *opt);
+/* The words of the last sph_cast_rays in the caller's order, owned by the handle, valid until the next one.  Blocks
+ * until the copy has landed.  Any out-pointer may be NULL; *words may be NULL where m == 0.  SPH_ESTATE before the
+ * first sph_cast_rays. */
+int sph_cast_host(sph_handle *h, const uint64_t **words, int *m);
+/* The view frame.  The basis is computed once, on the host, in fp32: g = target - eye, fwd = g / |g|, s0 = fwd x up,
+ * s = s0 / |s0|, u = s x fwd.  Through the centre of pixel (c, row), row 0 on top, runs the ray o = eye,
+ * d = (fwd + ax s) + ay u, ax = tan_half_x ((c + 0.5) / (0.5 W) - 1), ay the same from (H - 1 - row) and tan_half_y,
+ * t_min = near, t_max = far: t is the depth along the view axis.  With eye (5, 5, 15), target (5, 5, 0), up (0, 1, 0)
+ * and both tans 2 these are the rays of the column and liquid frames.  The picture, RGB8, row 0 first: the sphere the
+ * ray enters first, lit by one diffuse light, in a flat colour or the field frame's colour of its particle; white
+ * where one of the box's twelve edges, a cylinder of edge_radius, is not behind it; else black. */
+enum {
+    SPH_VIEW_FLAT = 0,     /* every sphere (0.1, 0.35, 0.9) */
+    SPH_VIEW_FIELD = 1     /* SPH_VIEW_FIELD + SPH_FIELD_*: the field frame's ramp of that field of the sphere's particle */
+};
+typedef struct SphViewOptions {
+    int32_t struct_size;   /* = sizeof(SphViewOptions) */
+    int32_t width, height; /* 0 = 800 x 600; at most 4096 x 4096 */
+    float eye[3], target[3], up[3]; /* finite; target - eye and (target - eye) x up must not vanish */
+    float tan_half_x, tan_half_y;   /* both 0: tan_half_y = 0.41421357 (45 degrees), tan_half_x = tan_half_y W / H; else both > 0, at most 1024 */
+    float near, far;       /* the ray's t window; near 0 = h; far 0 = +inf; else 0 < near <= far */
+    float radius;          /* of the spheres; 0 = 0.5 h, else 0 < radius <= h */
+    int32_t shade;         /* SPH_VIEW_* */
+    float value_lo;        /* a field shade's colour scale, as SphFieldFrameOptions': both 0 = the minimum and */
+    float value_hi;        /* maximum over ALL particles, reduced on the device */
+    float light[3];        /* the direction towards the light in world space; all 0 = (-0.35, 0.8, 0.5); finite */
+    float edge_radius;     /* of the box edges; 0 = 0.002 boxDim; negative: no edges */
+} SphViewOptions;
+/* sph_cast_rays' state rules and grid handling, sph_render_frame's queueing: does not block.  opt == NULL: SPH_EINVAL
+ * (a camera has to be given).  A bad size, camera, window, radius, shade, range, light or edge_radius: SPH_EINVAL.
+ * sph_frame_host serves the RGB and sph_get_render_time counts the frame; the other kinds' download and range calls
+ * return SPH_ESTATE after it.  A flat, field, column or liquid frame rendered afterwards is what it would have been
+ * without it. */
+int sph_render_view(sph_handle *h, const SphViewOptions *opt);
+/* The words behind the last view frame, width x height, row 0 first.  SPH_ESTATE if the last render was not a view
+ * frame. */
+int sph_download_view_buffer(sph_handle *h, uint64_t *words);
+typedef struct SphCastStats {
+    int32_t struct_size, pad_;  /* sizeof(SphCastStats), 0: both written by the call */
+    int64_t calls;              /* sph_cast_rays and sph_render_view calls that ran a kernel (either path) */
+    uint64_t rays;              /* rays of those calls (a view: width x height) */
+    uint64_t layers;            /* grid layers the default path's lanes looked into (check path: 0) */
+    uint64_t tests;             /* ray-particle pairs tested; the check path: rays x particles */
+    double seconds;             /* GPU time of sph_cast_rays' kernels (a view's is sph_get_render_time's) */
+} SphCastStats;
+/* Sums since create or since the last reset.  Blocks. */
+int sph_get_cast_stats(sph_handle *h, SphCastStats *out, int reset);
+
 const char *sph_build_info(void);
 
 #ifdef __cplusplus
